@@ -13,9 +13,12 @@ trace commitment is all-gathered and its bytes gathered on rank 0 over RCCL -- p
 been proven AND exchanged.  `python bench.py --gpus N` without a launcher starts the N ranks itself (one child process
 per GPU, before the parent touches the GPU); under `torch.distributed.run` it uses the ranks it is given.
 
-Prints ONE JSON line (see the task contract) including `roofline` for the dominant kernel and
-`cpu_baseline` (the optimised CPU prover oracle/fast proving the full instance of pipeline 0 on the host cores,
-measured; rank 0, N=1; its proof bytes are compared with the GPU's).
+Prints ONE JSON line (see the task contract).  A plain run sets up, warms up, times the --steps proofs, writes the last
+step's proof when --dump-outputs DIR is given, and prints the headline.  `--full` adds everything reported beside it:
+`roofline` for the dominant kernel (per-kernel HIP events in the timed region), per-stage times of a proof running alone,
+the host verification of the last proof, the aggregation of the last step, the guest flows, and `cpu_baseline` (the
+optimised CPU prover oracle/fast proving the full instance of pipeline 0 on the host cores, measured; rank 0, N=1; its
+proof bytes are compared with the GPU's).
 """
 import argparse
 import json
@@ -46,7 +49,15 @@ def parse():
     ap.add_argument("--inflight", type=int, default=3,
                     help="independent proofs in flight per GPU, each on its own HIP stream (segments of a chunk are "
                          "independent): memory-bound stages of one overlap the VALU-bound hashing of the other")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what is reported beside the headline: kernel and roofline figures, per-stage times, "
+                         "verification of the last proof, aggregation, guest flows, CPU baseline (off: only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the proof of the last step (rank 0) to DIR/proof.npy: its u32 words as float64")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def visible_gpu_count():
@@ -172,6 +183,12 @@ def cpu_baseline(args, params, airs, host_traces, pvs, gpu_proof):
                          "EQUAL" if same else "DIFFER FROM")}
 
 
+def progress(msg):
+    """--full: a line on stderr per finished part (the full run takes minutes; the JSON line on stdout comes last)"""
+    sys.stderr.write("bench.py: %s\n" % msg)
+    sys.stderr.flush()
+
+
 def _flow_runs(cmd, env):
     """warm-up run + three measured runs of one guest flow; returns (warm-up, the measured run of MEDIAN instructions per second, all three rates)"""
     import subprocess
@@ -180,8 +197,10 @@ def _flow_runs(cmd, env):
         return g["total_cycles"] / ((g["segment_tracegen_and_proving_ms"] + g["aggregation_setup_wait_ms"] + g["aggregation_ms"]) / 1e3)
 
     runs = []
-    for _ in range(4):
+    for k in range(4):
+        t0 = time.time()
         r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
+        progress("%s: run %d of 4, rc %d, %.1f s" % (" ".join(os.path.basename(c) for c in cmd[1:]), k + 1, r.returncode, time.time() - t0))
         if r.returncode != 0:
             raise RuntimeError(r.stderr[-300:])
         runs.append(json.loads(r.stdout.strip().splitlines()[-1]))
@@ -322,7 +341,7 @@ def devices_flow_before_the_ranks_touch_the_gpu(args, plumbing):
     """N > 1: the one-task-over-N-GPUs flow runs ONCE, while no rank uses a GPU: in the launcher (`python bench.py --gpus N`) before it
     starts its ranks -- handed to them in ZKHIP_BENCH_DEVICES_FLOW --, or, under torch.distributed.run, in rank 0 before it loads torch,
     the other ranks waiting for its flag file (named after MASTER_PORT) before they load theirs.  Returns the block (rank 0) or None."""
-    if args.no_guest_flow or args.gpus < 2:
+    if not args.full or args.no_guest_flow or args.gpus < 2:
         return None
     if "ZKHIP_BENCH_DEVICES_FLOW" in os.environ:
         return json.loads(os.environ["ZKHIP_BENCH_DEVICES_FLOW"]) if os.environ.get("RANK", "0") == "0" else None
@@ -344,7 +363,7 @@ def devices_flow_before_the_ranks_touch_the_gpu(args, plumbing):
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        if not args.no_guest_flow and os.environ.get("ZKHIP_BENCH_DRYRUN_1GPU") != "1":
+        if args.full and not args.no_guest_flow and os.environ.get("ZKHIP_BENCH_DRYRUN_1GPU") != "1":
             os.environ["ZKHIP_BENCH_DEVICES_FLOW"] = json.dumps(guest_flow_devices(args.gpus, os.environ.get("ZKHIP_BENCH_PLUMBING_ONLY") == "1"))
         sys.exit(spawn_ranks(args))
     plumbing = os.environ.get("ZKHIP_BENCH_PLUMBING_ONLY") == "1"
@@ -352,7 +371,7 @@ def main():
     guest = guest_chunk = guest_mixed = guest_mixed19 = guest_mem = None
     # (child processes: only before torch / HIP are loaded here, and never under a profiler -- its preloaded library has initialised the GPU
     # before this program starts; the profiling recipes pass --no-cpu-baseline or --no-guest-flow, either of which skips the guest flows)
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and not plumbing and not args.no_guest_flow and not args.no_cpu_baseline and "torch" not in sys.modules:
+    if args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not plumbing and not args.no_guest_flow and not args.no_cpu_baseline and "torch" not in sys.modules:
         guest = guest_flow()
         guest_chunk = guest_flow(chunk_config=True)
         guest_mixed = guest_flow_mixed()
@@ -489,9 +508,10 @@ def main():
             torch.cuda.synchronize()
 
     run(args.warmup)
-    for c in ctxs:
-        c.profile_reset()
-    ctx.profile_enable(True)  # per-kernel HIP events on pipeline 0's stream
+    if args.full:
+        for c in ctxs:
+            c.profile_reset()
+        ctx.profile_enable(True)  # per-kernel HIP events on pipeline 0's stream
     if world > 1:
         barrier()
     torch.cuda.synchronize()
@@ -501,6 +521,48 @@ def main():
     if world > 1:
         barrier()
     t1 = time.perf_counter()
+    dt = t1 - t0
+    if world > 1:
+        tmax = torch.tensor([dt], dtype=torch.float64, device=coll_dev)
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        dt = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    head = {
+        "metric": "chunk STARK proofs/sec (2^%d-row trace)" % log_n,
+        "value": round(world * args.steps / dt, 4),
+        "unit": "proofs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 2),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic",
+        "config": {"workload": "full STARK proof: 2^%d x %d degree-3 AIR + 2^%d x 2 Fibonacci AIR, blow-up 2, "
+                               "%d queries, PoW %d+%d (SURVEY.md 8(d) cfg #4)"
+                               % (log_n, width, log_n, params[2], params[3], params[4]),
+                   "proof_bytes": pk.proof_size,
+                   "resident_key_bytes_per_pipeline": pk.workspace_bytes,
+                   "inflight_per_gpu": n_pipe,
+                   "commit_pipeline_parts": max(0, args.commit_parts),
+                   "exchange": None if world == 1 else {
+                       "posted_per_rank": xstat["posted"], "mode": "asynchronous per proof (side stream), completed inside the timed region",
+                       "ms_blocked_at_end_of_timed_region": round(xstat["wait_s"] * 1e3, 3),
+                       "bytes_per_proof": "32 x %d all-gather + %d gather to rank 0" % (world, pk.proof_size),
+                       "backend": "gloo (dry run)" if dry else (coll_note or "RCCL (nccl backend), device tensors")},
+                   "parallelism": "%d independent proof(s) in flight per GPU (one HIP stream each)" % n_pipe + (", RCCL all-gather of commitments + proof gather" if world > 1 else "")
+                                  + (" [DRY RUN: all ranks on one GPU, gloo -- not a measurement]" if dry else "")},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    progress("timed steps: %.2f ms per step; the figures beside the headline follow" % (dt / args.steps * 1e3))
     ctx.profile_enable(False)
     stats_timed = ctx.profile_read()
     # per-stage breakdown: two more proofs on pipeline 0 ALONE (outside the timed region), so that each
@@ -523,11 +585,6 @@ def main():
     pvs = pipes[last_i % n_pipe]["pvs"]
     last_gathered = xstat.get("last_gathered")
     steps_profiled = len(range(0, args.steps, n_pipe))  # proofs that ran on pipeline 0
-    dt = t1 - t0
-    if world > 1:
-        tmax = torch.tensor([dt], dtype=torch.float64, device=coll_dev)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        dt = float(tmax.item())
     stats = stats_timed
 
     # every rank checks its own last proof with the host verifier (outside the timed region)
@@ -672,34 +729,11 @@ def main():
         hbm_whole = {"bound": "hbm", "algorithmic_bytes_per_proof": alg_proof, "achieved": round(alg_proof / per_gpu_s / 1e9, 1),
                      "peak": 8000.0, "unit": "GB/s", "frac": round(alg_proof / per_gpu_s / 8e12, 4),
                      "floor_ms_at_6.3TBps": round(alg_proof / 6.3e12 * 1e3, 2)}
-        out = {
-            "metric": "chunk STARK proofs/sec (2^%d-row trace)" % log_n,
-            "value": round(world * args.steps / dt, 4),
-            "unit": "proofs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 2),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32",
-            "data": "synthetic",
-            "config": {"workload": "full STARK proof: 2^%d x %d degree-3 AIR + 2^%d x 2 Fibonacci AIR, blow-up 2, "
-                                   "%d queries, PoW %d+%d (SURVEY.md 8(d) cfg #4)"
-                                   % (log_n, width, log_n, params[2], params[3], params[4]),
-                       "proof_bytes": pk.proof_size, "verified": ok,
-                       "resident_key_bytes_per_pipeline": pk.workspace_bytes,
-                       "inflight_per_gpu": n_pipe,
-                       "commit_pipeline_parts": max(0, args.commit_parts),
-                       "exchange": None if world == 1 else {
-                           "posted_per_rank": xstat["posted"], "mode": "asynchronous per proof (side stream), completed inside the timed region",
-                           "ms_blocked_at_end_of_timed_region": round(xstat["wait_s"] * 1e3, 3),
-                           "ms_one_blocking_exchange_alone": round(exchange_alone_ms, 3),
-                           "bytes_per_proof": "32 x %d all-gather + %d gather to rank 0" % (world, pk.proof_size),
-                           "backend": "gloo (dry run)" if dry else (coll_note or "RCCL (nccl backend), device tensors")},
-                       "parallelism": "%d independent proof(s) in flight per GPU (one HIP stream each)" % n_pipe + (", RCCL all-gather of commitments + proof gather" if world > 1 else "")
-                                      + (" [DRY RUN: all ranks on one GPU, gloo -- not a measurement]" if dry else "")},
+        out = dict(head)
+        out["config"]["verified"] = ok
+        if world > 1:
+            out["config"]["exchange"]["ms_one_blocking_exchange_alone"] = round(exchange_alone_ms, 3)
+        out.update({
             "roofline": roof,
             "roofline_other_kernels": others,
             "roofline_valu_whole_proof": valu_roof,
@@ -707,11 +741,12 @@ def main():
             "stage_ms_single_stream": {k: round(v[1] / 2, 3) for k, v in sorted(stats_alone.items(), key=lambda kv: -kv[1][1])},
             "stage_note": "per-kernel HIP-event times of one proof running alone (measured after the timed region); "
                           "`roofline` is from the timed region itself",
-        }
+        })
         if not args.no_aggregate and not args.no_cpu_baseline:
             # "gather of encoded proofs to rank 0 ... aggregation-tree proving of the gathered proofs runs on rank 0": the
             # proofs the ranks made in the last step, folded to ONE root under one aggregation key (zkvm-prover_amd/aggregate.py: leaf
             # node(s) over <= 4 proofs, wrapped by the internal circuit).  After the timed region; never part of `value`.
+            progress("aggregation of the last step")
             try:
                 from zkvm_prover_amd import aggregate
 
@@ -732,6 +767,7 @@ def main():
             except Exception as e:  # a reported extra, never a gate
                 out["aggregate"] = {"root_ms": None, "note": "failed: %r" % (e,)}
         if world == 1 and not args.no_cpu_baseline:
+            progress("CPU baseline (oracle/fast, two full-size proofs)")
             try:
                 # the instance of pipeline 0, fetched from the device: the CPU proves exactly what the GPU proved
                 p0 = pipes[0]
@@ -760,6 +796,16 @@ def main():
     if world > 1:
         dist.destroy_process_group()
 
+
+def dump_outputs(out_dir, proof):
+    """--dump-outputs DIR: what the timed path handed its caller in the last step -- the proof bytes of ProvingKey.fetch() --
+    as DIR/proof.npy, the proof's little-endian u32 words as float64 (exact).  The inputs are seeded, so two builds given
+    the same arguments can be compared word for word."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    words = np.frombuffer(bytes(proof) + b"\0" * (-len(proof) % 4), dtype="<u4")
+    np.save(os.path.join(out_dir, "proof.npy"), words.astype(np.float64))
 
 
 def valu_counts():

@@ -20,11 +20,24 @@ p3 Montgomery form keeps in memory (canonical = v * 2^-32 mod p).  `Proof<SC>` i
 The product-side codec of the same container is include/zkhip_codec.hpp; this Python twin exists so the fixture
 generator and the tests do not depend on the thing they check.
 """
+import os
 import struct
 
 P = 2013265921
 R_INV = pow(1 << 32, -1, P)
 R = (1 << 32) % P
+
+# the reference's eight stored proofs (ref_v1_vectors.json `sources`), decoded from base64 and committed under golden/ref_proofs;
+# the two prover/testdata files hold the same bytes as the verifier's *-phase1 files and are stored once
+STORED_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_proofs")
+STORED_SAME_AS = {"prover-chunk-proof.json": "chunk-proof-phase1.json", "prover-batch-proof.json": "batch-proof-phase1.json"}
+
+
+def stored_proof(name):
+    """(proofs, public_values) bytes of the stored reference proof `name`, e.g. "chunk-proof-feynman.json"."""
+    stem = os.path.join(STORED_DIR, STORED_SAME_AS.get(name, name)[:-len(".json")])
+    with open(stem + ".proofs.bin", "rb") as f, open(stem + ".public_values.bin", "rb") as g:
+        return f.read(), g.read()
 
 
 def from_monty(v):

@@ -24,7 +24,7 @@ def _run(extra_env, *argv):
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_bench_spawns_its_own_ranks(n):
-    r = _run({}, "--gpus", str(n), "--steps", "5", "--warmup", "1")
+    r = _run({}, "--gpus", str(n), "--steps", "5", "--warmup", "1", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -49,7 +49,7 @@ def test_bench_under_a_launcher_uses_the_given_ranks():
     for rank in range(2):
         env = dict(os.environ, ZKHIP_BENCH_PLUMBING_ONLY="1", RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2",
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3"],
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--full"],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=300) for p in procs]
     assert [p.returncode for p in procs] == [0, 0], outs

@@ -1,8 +1,7 @@
 """CPU: the product's codec of the reference's stored-proof container (include/zkhip_codec.hpp through the C ABI).
 
- * every stored reference proof decodes to the last byte and re-encodes to the identical bytes (all eight in the build
-   container from /root/reference; one committed copy everywhere), and the summary agrees with the independent
-   Python reader (tests/refproof_v1.py);
+ * every stored reference proof decodes to the last byte and re-encodes to the identical bytes (all eight, committed
+   under tests/golden/ref_proofs), and the summary agrees with the independent Python reader (tests/refproof_v1.py);
  * a proof of this backend (made by the oracle here -- byte-identical to the HIP prover's, tests/test_gpu_stark.py)
    converts to the v1 container and back without loss, for every proof flavour (plain, mixed heights, preprocessed,
    LogUp), and what comes back verifies;
@@ -21,7 +20,6 @@ import zkvm_prover_amd as z
 from zkvm_prover_amd import air
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference/crates"
 NOPV = np.zeros(0, np.uint32)
 PARAMS = (1, 0, 10, 0, 5)   # commit_pow_bits = 0: the v1 container carries no commit-phase witnesses
 
@@ -56,14 +54,12 @@ def test_committed_reference_proof_roundtrips_byte_exactly():
     assert z.proof_reencode_v1(blob[8:], z.V1_SINGLE) == blob[8:]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 def test_all_eight_reference_proofs_roundtrip_byte_exactly():
     with open(os.path.join(HERE, "golden", "ref_v1_vectors.json")) as f:
         sources = json.load(f)["sources"]
     assert len(sources) == 8
     for s in sources:
-        d = json.load(open(os.path.join(REF, s["file"])))
-        blob = base64.b64decode(d["proof"]["proofs"])
+        blob, _ = rp.stored_proof(s["name"])
         assert hashlib.sha256(blob).hexdigest() == s["sha256"]
         _check_blob(blob)
 

@@ -17,7 +17,7 @@ def test_bench_two_ranks_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1",
-                        "--log-rows", "16", "--width", "64", "--inflight", "2"], env=env, capture_output=True, text=True,
+                        "--log-rows", "16", "--width", "64", "--inflight", "2", "--full"], env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -42,7 +42,7 @@ def test_bench_under_torch_distributed_run_on_one_gpu():
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-                        "--log-rows", "14", "--width", "40", "--inflight", "2"], env=env, capture_output=True, text=True, timeout=900)
+                        "--log-rows", "14", "--width", "40", "--inflight", "2", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

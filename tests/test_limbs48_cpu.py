@@ -151,16 +151,15 @@ def test_batch_circuit_config_and_a_bls12_381_guest(tmp_path):
     # records of 12-word operands: op | a | b (25), op | x1 y1 x2 y2 | slope (61), op | a0 a1 | b0 b1 (49); adapter rows of 36 + 11 and 72 + 11 columns
     assert rec("mm_records_0").size == 5 * 25 and rec("mm_records_1").size == 17 and rec("ec_records_0").size == 2 * 61 and rec("fp2_records_0").size == 5 * 49
     assert rec("mmio_rows_0").size == 5 * 36 * 47 and rec("mmio_rows_1").size == 24 * 35 and rec("ecio_rows_0").size == 2 * 72 * 83 and rec("fp2io_rows_0").size == 5 * 72 * 83
-    # the reference's own file, where its tree is present (not on the GPU box): the same chip set
+    # the reference's own file (committed unchanged under tests/golden/ref_configs): the same chip set
     import os
-    ref = "/root/reference/crates/circuits/batch-circuit/openvm.toml"
-    if os.path.exists(ref):
-        out = tmp_path / "ref"
-        out.mkdir()
-        r = subprocess.run([v2.CLI, "dump-segments", str(tmp_path / "exe.bin"), str(tmp_path / "stdin.bin"), str(out), "10", "5", "7", ref], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        assert np.fromfile(out / "air_ids.u32", dtype=np.uint32).tolist() == ids
-        assert json.loads(r.stdout.strip().splitlines()[-1])["public_values"] == info["public_values"]
+    ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_configs", "batch-circuit.openvm.toml")
+    out = tmp_path / "ref"
+    out.mkdir()
+    r = subprocess.run([v2.CLI, "dump-segments", str(tmp_path / "exe.bin"), str(tmp_path / "stdin.bin"), str(out), "10", "5", "7", ref], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert np.fromfile(out / "air_ids.u32", dtype=np.uint32).tolist() == ids
+    assert json.loads(r.stdout.strip().splitlines()[-1])["public_values"] == info["public_values"]
 
 
 def test_ecc_and_fp2_chips_48_limbs_python_twins_satisfy_the_airs():

@@ -3,7 +3,6 @@ proofs (tests/golden/ref_v1_vectors.json, made by tests/golden/gen_ref_vectors.p
 /root/reference/crates/{verifier/testdata/proofs,prover/testdata}/*.json).  This is what pins the Poseidon2 permutation,
 TruncatedPermutation, PaddingFreeSponge, MerkleTreeMmcs (mixed heights) and the FRI fold to the reference's prover:
 none of the expected values below was produced by code of this repository."""
-import base64
 import ctypes as C
 import hashlib
 import json
@@ -119,21 +118,16 @@ def test_fri_layer_leaves(ora, vec):
         assert z.mmcs_verify(lf["root"], [lf["log_height"]], [8], lf["index"], lf["opening"]) == 0
 
 
-REF = "/root/reference/crates"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 def test_fixture_matches_reference_files(vec):
-    """In the build container: the fixture's sources are the reference's files, byte for byte, and the Python twin of
-    the container codec round-trips them."""
+    """The fixture's sources are the reference's stored proofs (committed under golden/ref_proofs), byte for byte, and
+    the Python twin of the container codec round-trips them."""
     for s in vec["sources"]:
-        d = json.load(open(os.path.join(REF, s["file"])))
-        blob = base64.b64decode(d["proof"]["proofs"])
+        blob, pv_blob = rp.stored_proof(s["name"])
         assert hashlib.sha256(blob).hexdigest() == s["sha256"]
         proofs = rp.decode_proofs(blob)
         assert len(proofs) == 1 and rp.encode_proofs(proofs) == blob
         assert rp.shape_of(proofs[0])["n_queries"] == vec["shapes"][s["name"]]["n_queries"]
-        pv = rp.decode_public_values(base64.b64decode(d["proof"]["public_values"]))
+        pv = rp.decode_public_values(pv_blob)
         assert len(pv) == 32 and all(rp.from_monty(v) < 256 for v in pv)  # 32 user public values, one byte each
 
 

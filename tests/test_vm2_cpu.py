@@ -388,15 +388,13 @@ def test_all_extensions_of_the_chunk_circuit_in_one_statement(tmp_path):
 
 
 def test_the_reference_config_file_itself_gives_the_same_chip_set(tmp_path):
-    """crates/circuits/chunk-circuit/openvm.toml as it lies in the reference tree (read here only; skipped where the tree is absent, e.g. on
-    the GPU box) goes through the executor's configuration reader: the chip ids, the heights and the run of the all-extensions guest are
-    those of this repository's restatement of that file (test_vm_cpu.chunk_circuit_toml) -- 51 chips."""
+    """the reference's crates/circuits/chunk-circuit/openvm.toml (committed unchanged as tests/golden/ref_configs/chunk-circuit.openvm.toml)
+    goes through the executor's configuration reader: the chip ids, the heights and the run of the all-extensions guest are those of this
+    repository's restatement of that file (test_vm_cpu.chunk_circuit_toml) -- 51 chips."""
     import subprocess
     from test_vm_cpu import chunk_circuit_toml
 
-    ref = "/root/reference/crates/circuits/chunk-circuit/openvm.toml"
-    if not os.path.exists(ref):
-        pytest.skip("no reference tree here")
+    ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_configs", "chunk-circuit.openvm.toml")
     words, data = all_extensions_program(True), all_extensions_data()
     (tmp_path / "exe.bin").write_bytes(rv.exe_bytes(words, data=data))
     (tmp_path / "stdin.bin").write_bytes(b"")

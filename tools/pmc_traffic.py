@@ -1,5 +1,5 @@
 """Builds profiles/roundNN_pmc_traffic.json from two rocprofv3 counter passes over the same bench command:
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d A -o f --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --inflight 1
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d A -o f --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --inflight 1
     rocprofv3 --kernel-trace --pmc WRITE_SIZE -d B -o w --output-format csv -- python3 bench.py ... (same)
     python tools/pmc_traffic.py A/f_counter_collection.csv B/w_counter_collection.csv N_PROOFS out.json
 HBM traffic per kernel per proof = FETCH_FACTOR * FETCH_SIZE + WRITE_SIZE (both reported in KiB... see `correction`)."""
@@ -85,7 +85,7 @@ def main():
             entry.update({"fetch_factor": factor, "hbm_bytes_per_proof_corrected": round((factor * f_kb + w_kb) * 1024)})
         kernels[k.replace("void ", "")] = entry
     json.dump({"source": "tools/pmc_traffic.py over two rocprofv3 --kernel-trace --pmc passes (FETCH_SIZE, WRITE_SIZE) of "
-                         "`python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --inflight 1` (%d proofs per run)" % n_proofs,
+                         "`python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --inflight 1` (%d proofs per run)" % n_proofs,
                "correction": CORRECTION, "kernels": kernels}, open(out, "w"), indent=1)
     for k, v in list(kernels.items())[:8]:
         print("%-40s %8.2f GB per proof" % (k[:40], v["hbm_bytes_per_proof_corrected"] / 1e9))

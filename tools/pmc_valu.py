@@ -1,5 +1,5 @@
 """Builds profiles/roundNN_pmc_valu.json from one rocprofv3 counter pass:
-    rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES -d D -o v --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --inflight 1
+    rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES -d D -o v --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --inflight 1
     python tools/pmc_valu.py D/v_counter_collection.csv D/v_kernel_trace.csv N_PROOFS out.json
 Per kernel and per proof: VALU instructions issued (wave granularity), waves, kernel time, and the time the same
 instructions would take at the row-hash kernel's measured issue rate -- a whole-proof VALU roofline."""
@@ -32,7 +32,7 @@ def main():
                       "ms_per_proof_under_pmc": round(dur[k] / n_proofs, 3), "ms_at_hash_issue_rate": round(i / rate * 1e3, 3)}
         tot_i += i
         tot_ms += i / rate * 1e3
-    json.dump({"source": "tools/pmc_valu.py over rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES of `python3 bench.py --steps 1 "
+    json.dump({"source": "tools/pmc_valu.py over rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES of `python3 bench.py --full --steps 1 "
                          "--warmup 0 --no-cpu-baseline --inflight 1` (%d proofs per run)" % n_proofs,
                "hash_issue_rate_wave_instr_per_s": rate,
                "total_valu_wave_instr_per_proof": round(tot_i), "total_ms_at_hash_issue_rate": round(tot_ms, 2),

@@ -1,4 +1,4 @@
-"""profiles/round03_pmc_valu.json from rocprofv3 counter passes of `python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --inflight 1`
+"""profiles/round03_pmc_valu.json from rocprofv3 counter passes of `python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --inflight 1`
 (separate --pmc runs, as /opt/skills/guides/MI355X_MICROARCH.md prescribes): per kernel and per launch the VALU wave-instructions
 (SQ_INSTS_VALU), waves, the SQ's VALU-active and busy cycle counters, and the kernel's duration under the profiler; for the kernels
 with an ISA mix (tools/isa_mix.py) the ABSOLUTE VALU roofline: wave-instructions x model cycles per wave-instruction / (1024 SIMDs x
@@ -87,7 +87,7 @@ def main():
     totals = {"total_valu_wave_instr_per_proof": round(total_instr)}
     if cpi:
         totals["total_valu_roofline_ms_per_proof"] = round(total_instr * cpi / (SIMDS * CLOCK_HZ) * 1e3, 3)
-    json.dump({**totals, "source": "tools/pmc_valu3.py over separate rocprofv3 --pmc passes of `python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline "
+    json.dump({**totals, "source": "tools/pmc_valu3.py over separate rocprofv3 --pmc passes of `python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "
                          "--inflight 1` (%d proofs per run)" % n_proofs,
                "peak": {"simds": SIMDS, "clock_hz": CLOCK_HZ},
                "note": "valu_roofline_ms_per_launch = SQ_INSTS_VALU x (4.2 cycles for the multiply-class share + 2.2 for the rest; shares from the "
