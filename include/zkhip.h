@@ -515,6 +515,40 @@ int zkhip_fri_fold_row(uint64_t index, unsigned log_height, const uint32_t beta[
  * F_p[X]/(X^4 - 11); ZKHIP_OK = balanced, ZKHIP_ERR_VERIFY = not */
 int zkhip_logup_exposed_check(const uint32_t *exposed, size_t n);
 
+/* ---- LogUp-GKR (docs/logup_gkr.md): the fractional-sum GKR proof of a tree of 2^log_n fractions num[i] / den[i] (Papini-Habock
+ *      2023), the bus argument of the pinned backend's v2 form, in this library's transcript.  Proof words (canonical, in transcript
+ *      order): root (P, Q), then per layer k = 0..log_n-1 the k round polynomials s(0), s(2), s(3) and the four layer values;
+ *      zkhip_gkr_proof_words(log_n) = 8 + 16 log_n + 6 log_n (log_n - 1).  What the proof reduces to -- the point (log_n extension
+ *      elements, lowest variable first) and the claims (num~, den~) of the leaves' multilinear extensions there -- is returned to
+ *      the caller, who discharges it. ---- */
+#define ZKHIP_GKR_MAX_LOG_N 28
+size_t zkhip_gkr_proof_words(unsigned log_n);
+/* d_num: 2^log_n numerators (device, Montgomery; base field, or extension elements when num_is_ext); d_den: 2^log_n extension
+ * denominators.  The transcript continues from whatever the caller observed into it.  The whole proof is issued on the ctx
+ * stream and read back once: proof_out (cap >= zkhip_gkr_proof_words words), point_out (4 log_n words) and claims_out
+ * (num~, den~: 8 words), canonical, on the HOST.  1 <= log_n <= ZKHIP_GKR_MAX_LOG_N. */
+int zkhip_gkr_fraction_prove(zkhip_ctx *ctx, zkhip_transcript *transcript, const uint32_t *d_num, int num_is_ext,
+                             const uint32_t *d_den, unsigned log_n, uint32_t *proof_out, size_t cap, uint32_t *point_out,
+                             uint32_t *claims_out);
+/* host verifier: a fresh challenger observes `prefix` (n_prefix canonical words), then replays the proof.  ZKHIP_OK with the point
+ * and the claims the proof reduces to; ZKHIP_ERR_VERIFY if a check fails, a word is not canonical or `words` is not the length
+ * for log_n.  Needs no device. */
+int zkhip_gkr_fraction_verify(const uint32_t *prefix, size_t n_prefix, const uint32_t *proof, size_t words, unsigned log_n,
+                              uint32_t *point_out, uint32_t *claims_out);
+/* The bus argument of a key: leaves are the (signed count, gamma + bus + 1 + sum_i beta^(i+1) f_i) pairs of every interaction of
+ * every row, chips with interactions in key order, interactions in program order, rows 0..N-1, padded with (0, 1) to
+ * 2^zkhip_bus_gkr_log_leaves(pk).  gamma, beta = two extension samples after the caller's prefix (as in the v1 LogUp phase).
+ * 0 when the key has no interactions. */
+unsigned zkhip_bus_gkr_log_leaves(const zkhip_pk *pk);
+/* traces and public values as in zkhip_prove; the transcript holds the caller's prefix.  Writes proof_out (canonical words, cap
+ * >= zkhip_gkr_proof_words(log_leaves)) and *words_out.  Uses buffers of its own: a zkhip_prove of the same key is unaffected. */
+int zkhip_bus_gkr_prove(zkhip_ctx *ctx, const zkhip_pk *pk, const uint32_t *const *d_traces, const uint32_t *const *pvs,
+                        zkhip_transcript *transcript, uint32_t *proof_out, size_t cap, size_t *words_out);
+/* host verifier of a bus proof: the challenges (gamma, beta: 8 canonical words), the point and the claims, after checking the
+ * GKR proof and the balance P = 0, Q != 0 (ZKHIP_ERR_VERIFY otherwise).  Needs no device. */
+int zkhip_bus_gkr_verify(const uint32_t *prefix, size_t n_prefix, const uint32_t *proof, size_t words, unsigned log_leaves,
+                         uint32_t *challenges_out, uint32_t *point_out, uint32_t *claims_out);
+
 /* Field offsets of a proof, in 32-bit words from its start (the layout is static for given parameters and AIR shapes:
  * DESIGN.md section 4).  The counterpart of `Proof::<SC>::decode_from_bytes` (crates/verifier/src/verifier.rs:62) for this
  * backend's proofs: commitments, opened values, FRI layers and query openings are read in place.  Needs no device. */

@@ -23,6 +23,7 @@ pub const ZKHIP_FP2_RECORD_WORDS: usize = 33;
 pub const ZKHIP_INT256_CMP_WIDTH: usize = 103;
 pub const ZKHIP_INT256_SHIFT_WIDTH: usize = 189;
 pub const ZKHIP_EC_RECORD_WORDS: usize = 41;
+pub const ZKHIP_GKR_MAX_LOG_N: c_uint = 28;
 pub const ZKHIP_SHA256_WIDTH: usize = 433;
 pub const ZKHIP_SHA256_PREP_WIDTH: usize = 6;
 pub const ZKHIP_SHA256_ROWS_PER_BLOCK: usize = 65;
@@ -360,6 +361,19 @@ extern "C" {
                              opening: *const u32) -> c_int;
     pub fn zkhip_fri_fold_row(index: u64, log_height: c_uint, beta: *const u32, e0: *const u32, e1: *const u32, out: *mut u32) -> c_int;
     pub fn zkhip_logup_exposed_check(exposed: *const u32, n: usize) -> c_int;
+
+    // LogUp-GKR (docs/logup_gkr.md)
+    pub fn zkhip_gkr_proof_words(log_n: c_uint) -> usize;
+    pub fn zkhip_gkr_fraction_prove(ctx: *mut zkhip_ctx, transcript: *mut zkhip_transcript, d_num: *const u32, num_is_ext: c_int,
+                                    d_den: *const u32, log_n: c_uint, proof_out: *mut u32, cap: usize, point_out: *mut u32,
+                                    claims_out: *mut u32) -> c_int;
+    pub fn zkhip_gkr_fraction_verify(prefix: *const u32, n_prefix: usize, proof: *const u32, words: usize, log_n: c_uint,
+                                     point_out: *mut u32, claims_out: *mut u32) -> c_int;
+    pub fn zkhip_bus_gkr_log_leaves(pk: *const zkhip_pk) -> c_uint;
+    pub fn zkhip_bus_gkr_prove(ctx: *mut zkhip_ctx, pk: *const zkhip_pk, d_traces: *const *const u32, pvs: *const *const u32,
+                               transcript: *mut zkhip_transcript, proof_out: *mut u32, cap: usize, words_out: *mut usize) -> c_int;
+    pub fn zkhip_bus_gkr_verify(prefix: *const u32, n_prefix: usize, proof: *const u32, words: usize, log_leaves: c_uint,
+                                challenges_out: *mut u32, point_out: *mut u32, claims_out: *mut u32) -> c_int;
 
     // the reference's stored-proof container (OpenVM-v1 Proof<SC>, bincode)
     pub fn zkhip_proof_decode_v1(bytes: *const u8, len: usize, kind: c_int, out: *mut zkhip_v1_summary) -> c_int;

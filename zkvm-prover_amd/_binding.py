@@ -287,6 +287,12 @@ def load_library():
         "zkhip_profile_enable": (C.c_int, [vp, C.c_int]),
         "zkhip_profile_read": (C.c_int, [vp, C.POINTER(_KernelStat), sz]),
         "zkhip_profile_reset": (C.c_int, [vp]),
+        "zkhip_gkr_proof_words": (sz, [C.c_uint]),
+        "zkhip_gkr_fraction_prove": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_uint, u32p, sz, u32p, u32p]),
+        "zkhip_gkr_fraction_verify": (C.c_int, [u32p, sz, u32p, sz, C.c_uint, u32p, u32p]),
+        "zkhip_bus_gkr_log_leaves": (C.c_uint, [vp]),
+        "zkhip_bus_gkr_prove": (C.c_int, [vp, vp, vp, vp, vp, u32p, sz, C.POINTER(sz)]),
+        "zkhip_bus_gkr_verify": (C.c_int, [u32p, sz, u32p, sz, C.c_uint, u32p, u32p, u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -904,6 +910,24 @@ class Context:
         self._check(self.lib.zkhip_sumcheck_round(self.h, arr, len(tables), n_half, _u32p(out)))
         return out
 
+    # ---- LogUp-GKR (docs/logup_gkr.md) ----------------------------------------------------------------
+    def gkr_prove(self, t_num, t_den, log_n, prefix, num_is_ext=False):
+        """GKR proof of the 2^log_n fractions t_num / t_den (device, Montgomery) after a fresh transcript observed `prefix`.
+        Returns (proof words, point (log_n x 4), claims (num~, den~: 2 x 4)), canonical numpy uint32."""
+        tr = Transcript(self)
+        pre = np.ascontiguousarray(prefix, dtype=np.uint32)
+        if pre.size:
+            tr.observe(pre)
+        words = self.lib.zkhip_gkr_proof_words(log_n)
+        proof = np.zeros(max(words, 1), dtype=np.uint32)
+        point = np.zeros(4 * log_n, dtype=np.uint32)
+        claims = np.zeros(8, dtype=np.uint32)
+        self._check(self.lib.zkhip_gkr_fraction_prove(self.h, tr.h, C.c_void_p(t_num.data_ptr()), int(bool(num_is_ext)),
+                                                      C.c_void_p(t_den.data_ptr()), log_n, _u32p(proof), proof.size, _u32p(point),
+                                                      _u32p(claims)))
+        tr.close()
+        return proof[:words], point.reshape(log_n, 4), claims.reshape(2, 4)
+
     # ---- profiling -----------------------------------------------------------------------------
     def profile_enable(self, on=True):
         self._check(self.lib.zkhip_profile_enable(self.h, int(on)))
@@ -1066,6 +1090,25 @@ class ProvingKey:
                                                   buf.size, C.byref(n)))
         return buf[:n.value].tobytes()
 
+    def bus_gkr_log_leaves(self):
+        return int(self.ctx.lib.zkhip_bus_gkr_log_leaves(self.h))
+
+    def bus_gkr_prove(self, traces, pvs, prefix):
+        """LogUp-GKR proof that the key's buses balance (zkhip_bus_gkr_prove) after a fresh transcript observed `prefix`:
+        proof words (canonical numpy uint32); check with bus_gkr_verify(prefix, proof, self.bus_gkr_log_leaves())."""
+        ctx = self.ctx
+        tr = Transcript(ctx)
+        pre = np.ascontiguousarray(prefix, dtype=np.uint32)
+        if pre.size:
+            tr.observe(pre)
+        tp = (C.c_void_p * len(traces))(*[t.data_ptr() if t is not None else None for t in traces])
+        pa, keep = _pvs_array(pvs)
+        proof = np.zeros(max(ctx.lib.zkhip_gkr_proof_words(self.bus_gkr_log_leaves()), 1), dtype=np.uint32)
+        n = C.c_size_t()
+        ctx._check(ctx.lib.zkhip_bus_gkr_prove(ctx.h, self.h, tp, pa, tr.h, _u32p(proof), proof.size, C.byref(n)))
+        tr.close()
+        return proof[:n.value]
+
     def close(self):
         if self.h:
             self.ctx.lib.zkhip_pk_destroy(self.ctx.h, self.h)
@@ -1098,6 +1141,38 @@ def verify(params, airs, pvs, proof_bytes):
     pa, keep2 = _pvs_array(pvs)
     buf = np.frombuffer(proof_bytes, dtype=np.uint8)
     return lib.zkhip_verify(C.byref(prm), arr, len(airs), pa, buf.ctypes.data_as(C.POINTER(C.c_uint8)), buf.size)
+
+
+def _gkr_words(prefix, proof):
+    pre = np.ascontiguousarray(prefix, dtype=np.uint32)
+    pw = np.ascontiguousarray(proof, dtype=np.uint32)
+    return pre, pw
+
+
+def gkr_verify(prefix, proof, log_n):
+    """Host verifier of a LogUp-GKR fraction proof (needs no GPU): (point (log_n x 4), claims (2 x 4)); raises ZkhipError."""
+    lib = load_library()
+    pre, pw = _gkr_words(prefix, proof)
+    point = np.zeros(4 * max(log_n, 1), dtype=np.uint32)
+    claims = np.zeros(8, dtype=np.uint32)
+    rc = lib.zkhip_gkr_fraction_verify(_u32p(pre), pre.size, _u32p(pw), pw.size, log_n, _u32p(point), _u32p(claims))
+    if rc != 0:
+        raise ZkhipError("zkhip_gkr_fraction_verify refused the proof (%d)" % rc)
+    return point[:4 * log_n].reshape(log_n, 4), claims.reshape(2, 4)
+
+
+def bus_gkr_verify(prefix, proof, log_leaves):
+    """Host verifier of a bus proof (needs no GPU): (challenges (gamma, beta: 2 x 4), point, claims) once the GKR proof checks
+    and the buses balance (P = 0, Q != 0); raises ZkhipError."""
+    lib = load_library()
+    pre, pw = _gkr_words(prefix, proof)
+    chal = np.zeros(8, dtype=np.uint32)
+    point = np.zeros(4 * max(log_leaves, 1), dtype=np.uint32)
+    claims = np.zeros(8, dtype=np.uint32)
+    rc = lib.zkhip_bus_gkr_verify(_u32p(pre), pre.size, _u32p(pw), pw.size, log_leaves, _u32p(chal), _u32p(point), _u32p(claims))
+    if rc != 0:
+        raise ZkhipError("zkhip_bus_gkr_verify refused the proof (%d)" % rc)
+    return chal.reshape(2, 4), point[:4 * log_leaves].reshape(log_leaves, 4), claims.reshape(2, 4)
 
 
 def verify_where(params, airs, pvs, proof_bytes):

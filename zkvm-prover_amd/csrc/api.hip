@@ -332,6 +332,7 @@ void zkhip_ctx_destroy(zkhip_ctx* ctx) {
     for (auto& e : ctx->quot_join)
         if (e) (void)hipEventDestroy(e);
     if (ctx->d_deferred_bad) (void)hipFree(ctx->d_deferred_bad);
+    if (ctx->gkr_ws) (void)hipFree(ctx->gkr_ws);
     if (ctx->h_sponge) (void)hipHostFree(ctx->h_sponge);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     for (auto& e : ctx->pipe_ev)
@@ -580,11 +581,7 @@ int zkhip_fri_fold(zkhip_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, unsign
 }
 
 // ---- transcript handle ------------------------------------------------------------------------
-struct zkhip_transcript {
-    DevTranscript* d = nullptr;
-    uint32_t* d_buf = nullptr;  // staging for observe/sample
-    size_t buf_words = 0;
-};
+// (struct zkhip_transcript: zkhip_internal.hpp)
 
 static int tr_buf(zkhip_ctx* ctx, zkhip_transcript* t, size_t words) {
     if (t->buf_words >= words) return ZKHIP_OK;

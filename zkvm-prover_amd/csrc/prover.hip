@@ -911,6 +911,13 @@ struct zkhip_pk {
     uint32_t *d_lu_den_all = nullptr, *d_lu_num_all = nullptr;
     size_t lu_den_elems = 0;
     ScanSeg* d_lu_scan = nullptr;
+    // LogUp-GKR bus argument (zkhip_bus_gkr_prove): a SECOND descriptor array over buffers of its own, made at first use -- the
+    // v1 phase's denominators / numerators / challenges / public values are never written by it
+    uint32_t* d_gkr_mem = nullptr;   // [den: 2^L ext | num: 2^L | lchal: N_CHAL + 8 | public values | descriptors]
+    LogupArgs* d_gkr_args = nullptr;
+    uint32_t *d_gkr_den = nullptr, *d_gkr_num = nullptr, *d_gkr_lchal = nullptr, *d_gkr_pvs = nullptr;
+    std::vector<LogupArgs> gkr_args_host;
+    std::vector<size_t> gkr_pv_off;   // per AIR: offset of its public values in d_gkr_pvs
     // quotient phase as batches: interpreter descriptors of the chips without a compiled kernel, the alpha-power
     // descriptors of every chip, the bit-reversal copies of every quotient chunk
     std::vector<QuotArgs> quot_args_host;  // one per AIR (the compiled kernels take their fields as parameters)
@@ -965,6 +972,69 @@ struct Bump {
 };
 
 uint32_t host_pow(uint32_t a, uint64_t e) { return mpow(a, e); }
+
+// padding leaves of the bus tree: numerator 0, denominator 1
+__global__ __launch_bounds__(256) void k_gkr_pad(uint32_t* __restrict__ den, uint32_t* __restrict__ num, size_t from, size_t to) {
+    const size_t i = from + (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= to) return;
+    reinterpret_cast<uint4*>(den)[i] = make_uint4(MONTY_ONE, 0, 0, 0);
+    num[i] = 0;
+}
+
+size_t bus_gkr_leaves(const zkhip_pk* pk) {
+    size_t n = 0;
+    for (const auto& A : pk->airs) n += (size_t)A.n_int * A.N;
+    return n;
+}
+unsigned bus_gkr_log(const zkhip_pk* pk) {
+    const size_t n = bus_gkr_leaves(pk);
+    if (!n) return 0;
+    unsigned l = 1;
+    while (((size_t)1 << l) < n) l++;
+    return l;
+}
+// the GKR-owned leaf buffers and descriptors of a key (first use)
+int bus_gkr_setup(zkhip_ctx* ctx, zkhip_pk* pk) {
+    if (pk->d_gkr_mem) return ZKHIP_OK;
+    const unsigned L = bus_gkr_log(pk);
+    const size_t nl = (size_t)1 << L, n_real = bus_gkr_leaves(pk);
+    size_t n_pv = 0;
+    pk->gkr_pv_off.clear();
+    for (const auto& A : pk->airs) pk->gkr_pv_off.push_back(n_pv), n_pv += A.n_pvs;
+    const size_t w_den = 4 * nl, w_num = nl, w_ch = N_CHAL + 8, w_pv = n_pv + 4;
+    const size_t w_args = (pk->n_lu * sizeof(LogupArgs) + 15) / 4;
+    if (hipMalloc((void**)&pk->d_gkr_mem, (w_den + w_num + w_ch + w_pv + w_args + 16) * 4) != hipSuccess) {
+        pk->d_gkr_mem = nullptr;
+        return set_error(ctx, ZKHIP_ERR_NOMEM, "bus gkr buffers");
+    }
+    pk->d_gkr_den = pk->d_gkr_mem;
+    pk->d_gkr_num = pk->d_gkr_den + w_den;
+    pk->d_gkr_lchal = pk->d_gkr_num + w_num;
+    pk->d_gkr_pvs = pk->d_gkr_lchal + w_ch;
+    pk->d_gkr_args = reinterpret_cast<LogupArgs*>(pk->d_gkr_mem + ((w_den + w_num + w_ch + w_pv + 3) & ~(size_t)3));
+    pk->gkr_args_host.clear();
+    size_t off = 0;
+    for (size_t a = 0; a < pk->airs.size(); a++) {
+        const AirPlan& A = pk->airs[a];
+        if (!A.n_int) continue;
+        LogupArgs la = pk->lu_args_host[pk->gkr_args_host.size()];   // the key's interaction bytecode and shapes ...
+        la.trace = nullptr;                                           // ... over the GKR buffers (patched per proof)
+        la.pvs = pk->d_gkr_pvs + pk->gkr_pv_off[a];
+        la.lchal = pk->d_gkr_lchal;
+        la.den = pk->d_gkr_den + 4 * off;
+        la.num = pk->d_gkr_num + off;
+        la.perm = la.sums = la.expo = nullptr;   // k_logup_denoms writes den / num only
+        pk->gkr_args_host.push_back(la);
+        off += (size_t)A.n_int * A.N;
+    }
+    if (nl > n_real) {
+        KernelScope ks(ctx, "gkr_bus_pad");
+        hipLaunchKernelGGL(k_gkr_pad, dim3((unsigned)((nl - n_real + 255) / 256)), dim3(256), 0, ctx->stream, pk->d_gkr_den, pk->d_gkr_num,
+                           n_real, nl);
+        ZK_HIP_CHECK(ctx, hipGetLastError());
+    }
+    return ZKHIP_OK;
+}
 
 int upload(zkhip_ctx* ctx, void* dst, const void* src, size_t bytes) {
     if (bytes == 0) return ZKHIP_OK;
@@ -1837,6 +1907,7 @@ void zkhip_pk_destroy(zkhip_ctx* ctx, zkhip_pk* pk) {
         if (A.d_jit_tab) (void)hipFree(A.d_jit_tab);
     }
     if (pk->d_ws) (void)hipFree(pk->d_ws);
+    if (pk->d_gkr_mem) (void)hipFree(pk->d_gkr_mem);
     delete pk;
 }
 
@@ -2538,6 +2609,58 @@ int zkhip_prove(zkhip_ctx* ctx, const zkhip_pk* pk, const uint32_t* const* d_tra
     }
     ZK_TRY(zkhip_prove_async(ctx, pk, d_traces, pvs));
     return zkhip_proof_fetch(ctx, pk, out, cap, out_len);
+}
+
+unsigned zkhip_bus_gkr_log_leaves(const zkhip_pk* pk) { return pk ? bus_gkr_log(pk) : 0; }
+
+int zkhip_bus_gkr_prove(zkhip_ctx* ctx, const zkhip_pk* pkc, const uint32_t* const* d_traces, const uint32_t* const* pvs,
+                        zkhip_transcript* transcript, uint32_t* proof_out, size_t cap, size_t* words_out) {
+    ZK_BIND_DEVICE(ctx);
+    if (!ctx || !pkc || !d_traces || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
+    zkhip_pk* pk = const_cast<zkhip_pk*>(pkc);
+    const unsigned L = bus_gkr_log(pk);
+    if (!L) return set_error(ctx, ZKHIP_ERR_INVALID, "bus gkr: the key has no bus interactions");
+    if (L > ZKHIP_GKR_MAX_LOG_N) return set_error(ctx, ZKHIP_ERR_INVALID, "bus gkr: too many interaction rows");
+    const size_t words = zkhip_gkr_proof_words(L);
+    if (cap < words) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, "bus gkr: proof buffer too small");
+    const size_t n_airs = pk->airs.size();
+    std::vector<uint32_t> pm;
+    for (size_t a = 0; a < n_airs; a++) {
+        const AirPlan& A = pk->airs[a];
+        if (A.n_pvs && (!pvs || !pvs[a])) return set_error(ctx, ZKHIP_ERR_INVALID, "missing public values");
+        for (size_t i = 0; i < A.n_pvs; i++) {
+            if (pvs[a][i] >= P) return set_error(ctx, ZKHIP_ERR_INVALID, "public value not canonical");
+            pm.push_back(to_monty(pvs[a][i]));
+        }
+        if (A.n_int && !d_traces[a]) return set_error(ctx, ZKHIP_ERR_INVALID, "missing trace");
+    }
+    ZK_TRY(bus_gkr_setup(ctx, pk));
+    hipStream_t st = ctx->stream;
+    // (both host vectors outlive the copies: the proof's read-back below synchronises the stream)
+    std::vector<LogupArgs> args = pk->gkr_args_host;
+    for (size_t a = 0, k = 0; a < n_airs; a++)
+        if (pk->airs[a].n_int) args[k++].trace = d_traces[a];
+    if (!pm.empty()) ZK_HIP_CHECK(ctx, hipMemcpyAsync(pk->d_gkr_pvs, pm.data(), pm.size() * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP_CHECK(ctx, hipMemcpyAsync(pk->d_gkr_args, args.data(), args.size() * sizeof(LogupArgs), hipMemcpyHostToDevice, st));
+    DevTranscript* tr = transcript->d;
+    uint32_t* d_gb = pk->d_gkr_lchal + N_CHAL;
+    ZK_TRY(transcript_sample(ctx, tr, d_gb, nullptr, 4));   // gamma
+    ZK_TRY(transcript_sample(ctx, tr, d_gb + 4, nullptr, 4));   // beta
+    {
+        KernelScope ks(ctx, "gkr_bus_chal");
+        hipLaunchKernelGGL(k_logup_chal, dim3(1), dim3(64), 0, st, (const uint32_t*)d_gb, pk->d_gkr_lchal);
+    }
+    {
+        KernelScope ks(ctx, "gkr_bus_leaves");
+        const LogupMulti lm{pk->d_gkr_args, pk->d_lu_rows_first, pk->d_lu_den_first, (uint32_t)pk->n_lu};
+        hipLaunchKernelGGL(k_logup_denoms, dim3(pk->lu_den_blocks), dim3(LU_BS), (size_t)pk->lu_max_slots * LU_BS * 4, st, lm);
+        ZK_HIP_CHECK(ctx, hipGetLastError());
+    }
+    const uint32_t* d_res = nullptr;
+    ZK_TRY(gkr_prove_device(ctx, tr, pk->d_gkr_num, false, pk->d_gkr_den, L, &d_res));
+    ZK_TRY(zkhip_d2h(ctx, proof_out, d_res, words * 4));
+    if (words_out) *words_out = words;
+    return ZKHIP_OK;
 }
 
 }  // extern "C"

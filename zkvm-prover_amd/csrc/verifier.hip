@@ -8,47 +8,12 @@
 #include <vector>
 
 #include "air_compile.hpp"
+#include "host_challenger.hpp"
 #include "poseidon2.hpp"
 #include "../../include/zkhip.h"
 
 namespace zk {
 namespace {
-
-struct HostChallenger {
-    uint32_t state[16];
-    uint32_t in_buf[8], out_buf[8];
-    unsigned n_in = 0, n_out = 0;
-    HostChallenger() { memset(state, 0, sizeof state); }
-    void duplex() {
-        for (unsigned i = 0; i < n_in; i++) state[i] = in_buf[i];
-        n_in = 0;
-        poseidon2_permute_host(state);
-        memcpy(out_buf, state, sizeof out_buf);
-        n_out = 8;
-    }
-    void observe(uint32_t v_monty) {
-        n_out = 0;
-        in_buf[n_in++] = v_monty;
-        if (n_in == 8) duplex();
-    }
-    void observe_canon(const uint32_t* v, size_t n) {
-        for (size_t i = 0; i < n; i++) observe(to_monty(v[i]));
-    }
-    uint32_t sample() {
-        if (n_in != 0 || n_out == 0) duplex();
-        return out_buf[--n_out];
-    }
-    Ext sample_ext() {
-        Ext e;
-        for (int i = 0; i < 4; i++) e.c[i] = sample();
-        return e;
-    }
-    uint32_t sample_bits(unsigned bits) { return from_monty(sample()) & (uint32_t)(((uint64_t)1 << bits) - 1); }
-    bool check_witness(unsigned bits, uint32_t w_canon) {
-        observe(to_monty(w_canon));
-        return sample_bits(bits) == 0;
-    }
-};
 
 Ext ext_from_canon(const uint32_t* p) { return Ext{{to_monty(p[0]), to_monty(p[1]), to_monty(p[2]), to_monty(p[3])}}; }
 

@@ -11,6 +11,7 @@
 
 #include "../../include/zkhip.h"
 #include "babybear.hpp"
+#include "transcript.hpp"
 
 namespace zk {
 
@@ -72,6 +73,16 @@ struct zkhip_ctx {
     // the scale tables of a four-step LDE (ntt.hip: column / row / rho powers of the coset shifts) depend on (log_n, added_bits, shift) only:
     // made once per context and read-only afterwards (a segment proof extends ~20 heights: a launch each, every proof, before round 5)
     std::map<uint64_t, uint32_t*> lde_tables;
+    // LogUp-GKR proofs (logup_gkr.hip): the fraction tree, the folded tables and the proof staging, grow-only
+    void* gkr_ws = nullptr;
+    size_t gkr_ws_bytes = 0;
+};
+
+// the device transcript behind a zkhip_transcript handle (api.hip)
+struct zkhip_transcript {
+    zk::DevTranscript* d = nullptr;
+    uint32_t* d_buf = nullptr;  // staging for observe/sample
+    size_t buf_words = 0;
 };
 
 namespace zk {
@@ -204,4 +215,10 @@ struct ScanSeg {
 };
 uint32_t scan_blocks_of(size_t n);
 int ext_inclusive_scan_multi(zkhip_ctx* ctx, const ScanSeg* d_segs, uint32_t n_seg, uint32_t total_blocks, bool any_multi_block);
+
+// logup_gkr.hip
+// the whole LogUp-GKR proof of 2^L fractions on the ctx stream, continuing the transcript d_t (no host synchronisation);
+// *d_result: device words [proof (gkr_proof_words) | point (4 L) | claims (8)], canonical, valid until the next proof on this ctx
+int gkr_prove_device(zkhip_ctx* ctx, DevTranscript* d_t, const uint32_t* d_num, bool num_ext, const uint32_t* d_den, unsigned L,
+                     const uint32_t** d_result);
 }  // namespace zk
