@@ -549,6 +549,50 @@ int zkhip_bus_gkr_prove(zkhip_ctx *ctx, const zkhip_pk *pk, const uint32_t *cons
 int zkhip_bus_gkr_verify(const uint32_t *prefix, size_t n_prefix, const uint32_t *proof, size_t words, unsigned log_leaves,
                          uint32_t *challenges_out, uint32_t *point_out, uint32_t *claims_out);
 
+/* ---- WHIR (docs/whir.md): a multilinear polynomial commitment (Arnon, Chiesa, Fenzi, Yogev 2024) in this library's transcript.
+ *      n_cols base-field columns of 2^m hypercube evaluations (entry i = sum b_j 2^j, z_0 the lowest bit) are committed as the
+ *      Reed-Solomon codewords of their monomial coefficients; an opening proves the columns' multilinear extensions at a point.
+ *      Rounds: R = max(1, floor((m - final_log) / fold_log)) (1 when m <= final_log), each binding fold_log variables; needs
+ *      fold_log <= m.  The caller chooses the query counts and the grinding; the library computes no security level. ---- */
+#define ZKHIP_WHIR_MAX_ROUNDS 32
+#define ZKHIP_WHIR_MAX_COLS 64
+#define ZKHIP_WHIR_MAX_LOG_N 26
+#define ZKHIP_WHIR_MAX_QUERIES 256
+typedef struct {
+    uint32_t log_blowup;                          /* b: the first codeword has 2^(m + b) rows; 1..3 */
+    uint32_t fold_log;                            /* k: variables bound per round (a coset of 2^k rows per leaf); 1..4 */
+    uint32_t final_log;                           /* stop folding once at most this many variables remain */
+    uint32_t pow_bits[ZKHIP_WHIR_MAX_ROUNDS];     /* grinding per round, <= 30 */
+    uint32_t num_queries[ZKHIP_WHIR_MAX_ROUNDS];  /* queries per round, 1..ZKHIP_WHIR_MAX_QUERIES */
+} zkhip_whir_params;
+/* words of an opening proof; 0 if the parameters do not fit m and n_cols */
+size_t zkhip_whir_proof_words(const zkhip_whir_params *params, unsigned m, size_t n_cols);
+typedef struct zkhip_whir_commitment zkhip_whir_commitment;
+/* d_cols: n_cols columns of 2^m Montgomery words, column c at d_cols + c * col_stride (device; they must stay alive as long as the
+ * commitment).  root_out: HOST, 8 canonical words (synchronises).  1 <= m <= ZKHIP_WHIR_MAX_LOG_N, 1 <= n_cols <= ZKHIP_WHIR_MAX_COLS. */
+int zkhip_whir_commit(zkhip_ctx *ctx, const zkhip_whir_params *params, const uint32_t *d_cols, size_t col_stride, size_t n_cols,
+                      unsigned m, zkhip_whir_commitment **out, uint32_t *root_out);
+/* opens the commitment at `point` (HOST, m extension elements, canonical), continuing `transcript` -- which must already hold the
+ * root: the opening does not observe it.  values_out (HOST, 4 n_cols words) = the columns' multilinear extensions at the point;
+ * proof_out (HOST, cap >= zkhip_whir_proof_words) canonical.  The commitment can be opened more than once. */
+int zkhip_whir_open(zkhip_ctx *ctx, zkhip_whir_commitment *com, zkhip_transcript *transcript, const uint32_t *point,
+                    uint32_t *values_out, uint32_t *proof_out, size_t cap);
+void zkhip_whir_commitment_destroy(zkhip_ctx *ctx, zkhip_whir_commitment *com);
+/* host verifier: a fresh challenger observes `prefix`, then replays the opening of `root` at `point` with the claimed `values`
+ * (4 n_cols words).  ZKHIP_OK / ZKHIP_ERR_VERIFY.  Needs no device. */
+int zkhip_whir_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const uint32_t *root, unsigned m,
+                      size_t n_cols, const uint32_t *point, const uint32_t *values, const uint32_t *proof, size_t words);
+/* The committed fractional sum: the leaves' columns [num (1 column, or 4 when num_is_ext) | den (4 coordinate columns)] are committed
+ * as ONE WHIR commitment, its root observed, the GKR proof of zkhip_gkr_fraction_prove run, and the commitment opened at the GKR's
+ * point.  Proof words: [root (8) | GKR proof | WHIR opening]. */
+size_t zkhip_gkr_committed_proof_words(const zkhip_whir_params *params, unsigned log_n, int num_is_ext);
+int zkhip_gkr_committed_prove(zkhip_ctx *ctx, zkhip_transcript *transcript, const zkhip_whir_params *params, const uint32_t *d_num,
+                              int num_is_ext, const uint32_t *d_den, unsigned log_n, uint32_t *proof_out, size_t cap);
+/* host verifier: replays all of it and checks num~(rho) and den~(rho) = sum_c X^c v_den_c against the GKR's final claims.
+ * root_out (8 words) and pq_out (P, Q: 8 words) canonical.  ZKHIP_OK / ZKHIP_ERR_VERIFY.  Needs no device. */
+int zkhip_gkr_committed_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const uint32_t *proof,
+                               size_t words, unsigned log_n, int num_is_ext, uint32_t *root_out, uint32_t *pq_out);
+
 /* Field offsets of a proof, in 32-bit words from its start (the layout is static for given parameters and AIR shapes:
  * DESIGN.md section 4).  The counterpart of `Proof::<SC>::decode_from_bytes` (crates/verifier/src/verifier.rs:62) for this
  * backend's proofs: commitments, opened values, FRI layers and query openings are read in place.  Needs no device. */

@@ -24,6 +24,10 @@ pub const ZKHIP_INT256_CMP_WIDTH: usize = 103;
 pub const ZKHIP_INT256_SHIFT_WIDTH: usize = 189;
 pub const ZKHIP_EC_RECORD_WORDS: usize = 41;
 pub const ZKHIP_GKR_MAX_LOG_N: c_uint = 28;
+pub const ZKHIP_WHIR_MAX_ROUNDS: usize = 32;
+pub const ZKHIP_WHIR_MAX_COLS: usize = 64;
+pub const ZKHIP_WHIR_MAX_LOG_N: c_uint = 26;
+pub const ZKHIP_WHIR_MAX_QUERIES: u32 = 256;
 pub const ZKHIP_SHA256_WIDTH: usize = 433;
 pub const ZKHIP_SHA256_PREP_WIDTH: usize = 6;
 pub const ZKHIP_SHA256_ROWS_PER_BLOCK: usize = 65;
@@ -71,6 +75,21 @@ pub struct zkhip_transcript {
 #[repr(C)]
 pub struct zkhip_pk {
     _private: [u8; 0],
+}
+#[repr(C)]
+pub struct zkhip_whir_commitment {
+    _private: [u8; 0],
+}
+
+// docs/whir.md
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct zkhip_whir_params {
+    pub log_blowup: u32,
+    pub fold_log: u32,
+    pub final_log: u32,
+    pub pow_bits: [u32; ZKHIP_WHIR_MAX_ROUNDS],
+    pub num_queries: [u32; ZKHIP_WHIR_MAX_ROUNDS],
 }
 
 #[repr(C)]
@@ -374,6 +393,22 @@ extern "C" {
                                transcript: *mut zkhip_transcript, proof_out: *mut u32, cap: usize, words_out: *mut usize) -> c_int;
     pub fn zkhip_bus_gkr_verify(prefix: *const u32, n_prefix: usize, proof: *const u32, words: usize, log_leaves: c_uint,
                                 challenges_out: *mut u32, point_out: *mut u32, claims_out: *mut u32) -> c_int;
+
+    // WHIR (docs/whir.md)
+    pub fn zkhip_whir_proof_words(params: *const zkhip_whir_params, m: c_uint, n_cols: usize) -> usize;
+    pub fn zkhip_whir_commit(ctx: *mut zkhip_ctx, params: *const zkhip_whir_params, d_cols: *const u32, col_stride: usize, n_cols: usize,
+                             m: c_uint, out: *mut *mut zkhip_whir_commitment, root_out: *mut u32) -> c_int;
+    pub fn zkhip_whir_open(ctx: *mut zkhip_ctx, com: *mut zkhip_whir_commitment, transcript: *mut zkhip_transcript, point: *const u32,
+                           values_out: *mut u32, proof_out: *mut u32, cap: usize) -> c_int;
+    pub fn zkhip_whir_commitment_destroy(ctx: *mut zkhip_ctx, com: *mut zkhip_whir_commitment);
+    pub fn zkhip_whir_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, root: *const u32, m: c_uint,
+                             n_cols: usize, point: *const u32, values: *const u32, proof: *const u32, words: usize) -> c_int;
+    pub fn zkhip_gkr_committed_proof_words(params: *const zkhip_whir_params, log_n: c_uint, num_is_ext: c_int) -> usize;
+    pub fn zkhip_gkr_committed_prove(ctx: *mut zkhip_ctx, transcript: *mut zkhip_transcript, params: *const zkhip_whir_params,
+                                     d_num: *const u32, num_is_ext: c_int, d_den: *const u32, log_n: c_uint, proof_out: *mut u32,
+                                     cap: usize) -> c_int;
+    pub fn zkhip_gkr_committed_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, proof: *const u32,
+                                      words: usize, log_n: c_uint, num_is_ext: c_int, root_out: *mut u32, pq_out: *mut u32) -> c_int;
 
     // the reference's stored-proof container (OpenVM-v1 Proof<SC>, bincode)
     pub fn zkhip_proof_decode_v1(bytes: *const u8, len: usize, kind: c_int, out: *mut zkhip_v1_summary) -> c_int;

@@ -37,6 +37,24 @@ class _Params(C.Structure):
                 ("commit_pow_bits", C.c_uint32), ("query_pow_bits", C.c_uint32)]
 
 
+WHIR_MAX_ROUNDS = 32
+
+
+class WhirParams(C.Structure):
+    """zkhip_whir_params (docs/whir.md)"""
+    _fields_ = [("log_blowup", C.c_uint32), ("fold_log", C.c_uint32), ("final_log", C.c_uint32),
+                ("pow_bits", C.c_uint32 * WHIR_MAX_ROUNDS), ("num_queries", C.c_uint32 * WHIR_MAX_ROUNDS)]
+
+    @classmethod
+    def make(cls, log_blowup, fold_log, final_log, pow_bits, num_queries):
+        """pow_bits / num_queries: one int for every round, or a list per round"""
+        p = cls(log_blowup=log_blowup, fold_log=fold_log, final_log=final_log)
+        for i in range(WHIR_MAX_ROUNDS):
+            p.pow_bits[i] = pow_bits[i] if hasattr(pow_bits, "__len__") else pow_bits
+            p.num_queries[i] = num_queries[i] if hasattr(num_queries, "__len__") else num_queries
+        return p
+
+
 class _Air(C.Structure):
     _fields_ = [("program", C.POINTER(C.c_uint32)), ("program_len", C.c_size_t), ("log_height", C.c_uint),
                 ("width", C.c_size_t), ("n_pvs", C.c_size_t), ("prep_trace", C.POINTER(C.c_uint32)),
@@ -293,6 +311,14 @@ def load_library():
         "zkhip_bus_gkr_log_leaves": (C.c_uint, [vp]),
         "zkhip_bus_gkr_prove": (C.c_int, [vp, vp, vp, vp, vp, u32p, sz, C.POINTER(sz)]),
         "zkhip_bus_gkr_verify": (C.c_int, [u32p, sz, u32p, sz, C.c_uint, u32p, u32p, u32p]),
+        "zkhip_whir_proof_words": (sz, [C.POINTER(WhirParams), C.c_uint, sz]),
+        "zkhip_whir_commit": (C.c_int, [vp, C.POINTER(WhirParams), vp, sz, sz, C.c_uint, C.POINTER(vp), u32p]),
+        "zkhip_whir_open": (C.c_int, [vp, vp, vp, u32p, u32p, u32p, sz]),
+        "zkhip_whir_commitment_destroy": (None, [vp, vp]),
+        "zkhip_whir_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, u32p, C.c_uint, sz, u32p, u32p, u32p, sz]),
+        "zkhip_gkr_committed_proof_words": (sz, [C.POINTER(WhirParams), C.c_uint, C.c_int]),
+        "zkhip_gkr_committed_prove": (C.c_int, [vp, vp, C.POINTER(WhirParams), vp, C.c_int, vp, C.c_uint, u32p, sz]),
+        "zkhip_gkr_committed_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, u32p, sz, C.c_uint, C.c_int, u32p, u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -928,6 +954,50 @@ class Context:
         tr.close()
         return proof[:words], point.reshape(log_n, 4), claims.reshape(2, 4)
 
+    # ---- WHIR (docs/whir.md) ---------------------------------------------------------------------------
+    def whir_commit(self, params, cols, m):
+        """WHIR commitment of the columns of `cols` (device tensor of n_cols x 2^m Montgomery words, kept alive by the returned
+        WhirCommitment).  Returns the WhirCommitment; its `root` is 8 canonical words."""
+        n_cols = cols.numel() >> m
+        assert n_cols << m == cols.numel() and cols.is_contiguous()
+        h = C.c_void_p()
+        root = np.zeros(8, dtype=np.uint32)
+        self._check(self.lib.zkhip_whir_commit(self.h, C.byref(params), C.c_void_p(cols.data_ptr()), 1 << m, n_cols, m, C.byref(h),
+                                               _u32p(root)))
+        return WhirCommitment(self, h, params, cols, m, n_cols, root)
+
+    def whir_open(self, com, point, prefix=None, transcript=None):
+        """Opening of `com` at `point` (m x 4 canonical words).  Without `transcript`, a fresh one observes `prefix` (default: the
+        root) first.  Returns (values (n_cols x 4), proof words), canonical numpy uint32."""
+        own = transcript is None
+        tr = Transcript(self) if own else transcript
+        if own:
+            pre = np.ascontiguousarray(com.root if prefix is None else prefix, dtype=np.uint32)
+            if pre.size:
+                tr.observe(pre)
+        pt = np.ascontiguousarray(point, dtype=np.uint32).reshape(-1)
+        words = self.lib.zkhip_whir_proof_words(C.byref(com.params), com.m, com.n_cols)
+        proof = np.zeros(max(words, 1), dtype=np.uint32)
+        values = np.zeros(4 * com.n_cols, dtype=np.uint32)
+        self._check(self.lib.zkhip_whir_open(self.h, com.h, tr.h, _u32p(pt), _u32p(values), _u32p(proof), proof.size))
+        if own:
+            tr.close()
+        return values.reshape(com.n_cols, 4), proof[:words]
+
+    def gkr_committed_prove(self, params, t_num, t_den, log_n, prefix, num_is_ext=False):
+        """Committed fractional-sum proof (zkhip_gkr_committed_prove) of the 2^log_n fractions t_num / t_den (device, Montgomery)
+        after a fresh transcript observed `prefix`: [root | GKR proof | WHIR opening], canonical numpy uint32."""
+        tr = Transcript(self)
+        pre = np.ascontiguousarray(prefix, dtype=np.uint32)
+        if pre.size:
+            tr.observe(pre)
+        words = self.lib.zkhip_gkr_committed_proof_words(C.byref(params), log_n, int(bool(num_is_ext)))
+        proof = np.zeros(max(words, 1), dtype=np.uint32)
+        self._check(self.lib.zkhip_gkr_committed_prove(self.h, tr.h, C.byref(params), C.c_void_p(t_num.data_ptr()), int(bool(num_is_ext)),
+                                                       C.c_void_p(t_den.data_ptr()), log_n, _u32p(proof), proof.size))
+        tr.close()
+        return proof[:words]
+
     # ---- profiling -----------------------------------------------------------------------------
     def profile_enable(self, on=True):
         self._check(self.lib.zkhip_profile_enable(self.h, int(on)))
@@ -1173,6 +1243,56 @@ def bus_gkr_verify(prefix, proof, log_leaves):
     if rc != 0:
         raise ZkhipError("zkhip_bus_gkr_verify refused the proof (%d)" % rc)
     return chal.reshape(2, 4), point[:4 * log_leaves].reshape(log_leaves, 4), claims.reshape(2, 4)
+
+
+class WhirCommitment:
+    """A WHIR commitment on the device (zkhip_whir_commitment); holds its columns alive."""
+
+    def __init__(self, ctx, h, params, cols, m, n_cols, root):
+        self.ctx, self.h, self.params, self.cols, self.m, self.n_cols, self.root = ctx, h, params, cols, m, n_cols, root
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.zkhip_whir_commitment_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def whir_proof_words(params, m, n_cols):
+    return int(load_library().zkhip_whir_proof_words(C.byref(params), m, n_cols))
+
+
+def whir_verify(params, prefix, root, m, n_cols, point, values, proof):
+    """Host verifier of a WHIR opening (needs no GPU): a fresh challenger observes `prefix`, then the opening of `root` at `point`
+    with the claimed `values` (n_cols x 4) is replayed; raises ZkhipError."""
+    lib = load_library()
+    pre, pw = _gkr_words(prefix, proof)
+    rt = np.ascontiguousarray(root, dtype=np.uint32).reshape(-1)
+    pt = np.ascontiguousarray(point, dtype=np.uint32).reshape(-1)
+    vals = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+    if rt.size != 8 or pt.size != 4 * m or vals.size != 4 * n_cols:
+        raise ZkhipError("whir_verify: root, point or values of the wrong size")
+    rc = lib.zkhip_whir_verify(C.byref(params), _u32p(pre), pre.size, _u32p(rt), m, n_cols, _u32p(pt), _u32p(vals), _u32p(pw), pw.size)
+    if rc != 0:
+        raise ZkhipError("zkhip_whir_verify refused the proof (%d)" % rc)
+
+
+def gkr_committed_verify(params, prefix, proof, log_n, num_is_ext=False):
+    """Host verifier of a committed fractional-sum proof (needs no GPU): (root (8), (P, Q) (2 x 4)); raises ZkhipError."""
+    lib = load_library()
+    pre, pw = _gkr_words(prefix, proof)
+    root = np.zeros(8, dtype=np.uint32)
+    pq = np.zeros(8, dtype=np.uint32)
+    rc = lib.zkhip_gkr_committed_verify(C.byref(params), _u32p(pre), pre.size, _u32p(pw), pw.size, log_n, int(bool(num_is_ext)), _u32p(root),
+                                        _u32p(pq))
+    if rc != 0:
+        raise ZkhipError("zkhip_gkr_committed_verify refused the proof (%d)" % rc)
+    return root, pq.reshape(2, 4)
 
 
 def verify_where(params, airs, pvs, proof_bytes):

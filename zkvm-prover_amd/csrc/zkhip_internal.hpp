@@ -221,4 +221,8 @@ int ext_inclusive_scan_multi(zkhip_ctx* ctx, const ScanSeg* d_segs, uint32_t n_s
 // *d_result: device words [proof (gkr_proof_words) | point (4 L) | claims (8)], canonical, valid until the next proof on this ctx
 int gkr_prove_device(zkhip_ctx* ctx, DevTranscript* d_t, const uint32_t* d_num, bool num_ext, const uint32_t* d_den, unsigned L,
                      const uint32_t** d_result);
+// the host verifier on a challenger the caller primed: point_out (4 L words) / claims_out (8 words) canonical, root_out = (P, Q)
+struct HostChallenger;
+int gkr_verify_host(HostChallenger& ch, const uint32_t* proof, size_t words, unsigned L, uint32_t* point_out, uint32_t* claims_out,
+                    Ext root_out[2]);
 }  // namespace zk
