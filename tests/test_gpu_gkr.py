@@ -52,7 +52,7 @@ def _gpu_proof(zk, num, den, log_n, prefix, ext_num):
     return zk.gkr_prove(zk.upload(num.reshape(-1)), zk.upload(den.reshape(-1)), log_n, prefix, num_is_ext=ext_num)
 
 
-@pytest.mark.parametrize("log_n", list(range(1, 13)))
+@pytest.mark.parametrize("log_n", list(range(1, 15)))
 @pytest.mark.parametrize("ext_num", [False, True])
 def test_gpu_words_equal_model(zk, log_n, ext_num):
     rng = np.random.default_rng(1000 + 2 * log_n + ext_num)

@@ -42,7 +42,7 @@ def _device_open(zk, prm, cols, m, point, prefix_extra=()):
 @pytest.mark.parametrize("b,k,fl,n_cols", SETS)
 def test_gpu_words_equal_model(zk, b, k, fl, n_cols):
     prm = _params(b, k, fl, pow_bits=1 + b, nq=2 + k)
-    for m in sorted({k, k + 1, 5, 7, 10} if (b, k) == (1, 4) else {k, k + 1, 5, 7}):
+    for m in sorted({k, k + 1, 5, 7, 10, 12, 13} if (b, k) == (1, 4) else {k, k + 1, 5, 7, 12}):
         if m < k:
             continue
         rng = np.random.default_rng(100 * m + 10 * b + k)
@@ -138,7 +138,7 @@ def test_committed_gkr_2_20(zk):
         z.gkr_committed_verify(_lp(prm), [5, 6], bad, log_n)
 
 
-@pytest.mark.parametrize("log_n,num_ext", [(3, False), (6, True), (9, False)])
+@pytest.mark.parametrize("log_n,num_ext", [(3, False), (6, True), (9, False), (13, True)])
 def test_committed_gkr_words_equal_model(zk, log_n, num_ext):
     rng = np.random.default_rng(30 + log_n)
     num = rng.integers(0, P, size=(1 << log_n, 4) if num_ext else 1 << log_n, dtype=np.uint32)

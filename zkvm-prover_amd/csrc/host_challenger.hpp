@@ -43,4 +43,12 @@ struct HostChallenger {
     }
 };
 
+// the field helpers every host verifier shares (csrc/verifier.hip)
+Ext ext_from_canon(const uint32_t* p);                 // 4 canonical words -> Montgomery
+void ext_to_canon(uint32_t* out, const Ext& e);         // Montgomery -> 4 canonical words
+Ext poly_at(const Ext* s, unsigned d, const Ext& x);   // the polynomial of degree <= d through (j, s[j]), j = 0..d, at x
+Ext eq_eval(const Ext* p, const Ext* x, size_t n);      // eq(p, x) = prod_j (p_j x_j + (1 - p_j)(1 - x_j))
+// p3-fri `fold_row` for arity 2: pair k of a bit-reversed layer of 2^(log_n_out+1) values folded at beta
+Ext fold_row(size_t k, unsigned log_n_out, const Ext& beta, const Ext& e0, const Ext& e1);
+
 }  // namespace zk

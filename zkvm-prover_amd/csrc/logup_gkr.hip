@@ -5,43 +5,29 @@
 // Device side, per proof of 2^L leaves:
 //   * the fraction tree: every layer is written (each layer's sum-check reads the layer below it); a workgroup reduces a block of
 //     512 entries nine layers deep through LDS, so the whole tree is ceil(L / 9) launches;
-//   * layers whose sum-check tables hold at most GKR_T entries (the top ones: layers 0..GKR_LT) run in ONE single-workgroup kernel
+//   * layers whose sum-check tables hold at most SC_T entries (the top ones: layers 0..SC_LT) run in ONE single-workgroup kernel
 //     with the tables in LDS and the transcript in-kernel (k_gkr_small, head form);
-//   * a bigger layer k: the eq table in log-many doubling passes (the first GKR_LT in one workgroup), then per round one streaming
+//   * a bigger layer k: the eq table in log-many doubling passes (the first SC_LT in one workgroup), then per round one streaming
 //     pass that folds the five tables (p0, p1, q0, q1, eq) with the previous challenge AND evaluates the next round polynomial at
 //     0, 2, 3 (two-stage reduction; field addition is exact, so the order does not change the words), and one one-wave kernel that
-//     adds the partial sums up, observes them and samples the challenge; once the tables fit GKR_T entries the rest of the layer
+//     adds the partial sums up, observes them and samples the challenge; once the tables fit SC_T entries the rest of the layer
 //     goes to k_gkr_small (tail form), which also samples the next layer's challenges.
+// The pass, the one-wave kernel and the rounds of k_gkr_small are the sum-check core's (sumcheck_dev.hpp).
 // Nothing goes through the host between the first launch and the final read-back.
 #include <algorithm>
 #include <vector>
 
 #include "host_challenger.hpp"
-#include "lds_barrier.hpp"
-#include "transcript_dev.hpp"
-#include "zkhip_internal.hpp"
+#include "sumcheck_dev.hpp"
 
 namespace zk {
 
-constexpr unsigned GKR_LT = 10;               // tables of <= 2^GKR_LT entries live in LDS (5 x 16 KiB)
-constexpr unsigned GKR_T = 1u << GKR_LT;
-constexpr unsigned GKR_SW = 512;              // threads of the single-workgroup kernels
-constexpr unsigned GKR_NB = 1024;             // most workgroups of a streaming pass (partial sums: [12][GKR_NB] words)
 constexpr unsigned GKR_TREE_DEPTH = 9;        // layers one tree launch reduces (512 entries per workgroup)
 constexpr unsigned GKR_MAXL = ZKHIP_GKR_MAX_LOG_N;
 
 // proof words before layer k's round polynomials: the root, then 12 j + 16 words for every layer j < k
 ZK_HD size_t gkr_layer_off(unsigned k) { return 8 + 16 * (size_t)k + 6 * (size_t)k * (k ? k - 1 : 0); }
 ZK_HD size_t gkr_proof_words(unsigned L) { return gkr_layer_off(L); }
-
-__device__ __forceinline__ Ext gkr_ld(const uint32_t* p, size_t i) {
-    const uint4 v = reinterpret_cast<const uint4*>(p)[i];
-    return Ext{{v.x, v.y, v.z, v.w}};
-}
-__device__ __forceinline__ void gkr_st(uint32_t* p, size_t i, const Ext& e) {
-    reinterpret_cast<uint4*>(p)[i] = make_uint4(e.c[0], e.c[1], e.c[2], e.c[3]);
-}
-__device__ __forceinline__ Ext gkr_fold(const Ext& a, const Ext& b, const Ext& r) { return ext_add(a, ext_mul(r, ext_sub(b, a))); }
 
 // the layers of the tree: p[k], q[k] hold 2^k entries (extension; p[L] is the caller's numerator array, base field when base_leaves)
 struct GkrLayers {
@@ -60,31 +46,26 @@ __global__ __launch_bounds__(256) void k_gkr_tree(const uint32_t* __restrict__ p
     Ext p, q;
     if (tid < n) {
         const size_t i = (size_t)blockIdx.x * 512 + 2 * tid;
-        const Ext q0 = gkr_ld(q_in, i), q1 = gkr_ld(q_in, i + 1);
+        const Ext q0 = sc_ld(q_in, i), q1 = sc_ld(q_in, i + 1);
         if (BASE) p = ext_add(ext_mul_base(q1, p_in[i]), ext_mul_base(q0, p_in[i + 1]));
-        else p = ext_add(ext_mul(gkr_ld(p_in, i), q1), ext_mul(gkr_ld(p_in, i + 1), q0));
+        else p = ext_add(ext_mul(sc_ld(p_in, i), q1), ext_mul(sc_ld(p_in, i + 1), q0));
         q = ext_mul(q0, q1);
-        gkr_st(lay.p[log_in - 1], (size_t)blockIdx.x * n + tid, p);
-        gkr_st(lay.q[log_in - 1], (size_t)blockIdx.x * n + tid, q);
-        sp[tid] = make_uint4(p.c[0], p.c[1], p.c[2], p.c[3]);
-        sq[tid] = make_uint4(q.c[0], q.c[1], q.c[2], q.c[3]);
+        sc_st(lay.p[log_in - 1], (size_t)blockIdx.x * n + tid, p);
+        sc_st(lay.q[log_in - 1], (size_t)blockIdx.x * n + tid, q);
+        sp[tid] = ext_pack(p), sq[tid] = ext_pack(q);
     }
     for (unsigned d = 1; d < depth; d++) {
         zk_syncthreads();
         n >>= 1;
         if (tid < n) {
-            const uint4 a = sp[2 * tid], b = sp[2 * tid + 1], c = sq[2 * tid], e = sq[2 * tid + 1];
-            const Ext p0{{a.x, a.y, a.z, a.w}}, p1{{b.x, b.y, b.z, b.w}}, q0{{c.x, c.y, c.z, c.w}}, q1{{e.x, e.y, e.z, e.w}};
+            const Ext p0 = ext_unpack(sp[2 * tid]), p1 = ext_unpack(sp[2 * tid + 1]), q0 = ext_unpack(sq[2 * tid]), q1 = ext_unpack(sq[2 * tid + 1]);
             p = ext_add(ext_mul(p0, q1), ext_mul(p1, q0));
             q = ext_mul(q0, q1);
-            gkr_st(lay.p[log_in - 1 - d], (size_t)blockIdx.x * n + tid, p);
-            gkr_st(lay.q[log_in - 1 - d], (size_t)blockIdx.x * n + tid, q);
+            sc_st(lay.p[log_in - 1 - d], (size_t)blockIdx.x * n + tid, p);
+            sc_st(lay.q[log_in - 1 - d], (size_t)blockIdx.x * n + tid, q);
         }
         zk_syncthreads();
-        if (tid < n) {
-            sp[tid] = make_uint4(p.c[0], p.c[1], p.c[2], p.c[3]);
-            sq[tid] = make_uint4(q.c[0], q.c[1], q.c[2], q.c[3]);
-        }
+        if (tid < n) sp[tid] = ext_pack(p), sq[tid] = ext_pack(q);
     }
 }
 
@@ -95,134 +76,55 @@ struct GkrSrc {
     const uint32_t* q;
     const uint32_t* tab[5];
     int tree, base;
-};
-__device__ __forceinline__ Ext gkr_src(const GkrSrc& s, int t, size_t j) {
-    if (s.tree && t < 4) {
-        const size_t i = 2 * j + (t & 1);
-        if (t < 2) return s.base ? ext_from_base(s.p[i]) : gkr_ld(s.p, i);
-        return gkr_ld(s.q, i);
-    }
-    return gkr_ld(s.tab[t], j);
-}
-// g at t = 0, 2, 3 of the pair (f0, f1) of every table: eq * (p0 q1 + p1 q0 + lambda q0 q1)
-__device__ __forceinline__ Ext gkr_g(const Ext* v, const Ext& lam) {
-    const Ext qq = ext_mul(v[2], v[3]);
-    const Ext s = ext_add(ext_add(ext_mul(v[0], v[3]), ext_mul(v[1], v[2])), ext_mul(lam, qq));
-    return ext_mul(v[4], s);
-}
-__device__ __forceinline__ void gkr_eval(const Ext* f0, const Ext* f1, const Ext& lam, Ext* acc) {
-    Ext v[5], d[5];
-#pragma unroll
-    for (int t = 0; t < 5; t++) v[t] = f0[t], d[t] = ext_sub(f1[t], f0[t]);
-    acc[0] = ext_add(acc[0], gkr_g(v, lam));
-#pragma unroll
-    for (int t = 0; t < 5; t++) v[t] = ext_add(f1[t], d[t]);
-    acc[1] = ext_add(acc[1], gkr_g(v, lam));
-#pragma unroll
-    for (int t = 0; t < 5; t++) v[t] = ext_add(v[t], d[t]);
-    acc[2] = ext_add(acc[2], gkr_g(v, lam));
-}
-__device__ __forceinline__ uint32_t gkr_wave_sum(uint32_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = madd(x, __shfl_xor(x, off, 64));
-    return x;
-}
-
-// one streaming round: fold with r (r == null: round 0, nothing to fold) and evaluate s(0), s(2), s(3) over n_pairs pairs
-struct GkrPass {
-    GkrSrc src;
-    uint32_t* dst;   // five tables, `dst_stride` words apart
-    size_t dst_stride;
-    const uint32_t* r;
-    const uint32_t* lam;
-    size_t n_pairs;
-    uint32_t* partial;   // [12][GKR_NB]
-};
-__global__ __launch_bounds__(256) void k_gkr_pass(GkrPass a) {
-    __shared__ uint32_t red[4][12];
-    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const Ext lam = gkr_ld(a.lam, 0);
-    const Ext r = a.r ? gkr_ld(a.r, 0) : ext_zero();
-    Ext acc[3] = {ext_zero(), ext_zero(), ext_zero()};
-    for (size_t y = (size_t)blockIdx.x * 256 + tid; y < a.n_pairs; y += (size_t)gridDim.x * 256) {
-        Ext f0[5], f1[5];
-#pragma unroll
-        for (int t = 0; t < 5; t++) {
-            if (a.r) {
-                const Ext s0 = gkr_src(a.src, t, 4 * y), s1 = gkr_src(a.src, t, 4 * y + 1);
-                const Ext s2 = gkr_src(a.src, t, 4 * y + 2), s3 = gkr_src(a.src, t, 4 * y + 3);
-                f0[t] = gkr_fold(s0, s1, r), f1[t] = gkr_fold(s2, s3, r);
-                gkr_st(a.dst + t * a.dst_stride, 2 * y, f0[t]);
-                gkr_st(a.dst + t * a.dst_stride, 2 * y + 1, f1[t]);
-            } else {
-                f0[t] = gkr_src(a.src, t, 2 * y), f1[t] = gkr_src(a.src, t, 2 * y + 1);
-            }
+    __device__ __forceinline__ Ext operator()(unsigned t, size_t j) const {
+        if (tree && t < 4) {
+            const size_t i = 2 * j + (t & 1);
+            if (t < 2) return base ? ext_from_base(p[i]) : sc_ld(p, i);
+            return sc_ld(q, i);
         }
-        gkr_eval(f0, f1, lam, acc);
+        return sc_ld(tab[t], j);
     }
-#pragma unroll
-    for (int e = 0; e < 3; e++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t x = gkr_wave_sum(acc[e].c[q]);
-            if (lane == 0) red[wave][4 * e + q] = x;
-        }
-    zk_syncthreads();
-    if (tid < 12) a.partial[(size_t)tid * GKR_NB + blockIdx.x] = madd(madd(red[0][tid], red[1][tid]), madd(red[2][tid], red[3][tid]));
-}
-
-// the partial sums of a pass -> the round polynomial: written into the proof, observed, and the round challenge sampled
-__global__ __launch_bounds__(64) void k_gkr_round_tr(DevTranscript* tr, const uint32_t* __restrict__ partial, unsigned nb,
-                                                      uint32_t* __restrict__ proof_out, uint32_t* __restrict__ r_out) {
-    const unsigned lane = threadIdx.x;
-    const CoopConsts cc = coop_load_consts(lane & 15u);
-    uint32_t s[12] = {};
-    for (unsigned b = lane; b < nb; b += 64)   // twelve independent loads per step
-#pragma unroll
-        for (int k = 0; k < 12; k++) s[k] = madd(s[k], partial[(size_t)k * GKR_NB + b]);
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = gkr_wave_sum(s[k]);
-    TrRegs R = tr_load(tr, lane);
-#pragma unroll
-    for (int k = 0; k < 12; k++) {
-        if (lane == 0) proof_out[k] = from_monty(s[k]);
-        tr_observe1(R, lane, s[k], cc);
+};
+// a layer's round: s(x) = sum_y eq (p0 q1 + p1 q0 + lambda q0 q1) at 0, 2, 3
+struct GkrRound {
+    static constexpr unsigned T = 5, E = 3;
+    const uint32_t* lam_p;
+    Ext lam;
+    __device__ __forceinline__ void load() { lam = sc_ld(lam_p, 0); }
+    __device__ __forceinline__ Ext operator()(const Ext* v) const {
+        const Ext qq = ext_mul(v[2], v[3]);
+        const Ext s = ext_add(ext_add(ext_mul(v[0], v[3]), ext_mul(v[1], v[2])), ext_mul(lam, qq));
+        return ext_mul(v[4], s);
     }
-    for (int q = 0; q < 4; q++) {
-        const uint32_t v = tr_sample1(R, lane, cc);
-        if (lane == 0) r_out[q] = v;
-    }
-    tr_store(tr, R, lane);
-}
+};
 
 // eq(rho, x) over the highest nv variables of k (x_{k-nv} .. x_{k-1}), by doubling in LDS: out[i], i < 2^nv, bit b of i = x_{k-nv+b}
-__global__ __launch_bounds__(GKR_SW) void k_gkr_eq_seed(const uint32_t* __restrict__ rho, unsigned k, unsigned nv, uint32_t* __restrict__ out) {
-    __shared__ uint4 e[GKR_T];
+__global__ __launch_bounds__(SC_SW) void k_gkr_eq_seed(const uint32_t* __restrict__ rho, unsigned k, unsigned nv, uint32_t* __restrict__ out) {
+    __shared__ uint4 e[SC_T];
     const unsigned tid = threadIdx.x;
-    if (tid == 0) e[0] = make_uint4(MONTY_ONE, 0, 0, 0);
+    if (tid == 0) e[0] = ext_pack(ext_one());
     for (unsigned s = 1, j = k - 1; s < (1u << nv); s <<= 1, j--) {
         zk_syncthreads();
-        const Ext rj = gkr_ld(rho, j);
+        const Ext rj = sc_ld(rho, j);
         Ext v = ext_zero();
-        if (tid < s) v = Ext{{e[tid].x, e[tid].y, e[tid].z, e[tid].w}};
+        if (tid < s) v = ext_unpack(e[tid]);
         zk_syncthreads();
         if (tid < s) {
             const Ext hi = ext_mul(v, rj), lo = ext_sub(v, hi);   // v (1 - rho_j), v rho_j
-            e[2 * tid] = make_uint4(lo.c[0], lo.c[1], lo.c[2], lo.c[3]);
-            e[2 * tid + 1] = make_uint4(hi.c[0], hi.c[1], hi.c[2], hi.c[3]);
+            e[2 * tid] = ext_pack(lo), e[2 * tid + 1] = ext_pack(hi);
         }
     }
     zk_syncthreads();
-    for (unsigned i = tid; i < (1u << nv); i += GKR_SW) reinterpret_cast<uint4*>(out)[i] = e[i];
+    for (unsigned i = tid; i < (1u << nv); i += SC_SW) reinterpret_cast<uint4*>(out)[i] = e[i];
 }
 // one doubling: out[2y + b] = in[y] * (b ? rho_j : 1 - rho_j), y < n
 __global__ __launch_bounds__(256) void k_gkr_eq_double(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n,
                                                        const uint32_t* __restrict__ rho_j) {
     const size_t y = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (y >= n) return;
-    const Ext v = gkr_ld(in, y), hi = ext_mul(v, gkr_ld(rho_j, 0));
-    gkr_st(out, 2 * y, ext_sub(v, hi));
-    gkr_st(out, 2 * y + 1, hi);
+    const Ext v = sc_ld(in, y), hi = ext_mul(v, sc_ld(rho_j, 0));
+    sc_st(out, 2 * y, ext_sub(v, hi));
+    sc_st(out, 2 * y + 1, hi);
 }
 
 // ---- the single-workgroup form --------------------------------------------------------------------------------------------------
@@ -240,17 +142,9 @@ struct GkrSmall {
     uint32_t* lam;   // 1 ext
     uint32_t* out;   // proof words, then the point (4 L), then the claims (8), canonical
 };
-__device__ __forceinline__ void gkr_lds_st(uint32_t* X, unsigned t, unsigned j, const Ext& e) {
-    reinterpret_cast<uint4*>(X)[(size_t)t * GKR_T + j] = make_uint4(e.c[0], e.c[1], e.c[2], e.c[3]);
-}
-__device__ __forceinline__ Ext gkr_lds_ld(const uint32_t* X, unsigned t, unsigned j) {
-    const uint4 v = reinterpret_cast<const uint4*>(X)[(size_t)t * GKR_T + j];
-    return Ext{{v.x, v.y, v.z, v.w}};
-}
-__global__ __launch_bounds__(GKR_SW) void k_gkr_small(GkrSmall a) {
-    extern __shared__ uint32_t X[];   // five tables of GKR_T extension elements
-    __shared__ uint32_t red[GKR_SW / 64][12];
-    __shared__ uint32_t s_rho[GKR_MAXL][4], s_r[GKR_MAXL][4], s_lam[4], s_chal[4];
+__global__ __launch_bounds__(SC_SW) void k_gkr_small(GkrSmall a) {
+    extern __shared__ uint32_t X[];   // five tables of SC_T extension elements
+    __shared__ uint32_t s_rho[GKR_MAXL][4], s_r[GKR_MAXL][4], s_lam[4];
     const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     TrRegs R{};
     CoopConsts cc{};
@@ -258,7 +152,7 @@ __global__ __launch_bounds__(GKR_SW) void k_gkr_small(GkrSmall a) {
     unsigned k = a.tail ? a.k_last : 0;
     if (!a.tail) {
         if (wave == 0) {   // root (P, Q)
-            const Ext P = gkr_ld(a.lay.p[0], 0), Q = gkr_ld(a.lay.q[0], 0);
+            const Ext P = sc_ld(a.lay.p[0], 0), Q = sc_ld(a.lay.q[0], 0);
             for (int w = 0; w < 8; w++) {
                 const uint32_t v = w < 4 ? P.c[w] : Q.c[w - 4];
                 if (lane == 0) a.out[w] = from_monty(v);
@@ -278,78 +172,39 @@ __global__ __launch_bounds__(GKR_SW) void k_gkr_small(GkrSmall a) {
         unsigned m, i;
         if (a.tail) {
             m = a.m, i = a.i0;
-            const Ext rp = gkr_ld(a.r, a.i0 - 1);
-            for (unsigned y = tid; y < m; y += GKR_SW)
+            const Ext rp = sc_ld(a.r, a.i0 - 1);
+            for (unsigned y = tid; y < m; y += SC_SW)
 #pragma unroll
-                for (int t = 0; t < 5; t++) gkr_lds_st(X, t, y, gkr_fold(gkr_src(a.src, t, 2 * y), gkr_src(a.src, t, 2 * y + 1), rp));
+                for (int t = 0; t < 5; t++) sc_st(X, t * SC_T + y, sc_fold(a.src(t, 2 * y), a.src(t, 2 * y + 1), rp));
         } else {
             m = 1u << k, i = 0;
             GkrSrc s{};
             s.p = a.lay.p[k + 1], s.q = a.lay.q[k + 1], s.tree = 1, s.base = a.base_leaves && k + 1 == a.L;
-            for (unsigned y = tid; y < m; y += GKR_SW)
+            for (unsigned y = tid; y < m; y += SC_SW)
 #pragma unroll
-                for (int t = 0; t < 4; t++) gkr_lds_st(X, t, y, gkr_src(s, t, y));
-            if (tid == 0) gkr_lds_st(X, 4, 0, ext_one());
+                for (int t = 0; t < 4; t++) sc_st(X, t * SC_T + y, s(t, y));
+            if (tid == 0) sc_st(X, 4 * SC_T, ext_one());
             for (unsigned sz = 1, j = k - 1; sz < m; sz <<= 1, j--) {   // eq(rho_k, .) by doubling, highest variable first
                 zk_syncthreads();
                 const Ext rj{{s_rho[j][0], s_rho[j][1], s_rho[j][2], s_rho[j][3]}};
-                Ext v[GKR_T / GKR_SW];
-                for (unsigned y = tid, c = 0; y < sz; y += GKR_SW, c++) v[c] = gkr_lds_ld(X, 4, y);
+                Ext v[SC_T / SC_SW];
+                for (unsigned y = tid, c = 0; y < sz; y += SC_SW, c++) v[c] = sc_ld(X, 4 * SC_T + y);
                 zk_syncthreads();
-                for (unsigned y = tid, c = 0; y < sz; y += GKR_SW, c++) {
+                for (unsigned y = tid, c = 0; y < sz; y += SC_SW, c++) {
                     const Ext hi = ext_mul(v[c], rj);
-                    gkr_lds_st(X, 4, 2 * y, ext_sub(v[c], hi));
-                    gkr_lds_st(X, 4, 2 * y + 1, hi);
+                    sc_st(X, 4 * SC_T + 2 * y, ext_sub(v[c], hi));
+                    sc_st(X, 4 * SC_T + 2 * y + 1, hi);
                 }
             }
         }
         zk_syncthreads();
-        const Ext lam{{s_lam[0], s_lam[1], s_lam[2], s_lam[3]}};
+        const GkrRound g{nullptr, Ext{{s_lam[0], s_lam[1], s_lam[2], s_lam[3]}}};
         uint32_t* proof_k = a.out + gkr_layer_off(k);
-        for (; i < k; i++, m >>= 1) {
-            Ext acc[3] = {ext_zero(), ext_zero(), ext_zero()};
-            if (tid < m / 2) {   // m <= GKR_T = 2 GKR_SW: one pair per thread
-                Ext f0[5], f1[5];
-#pragma unroll
-                for (int t = 0; t < 5; t++) f0[t] = gkr_lds_ld(X, t, 2 * tid), f1[t] = gkr_lds_ld(X, t, 2 * tid + 1);
-                gkr_eval(f0, f1, lam, acc);
-            }
-#pragma unroll
-            for (int e = 0; e < 3; e++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t x = gkr_wave_sum(acc[e].c[q]);
-                    if (lane == 0) red[wave][4 * e + q] = x;
-                }
-            zk_syncthreads();
-            if (wave == 0) {
-                for (int w = 0; w < 12; w++) {
-                    uint32_t x = 0;
-                    for (unsigned v = 0; v < GKR_SW / 64; v++) x = madd(x, red[v][w]);
-                    if (lane == 0) proof_k[12 * i + w] = from_monty(x);
-                    tr_observe1(R, lane, x, cc);
-                }
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t v = tr_sample1(R, lane, cc);
-                    if (lane == 0) s_chal[q] = v, s_r[i][q] = v, a.r[4 * i + q] = v;
-                }
-            }
-            zk_syncthreads();
-            const Ext r{{s_chal[0], s_chal[1], s_chal[2], s_chal[3]}};
-            Ext nv[5];
-            if (tid < m / 2)
-#pragma unroll
-                for (int t = 0; t < 5; t++) nv[t] = gkr_fold(gkr_lds_ld(X, t, 2 * tid), gkr_lds_ld(X, t, 2 * tid + 1), r);
-            zk_syncthreads();
-            if (tid < m / 2)
-#pragma unroll
-                for (int t = 0; t < 5; t++) gkr_lds_st(X, t, tid, nv[t]);
-            zk_syncthreads();
-        }
+        for (; i < k; i++, m >>= 1) sc_small_round(g, X, SC_T, m, R, cc, proof_k + 12 * i, a.r + 4 * i, s_r[i]);   // m <= 2 SC_SW
         // end of layer k: p_{k+1}(0, r), p_{k+1}(1, r), q_{k+1}(0, r), q_{k+1}(1, r); mu; rho_{k+1} = (mu, r_0 .. r_{k-1})
         if (wave == 0) {
             Ext v[4];
-            for (int t = 0; t < 4; t++) v[t] = gkr_lds_ld(X, t, 0);
+            for (int t = 0; t < 4; t++) v[t] = sc_ld(X, t * SC_T);
             for (int w = 0; w < 16; w++) {
                 const uint32_t x = v[w >> 2].c[w & 3];
                 if (lane == 0) proof_k[12 * k + w] = from_monty(x);
@@ -364,7 +219,7 @@ __global__ __launch_bounds__(GKR_SW) void k_gkr_small(GkrSmall a) {
             }
             if (k + 1 == a.L) {
                 if (lane == 0) {
-                    const Ext cp = gkr_fold(v[0], v[1], mu), cq = gkr_fold(v[2], v[3], mu);
+                    const Ext cp = sc_fold(v[0], v[1], mu), cq = sc_fold(v[2], v[3], mu);
                     uint32_t* pt = a.out + gkr_proof_words(a.L);
                     for (unsigned j = 0; j <= k; j++)
                         for (int q = 0; q < 4; q++) pt[4 * j + q] = from_monty(s_rho[j][q]);
@@ -397,7 +252,7 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 int gkr_prove_device(zkhip_ctx* ctx, DevTranscript* d_t, const uint32_t* d_num, bool num_ext, const uint32_t* d_den, unsigned L,
                      const uint32_t** d_result) {
     if (L < 1 || L > GKR_MAXL) return set_error(ctx, ZKHIP_ERR_INVALID, "gkr: log_n out of range");
-    const bool big = L - 1 > GKR_LT;   // some layer needs the streaming passes
+    const bool big = L - 1 > SC_LT;   // some layer needs the streaming passes
     const size_t capA = big ? (size_t)1 << (L - 2) : 1, capB = big ? (size_t)1 << (L - 3) : 1, capE = big ? (size_t)1 << (L - 1) : 1;
     size_t off = 0;
     std::vector<size_t> o_layer(L);
@@ -406,7 +261,7 @@ int gkr_prove_device(zkhip_ctx* ctx, DevTranscript* d_t, const uint32_t* d_num, 
     const size_t o_B = off; off += align256(5 * capB * 16);
     const size_t o_E0 = off; off += align256(capE * 16);
     const size_t o_E1 = off; off += align256(capE * 16);
-    const size_t o_partial = off; off += align256(12 * GKR_NB * 4);
+    const size_t o_partial = off; off += align256(12 * SC_NB * 4);
     const size_t o_rho = off; off += align256(GKR_MAXL * 16);
     const size_t o_r = off; off += align256(GKR_MAXL * 16);
     const size_t o_lam = off; off += 256;
@@ -422,7 +277,7 @@ int gkr_prove_device(zkhip_ctx* ctx, DevTranscript* d_t, const uint32_t* d_num, 
     }
     static DeviceOnce attr_set;
     if (attr_set.need(ctx->device)) {
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_gkr_small, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * GKR_T * 16));
+        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_gkr_small, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * SC_T * 16));
         attr_set.mark(ctx->device);
     }
     uint8_t* base = (uint8_t*)ctx->gkr_ws;
@@ -448,24 +303,24 @@ int gkr_prove_device(zkhip_ctx* ctx, DevTranscript* d_t, const uint32_t* d_num, 
         }
         ZK_HIP_CHECK(ctx, hipGetLastError());
     }
-    const size_t lds = 5 * GKR_T * 16;
-    {   // root and layers 0 .. GKR_LT: one workgroup
+    const size_t lds = 5 * SC_T * 16;
+    {   // root and layers 0 .. SC_LT: one workgroup
         KernelScope ks(ctx, "gkr_small");
         GkrSmall s{};
-        s.tr = d_t, s.lay = lay, s.L = L, s.k_last = std::min(L - 1, GKR_LT), s.tail = 0, s.base_leaves = !num_ext;
+        s.tr = d_t, s.lay = lay, s.L = L, s.k_last = std::min(L - 1, SC_LT), s.tail = 0, s.base_leaves = !num_ext;
         s.rho = rho, s.r = r, s.lam = lam, s.out = out;
-        hipLaunchKernelGGL(k_gkr_small, dim3(1), dim3(GKR_SW), lds, st, s);
+        hipLaunchKernelGGL(k_gkr_small, dim3(1), dim3(SC_SW), lds, st, s);
         ZK_HIP_CHECK(ctx, hipGetLastError());
     }
-    for (unsigned k = GKR_LT + 1; k < L; k++) {
-        {   // eq(rho_k, .): the highest GKR_LT variables in one workgroup, then one doubling per variable; lands in E0
-            const unsigned nd = k - GKR_LT;
+    for (unsigned k = SC_LT + 1; k < L; k++) {
+        {   // eq(rho_k, .): the highest SC_LT variables in one workgroup, then one doubling per variable; lands in E0
+            const unsigned nd = k - SC_LT;
             uint32_t* e = nd % 2 == 0 ? E0 : E1;
             {
                 KernelScope ks(ctx, "gkr_eq");
-                hipLaunchKernelGGL(k_gkr_eq_seed, dim3(1), dim3(GKR_SW), 0, st, (const uint32_t*)rho, k, GKR_LT, e);
+                hipLaunchKernelGGL(k_gkr_eq_seed, dim3(1), dim3(SC_SW), 0, st, (const uint32_t*)rho, k, SC_LT, e);
             }
-            size_t n = GKR_T;
+            size_t n = SC_T;
             for (unsigned j = nd; j-- > 0; n <<= 1) {
                 KernelScope ks(ctx, "gkr_eq");
                 uint32_t* o = e == E0 ? E1 : E0;
@@ -479,25 +334,26 @@ int gkr_prove_device(zkhip_ctx* ctx, DevTranscript* d_t, const uint32_t* d_num, 
         src.p = lay.p[k + 1], src.q = lay.q[k + 1], src.tab[4] = E0, src.tree = 1, src.base = !num_ext && k + 1 == L;
         size_t m = (size_t)1 << k;
         unsigned i = 0;
-        for (; m > GKR_T; m >>= 1, i++) {   // round i on tables of m entries: fold with r_{i-1}, evaluate s_i
-            GkrPass p{};
-            p.src = src, p.lam = lam, p.n_pairs = m / 2, p.partial = partial;
+        for (; m > SC_T; m >>= 1, i++) {   // round i on tables of m entries: fold with r_{i-1}, evaluate s_i
+            ScPass<GkrSrc, GkrRound> p{};
+            p.src = src, p.g.lam_p = lam, p.n_pairs = m / 2, p.partial = partial;
             p.r = i ? r + 4 * (i - 1) : nullptr;
-            if (i) p.dst = i % 2 ? A : B, p.dst_stride = 4 * (i % 2 ? capA : capB);
-            const unsigned nb = (unsigned)std::min<size_t>(GKR_NB, (m / 2 + 255) / 256);
+            if (i)
+                for (int t = 0; t < 5; t++) p.dst[t] = (i % 2 ? A : B) + 4 * t * (i % 2 ? capA : capB);
+            const unsigned nb = (unsigned)std::min<size_t>(SC_NB, (m / 2 + 255) / 256);
             {
                 KernelScope ks(ctx, "gkr_pass");
-                hipLaunchKernelGGL(k_gkr_pass, dim3(nb), dim3(256), 0, st, p);
+                hipLaunchKernelGGL(k_sc_pass, dim3(nb), dim3(256), 0, st, p);
             }
             {
                 KernelScope ks(ctx, "gkr_round_tr");
-                hipLaunchKernelGGL(k_gkr_round_tr, dim3(1), dim3(64), 0, st, d_t, (const uint32_t*)partial, nb, out + gkr_layer_off(k) + 12 * i,
+                hipLaunchKernelGGL(k_sc_round_tr<12>, dim3(1), dim3(64), 0, st, d_t, (const uint32_t*)partial, nb, out + gkr_layer_off(k) + 12 * i,
                                    r + 4 * i);
             }
             ZK_HIP_CHECK(ctx, hipGetLastError());
             if (i) {
                 src.tree = 0;
-                for (int t = 0; t < 5; t++) src.tab[t] = p.dst + t * p.dst_stride;
+                for (int t = 0; t < 5; t++) src.tab[t] = p.dst[t];
             }
         }
         {   // the rest of layer k in one workgroup
@@ -505,7 +361,7 @@ int gkr_prove_device(zkhip_ctx* ctx, DevTranscript* d_t, const uint32_t* d_num, 
             GkrSmall s{};
             s.tr = d_t, s.lay = lay, s.L = L, s.k_last = k, s.tail = 1, s.i0 = i, s.m = (unsigned)m, s.base_leaves = !num_ext, s.src = src;
             s.rho = rho, s.r = r, s.lam = lam, s.out = out;
-            hipLaunchKernelGGL(k_gkr_small, dim3(1), dim3(GKR_SW), lds, st, s);
+            hipLaunchKernelGGL(k_gkr_small, dim3(1), dim3(SC_SW), lds, st, s);
             ZK_HIP_CHECK(ctx, hipGetLastError());
         }
     }
@@ -514,24 +370,6 @@ int gkr_prove_device(zkhip_ctx* ctx, DevTranscript* d_t, const uint32_t* d_num, 
 }
 
 // ---- the host verifier ---------------------------------------------------------------------------------------------------------
-namespace {
-Ext gkr_canon(const uint32_t* p) { return Ext{{to_monty(p[0]), to_monty(p[1]), to_monty(p[2]), to_monty(p[3])}}; }
-void gkr_put(uint32_t* out, const Ext& e) {
-    for (int q = 0; q < 4; q++) out[q] = from_monty(e.c[q]);
-}
-Ext gkr_const(uint32_t c) { return ext_from_base(to_monty(c)); }
-// the cubic through s(0), s(1), s(2), s(3), at x (Lagrange)
-Ext gkr_interp(const Ext s[4], const Ext& x) {
-    const Ext x1 = ext_sub(x, gkr_const(1)), x2 = ext_sub(x, gkr_const(2)), x3 = ext_sub(x, gkr_const(3));
-    const Ext inv2 = gkr_const(1006632961u), inv6 = gkr_const(1677721601u);
-    const Ext l0 = ext_neg(ext_mul(ext_mul(ext_mul(x1, x2), x3), inv6));
-    const Ext l1 = ext_mul(ext_mul(ext_mul(x, x2), x3), inv2);
-    const Ext l2 = ext_neg(ext_mul(ext_mul(ext_mul(x, x1), x3), inv2));
-    const Ext l3 = ext_mul(ext_mul(ext_mul(x, x1), x2), inv6);
-    return ext_add(ext_add(ext_mul(l0, s[0]), ext_mul(l1, s[1])), ext_add(ext_mul(l2, s[2]), ext_mul(l3, s[3])));
-}
-}  // namespace
-
 // replays the proof on `ch`; point_out (4 L words) / claims_out (8 words) canonical, root_out = (P, Q) in Montgomery form
 int gkr_verify_host(HostChallenger& ch, const uint32_t* proof, size_t words, unsigned L, uint32_t* point_out, uint32_t* claims_out,
                     Ext root_out[2]) {
@@ -539,7 +377,7 @@ int gkr_verify_host(HostChallenger& ch, const uint32_t* proof, size_t words, uns
     for (size_t w = 0; w < words; w++)
         if (proof[w] >= P) return ZKHIP_ERR_VERIFY;
     for (size_t w = 0; w < 8; w++) ch.observe(to_monty(proof[w]));
-    Ext cp = gkr_canon(proof), cq = gkr_canon(proof + 4);
+    Ext cp = ext_from_canon(proof), cq = ext_from_canon(proof + 4);
     root_out[0] = cp, root_out[1] = cq;
     std::vector<Ext> rho, r;
     for (unsigned k = 0; k < L; k++) {
@@ -549,21 +387,15 @@ int gkr_verify_host(HostChallenger& ch, const uint32_t* proof, size_t words, uns
         r.clear();
         for (unsigned i = 0; i < k; i++) {
             const uint32_t* w = pk + 12 * i;
-            Ext s[4];
-            s[0] = gkr_canon(w), s[2] = gkr_canon(w + 4), s[3] = gkr_canon(w + 8);
-            s[1] = ext_sub(claim, s[0]);
+            const Ext s0 = ext_from_canon(w), s[4] = {s0, ext_sub(claim, s0), ext_from_canon(w + 4), ext_from_canon(w + 8)};
             for (int j = 0; j < 12; j++) ch.observe(to_monty(w[j]));
             const Ext ri = ch.sample_ext();
-            claim = gkr_interp(s, ri);
+            claim = poly_at(s, 3, ri);
             r.push_back(ri);
         }
         const uint32_t* w = pk + 12 * k;
-        const Ext p0 = gkr_canon(w), p1 = gkr_canon(w + 4), q0 = gkr_canon(w + 8), q1 = gkr_canon(w + 12);
-        Ext eq = ext_one();
-        for (unsigned j = 0; j < k; j++) {
-            const Ext pr = ext_mul(rho[j], r[j]);   // rho r + (1 - rho)(1 - r) = 1 - rho - r + 2 rho r
-            eq = ext_mul(eq, ext_add(ext_sub(ext_sub(gkr_const(1), rho[j]), r[j]), ext_add(pr, pr)));
-        }
+        const Ext p0 = ext_from_canon(w), p1 = ext_from_canon(w + 4), q0 = ext_from_canon(w + 8), q1 = ext_from_canon(w + 12);
+        const Ext eq = eq_eval(rho.data(), r.data(), k);
         const Ext body = ext_add(ext_add(ext_mul(p0, q1), ext_mul(p1, q0)), ext_mul(lam, ext_mul(q0, q1)));
         if (!ext_eq(ext_mul(eq, body), claim)) return ZKHIP_ERR_VERIFY;
         for (int j = 0; j < 16; j++) ch.observe(to_monty(w[j]));
@@ -574,8 +406,8 @@ int gkr_verify_host(HostChallenger& ch, const uint32_t* proof, size_t words, uns
         cq = ext_add(q0, ext_mul(mu, ext_sub(q1, q0)));
     }
     if (point_out)
-        for (unsigned j = 0; j < L; j++) gkr_put(point_out + 4 * j, rho[j]);
-    if (claims_out) gkr_put(claims_out, cp), gkr_put(claims_out + 4, cq);
+        for (unsigned j = 0; j < L; j++) ext_to_canon(point_out + 4 * j, rho[j]);
+    if (claims_out) ext_to_canon(claims_out, cp), ext_to_canon(claims_out + 4, cq);
     return ZKHIP_OK;
 }
 
@@ -623,7 +455,7 @@ int zkhip_bus_gkr_verify(const uint32_t* prefix, size_t n_prefix, const uint32_t
     HostChallenger ch;
     ch.observe_canon(prefix, n_prefix);
     const Ext gamma = ch.sample_ext(), beta = ch.sample_ext();
-    if (challenges_out) gkr_put(challenges_out, gamma), gkr_put(challenges_out + 4, beta);
+    if (challenges_out) ext_to_canon(challenges_out, gamma), ext_to_canon(challenges_out + 4, beta);
     Ext root[2];
     ZK_TRY(gkr_verify_host(ch, proof, words, log_leaves, point_out, claims_out, root));
     if (!ext_eq(root[0], ext_zero()) || ext_eq(root[1], ext_zero())) return ZKHIP_ERR_VERIFY;   // balanced: P = 0, Q != 0

@@ -14,18 +14,9 @@
 // All are HBM-streaming (16-byte lanes, coalesced 1 KiB per wave instruction).
 #include <algorithm>
 
-#include "lds_barrier.hpp"
-#include "zkhip_internal.hpp"
+#include "sumcheck_dev.hpp"
 
 namespace zk {
-
-__device__ __forceinline__ Ext ld4(const uint32_t* p, size_t i) {
-    uint4 v = reinterpret_cast<const uint4*>(p)[i];
-    return Ext{{v.x, v.y, v.z, v.w}};
-}
-__device__ __forceinline__ void st4(uint32_t* p, size_t i, const Ext& e) {
-    reinterpret_cast<uint4*>(p)[i] = make_uint4(e.c[0], e.c[1], e.c[2], e.c[3]);
-}
 
 // ---- batch inversion ---------------------------------------------------------------------------
 constexpr int BI_K = 8;
@@ -43,7 +34,7 @@ __global__ __launch_bounds__(256) void k_ext_batch_inverse(const uint32_t* in, u
 #pragma unroll
     for (int k = 0; k < BI_K; k++) {
         size_t i = gid + (size_t)k * nthreads;
-        x[k] = i < n ? ld4(in, i) : ext_one();
+        x[k] = i < n ? sc_ld(in, i) : ext_one();
         if ((x[k].c[0] | x[k].c[1] | x[k].c[2] | x[k].c[3]) == 0) {
             zero_mask |= 1u << k;
             x[k] = ext_one();
@@ -59,7 +50,7 @@ __global__ __launch_bounds__(256) void k_ext_batch_inverse(const uint32_t* in, u
         if (i < n) {
             if (zero_mask & (1u << k)) o = ext_zero();
             if (num) o = ext_mul_base(o, num[i]);  // LogUp term num/den
-            st4(out, i, o);
+            sc_st(out, i, o);
         }
     }
 }
@@ -97,7 +88,7 @@ __global__ __launch_bounds__(256) void k_scan_local(uint32_t* __restrict__ data,
     Ext run = ext_zero();
 #pragma unroll
     for (int k = 0; k < SC_K; k++) {
-        v[k] = base + k < n ? ld4(data, base + k) : ext_zero();
+        v[k] = base + k < n ? sc_ld(data, base + k) : ext_zero();
         run = ext_add(run, v[k]);
         v[k] = run;
     }
@@ -112,10 +103,10 @@ __global__ __launch_bounds__(256) void k_scan_local(uint32_t* __restrict__ data,
         off = ext_add(off, Ext{{wave_tot[w][0], wave_tot[w][1], wave_tot[w][2], wave_tot[w][3]}});
 #pragma unroll
     for (int k = 0; k < SC_K; k++)
-        if (base + k < n) st4(data, base + k, ext_add(v[k], off));
+        if (base + k < n) sc_st(data, base + k, ext_add(v[k], off));
     if (tid == 255) {
         Ext t = ext_add(off, run);
-        st4(totals, blockIdx.x, t);
+        sc_st(totals, blockIdx.x, t);
     }
 }
 // phase 2: one workgroup scans the workgroup totals in place (exclusive -> stored as inclusive)
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(1024) void k_scan_totals(uint32_t* __restrict__ tot
     zk_syncthreads();
     for (size_t start = 0; start < n_blocks; start += 1024) {
         size_t i = start + tid;
-        Ext v = i < n_blocks ? ld4(totals, i) : ext_zero();
+        Ext v = i < n_blocks ? sc_ld(totals, i) : ext_zero();
         Ext incl = wave_inclusive_scan(v, lane);
         if (lane == 63) {
 #pragma unroll
@@ -138,7 +129,7 @@ __global__ __launch_bounds__(1024) void k_scan_totals(uint32_t* __restrict__ tot
         for (unsigned w = 0; w < wave; w++)
             off = ext_add(off, Ext{{wave_tot[w][0], wave_tot[w][1], wave_tot[w][2], wave_tot[w][3]}});
         Ext r = ext_add(incl, off);
-        if (i < n_blocks) st4(totals, i, r);
+        if (i < n_blocks) sc_st(totals, i, r);
         zk_syncthreads();
         if (tid == 1023) {
 #pragma unroll
@@ -150,10 +141,10 @@ __global__ __launch_bounds__(1024) void k_scan_totals(uint32_t* __restrict__ tot
 // phase 3: add the preceding workgroups' total
 __global__ __launch_bounds__(256) void k_scan_add(uint32_t* __restrict__ data, size_t n, const uint32_t* __restrict__ totals) {
     if (blockIdx.x == 0) return;
-    const Ext off = ld4(totals, blockIdx.x - 1);
+    const Ext off = sc_ld(totals, blockIdx.x - 1);
     const size_t base = (size_t)blockIdx.x * SC_BLOCK;
     for (unsigned e = threadIdx.x; e < SC_BLOCK; e += 256)
-        if (base + e < n) st4(data, base + e, ext_add(ld4(data, base + e), off));
+        if (base + e < n) sc_st(data, base + e, ext_add(sc_ld(data, base + e), off));
 }
 
 int ext_inclusive_scan(zkhip_ctx* ctx, uint32_t* d_out, size_t n) {
@@ -195,7 +186,7 @@ __global__ __launch_bounds__(256) void k_scan_local_multi(const ScanSeg* __restr
     Ext run = ext_zero();
 #pragma unroll
     for (int k = 0; k < SC_K; k++) {
-        v[k] = base + k < n ? ld4(data, base + k) : ext_zero();
+        v[k] = base + k < n ? sc_ld(data, base + k) : ext_zero();
         run = ext_add(run, v[k]);
         v[k] = run;
     }
@@ -210,8 +201,8 @@ __global__ __launch_bounds__(256) void k_scan_local_multi(const ScanSeg* __restr
         off = ext_add(off, Ext{{wave_tot[w][0], wave_tot[w][1], wave_tot[w][2], wave_tot[w][3]}});
 #pragma unroll
     for (int k = 0; k < SC_K; k++)
-        if (base + k < n) st4(data, base + k, ext_add(v[k], off));
-    if (tid == 255) st4(sg.totals, lb, ext_add(off, run));
+        if (base + k < n) sc_st(data, base + k, ext_add(v[k], off));
+    if (tid == 255) sc_st(sg.totals, lb, ext_add(off, run));
 }
 // one workgroup per segment scans that segment's workgroup totals
 __global__ __launch_bounds__(1024) void k_scan_totals_multi(const ScanSeg* __restrict__ segs) {
@@ -226,7 +217,7 @@ __global__ __launch_bounds__(1024) void k_scan_totals_multi(const ScanSeg* __res
     zk_syncthreads();
     for (size_t start = 0; start < n_blocks; start += 1024) {
         size_t i = start + tid;
-        Ext v = i < n_blocks ? ld4(totals, i) : ext_zero();
+        Ext v = i < n_blocks ? sc_ld(totals, i) : ext_zero();
         Ext incl = wave_inclusive_scan(v, lane);
         if (lane == 63) {
 #pragma unroll
@@ -237,7 +228,7 @@ __global__ __launch_bounds__(1024) void k_scan_totals_multi(const ScanSeg* __res
         for (unsigned w = 0; w < wave; w++)
             off = ext_add(off, Ext{{wave_tot[w][0], wave_tot[w][1], wave_tot[w][2], wave_tot[w][3]}});
         Ext r = ext_add(incl, off);
-        if (i < n_blocks) st4(totals, i, r);
+        if (i < n_blocks) sc_st(totals, i, r);
         zk_syncthreads();
         if (tid == 1023) {
 #pragma unroll
@@ -250,10 +241,10 @@ __global__ __launch_bounds__(256) void k_scan_add_multi(const ScanSeg* __restric
     const ScanSeg sg = segs[seg_of_block(segs, n_seg, blockIdx.x)];
     const uint32_t lb = blockIdx.x - sg.first_block;
     if (lb == 0) return;
-    const Ext off = ld4(sg.totals, lb - 1);
+    const Ext off = sc_ld(sg.totals, lb - 1);
     const size_t base = (size_t)lb * SC_BLOCK;
     for (unsigned e = threadIdx.x; e < SC_BLOCK; e += 256)
-        if (base + e < sg.n) st4(sg.data, base + e, ext_add(ld4(sg.data, base + e), off));
+        if (base + e < sg.n) sc_st(sg.data, base + e, ext_add(sc_ld(sg.data, base + e), off));
 }
 uint32_t scan_blocks_of(size_t n) { return (uint32_t)((n + SC_BLOCK - 1) / SC_BLOCK); }
 int ext_inclusive_scan_multi(zkhip_ctx* ctx, const ScanSeg* d_segs, uint32_t n_seg, uint32_t total_blocks, bool any_multi_block) {
@@ -275,15 +266,11 @@ int logup_running_sum(zkhip_ctx* ctx, const uint32_t* d_den, const uint32_t* d_n
 }
 
 // ---- MLE fold ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_mle_fold(const uint4* __restrict__ in, uint4* __restrict__ out, size_t n,
+__global__ __launch_bounds__(256) void k_mle_fold(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n,
                                                   const uint32_t* __restrict__ r_p) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const Ext r{{r_p[0], r_p[1], r_p[2], r_p[3]}};
-    uint4 a = in[2 * i], b = in[2 * i + 1];
-    Ext d{{msub(b.x, a.x), msub(b.y, a.y), msub(b.z, a.z), msub(b.w, a.w)}};
-    Ext t = ext_mul(r, d);
-    out[i] = make_uint4(madd(a.x, t.c[0]), madd(a.y, t.c[1]), madd(a.z, t.c[2]), madd(a.w, t.c[3]));
+    sc_st(out, i, sc_fold(sc_ld(in, 2 * i), sc_ld(in, 2 * i + 1), sc_ld(r_p, 0)));
 }
 
 // ---- sum-check round ---------------------------------------------------------------------------
@@ -295,8 +282,7 @@ struct SumcheckArgs {
 };
 // partial[block][t] for t = 0..k
 __global__ __launch_bounds__(256) void k_sumcheck_partial(SumcheckArgs a, uint32_t* __restrict__ partial) {
-    __shared__ uint32_t red[4][(SCR_MAXK + 1) * 4];
-    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const unsigned tid = threadIdx.x;
     Ext acc[SCR_MAXK + 1];
 #pragma unroll
     for (int t = 0; t <= SCR_MAXK; t++) acc[t] = ext_zero();
@@ -305,8 +291,8 @@ __global__ __launch_bounds__(256) void k_sumcheck_partial(SumcheckArgs a, uint32
 #pragma unroll
         for (int j = 0; j < SCR_MAXK; j++)
             if ((uint32_t)j < a.k) {
-                v[j] = ld4(a.tab[j], 2 * i);
-                d[j] = ext_sub(ld4(a.tab[j], 2 * i + 1), v[j]);
+                v[j] = sc_ld(a.tab[j], 2 * i);
+                d[j] = ext_sub(sc_ld(a.tab[j], 2 * i + 1), v[j]);
             }
 #pragma unroll
         for (int t = 0; t <= SCR_MAXK; t++)
@@ -321,28 +307,14 @@ __global__ __launch_bounds__(256) void k_sumcheck_partial(SumcheckArgs a, uint32
                     if ((uint32_t)j < a.k) v[j] = ext_add(v[j], d[j]);  // next evaluation point
             }
     }
-#pragma unroll
-    for (int t = 0; t <= SCR_MAXK; t++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            uint32_t x = acc[t].c[q];
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) x = madd(x, __shfl_xor(x, off, 64));
-            if (lane == 0) red[wave][t * 4 + q] = x;
-        }
-    zk_syncthreads();
-    if (tid < (a.k + 1) * 4) {
-        uint32_t x = madd(madd(red[0][tid], red[1][tid]), madd(red[2][tid], red[3][tid]));
-        partial[(size_t)blockIdx.x * ((SCR_MAXK + 1) * 4) + tid] = x;
-    }
+    sc_block_sum(acc, partial + (size_t)blockIdx.x * ((SCR_MAXK + 1) * 4), 1, (a.k + 1) * 4);
 }
 __global__ __launch_bounds__(64) void k_sumcheck_final(const uint32_t* __restrict__ partial, unsigned n_blocks, unsigned k,
                                                        uint32_t* __restrict__ out_canon) {
     const unsigned slot = blockIdx.x;  // t*4+q
     uint32_t x = 0;
     for (unsigned b = threadIdx.x; b < n_blocks; b += 64) x = madd(x, partial[(size_t)b * ((SCR_MAXK + 1) * 4) + slot]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = madd(x, __shfl_xor(x, off, 64));
+    x = sc_wave_sum(x);
     if (threadIdx.x == 0) out_canon[slot] = from_monty(x);
     (void)k;
 }
@@ -385,8 +357,7 @@ int zkhip_mle_fold(zkhip_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, size_t
     ZK_TRY(get_scratch(ctx, 2, 16, &d_r));
     ZK_TRY(zkhip_h2d(ctx, d_r, rm, 16));
     KernelScope ks(ctx, "mle_fold");
-    hipLaunchKernelGGL(k_mle_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4*)d_in,
-                       (uint4*)d_out, n, (const uint32_t*)d_r);
+    hipLaunchKernelGGL(k_mle_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_in, d_out, n, (const uint32_t*)d_r);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return ZKHIP_OK;
 }

@@ -13,9 +13,45 @@
 #include "../../include/zkhip.h"
 
 namespace zk {
-namespace {
 
+// ---- field helpers of every host verifier (declared in host_challenger.hpp) ----
 Ext ext_from_canon(const uint32_t* p) { return Ext{{to_monty(p[0]), to_monty(p[1]), to_monty(p[2]), to_monty(p[3])}}; }
+void ext_to_canon(uint32_t* out, const Ext& e) {
+    for (int q = 0; q < 4; q++) out[q] = from_monty(e.c[q]);
+}
+
+Ext poly_at(const Ext* s, unsigned d, const Ext& x) {   // Lagrange: sum_j s_j prod_{i != j} (x - i) / (j - i)
+    Ext acc = ext_zero();
+    for (unsigned j = 0; j <= d; j++) {
+        Ext num = s[j];
+        uint32_t den = to_monty(1);
+        for (unsigned i = 0; i <= d; i++)
+            if (i != j) num = ext_mul(num, ext_sub(x, ext_from_base(to_monty(i)))), den = mmul(den, msub(to_monty(j), to_monty(i)));
+        acc = ext_add(acc, ext_mul_base(num, minv(den)));
+    }
+    return acc;
+}
+
+Ext eq_eval(const Ext* p, const Ext* x, size_t n) {
+    Ext acc = ext_one();
+    for (size_t j = 0; j < n; j++) {
+        const Ext px = ext_mul(p[j], x[j]);   // p x + (1 - p)(1 - x) = 1 - p - x + 2 p x
+        acc = ext_mul(acc, ext_add(ext_sub(ext_sub(ext_one(), p[j]), x[j]), ext_add(px, px)));
+    }
+    return acc;
+}
+
+// p3-fri `fold_row` for arity 2: pair k of a layer of 2^(log_n_out+1) values in bit-reversed order sits on the points
+// +-x, x = g^bitrev(k) with g the generator of that size; the line through (x, e0), (-x, e1) is evaluated at beta.
+Ext fold_row(size_t k, unsigned log_n_out, const Ext& beta, const Ext& e0, const Ext& e1) {
+    const uint32_t xx = mpow(two_adic_generator(log_n_out + 1), bitrev32((uint32_t)k, log_n_out));
+    const uint32_t c = mneg(mmul(minv(xx), minv(to_monty(2))));
+    Ext bx = beta;
+    bx.c[0] = msub(bx.c[0], xx);
+    return ext_add(e0, ext_mul(bx, ext_mul_base(ext_sub(e1, e0), c)));
+}
+
+namespace {
 
 // recompute the root implied by an opening of a mixed-height commitment
 bool verify_opening(const uint32_t root_m[8], const std::vector<unsigned>& lhs, const std::vector<size_t>& ws,
@@ -56,16 +92,6 @@ bool verify_opening(const uint32_t root_m[8], const std::vector<unsigned>& lhs, 
         if (level == 0) break;
     }
     return memcmp(cur, root_m, 32) == 0;
-}
-
-// p3-fri `fold_row` for arity 2: pair k of a layer of 2^(log_n_out+1) values in bit-reversed order sits on the points
-// +-x, x = g^bitrev(k) with g the generator of that size; the line through (x, e0), (-x, e1) is evaluated at beta.
-Ext fold_row(size_t k, unsigned log_n_out, const Ext& beta, const Ext& e0, const Ext& e1) {
-    const uint32_t xx = mpow(two_adic_generator(log_n_out + 1), bitrev32((uint32_t)k, log_n_out));
-    const uint32_t c = mneg(mmul(minv(xx), minv(to_monty(2))));
-    Ext bx = beta;
-    bx.c[0] = msub(bx.c[0], xx);
-    return ext_add(e0, ext_mul(bx, ext_mul_base(ext_sub(e1, e0), c)));
 }
 
 }  // namespace

@@ -11,19 +11,15 @@
 //     challenge; once a table holds <= 2^10 entries ONE workgroup runs the round's remaining sum-check rounds with the transcript
 //     in-kernel; the coefficients fold by 2^k in one pass; the out-of-domain answer is a reduction; the weight update adds all of a
 //     round's new eq terms in one pass.  The query indices go to the host once per round (Merkle openings take host indices).
+//     The pass, the one-wave kernel and the rounds of k_whir_small are the sum-check core's (sumcheck_dev.hpp).
 #include <algorithm>
 #include <vector>
 
 #include "host_challenger.hpp"
-#include "lds_barrier.hpp"
-#include "transcript_dev.hpp"
-#include "zkhip_internal.hpp"
+#include "sumcheck_dev.hpp"
 
 namespace zk {
 
-constexpr unsigned WHIR_NB = 1024;         // most workgroups of a streaming pass (partial sums: [nvals * 4][WHIR_NB] words)
-constexpr unsigned WHIR_LT = 10;           // tables of <= 2^WHIR_LT entries: the single-workgroup sum-check
-constexpr unsigned WHIR_SW = 512;          // its threads (one pair each)
 constexpr unsigned WHIR_ZT = 12;           // a zeta-transform tile holds 2^12 words of LDS
 
 struct WhirCols {   // column c, entry i: p[c][i * es[c]]
@@ -69,32 +65,6 @@ WhirLayout whir_layout(const zkhip_whir_params* p, unsigned m, size_t n_cols, co
     }
     L.total = off;
     return L;
-}
-
-__device__ __forceinline__ Ext w_ld(const uint32_t* p, size_t i) {
-    const uint4 v = reinterpret_cast<const uint4*>(p)[i];
-    return Ext{{v.x, v.y, v.z, v.w}};
-}
-__device__ __forceinline__ void w_st(uint32_t* p, size_t i, const Ext& e) {
-    reinterpret_cast<uint4*>(p)[i] = make_uint4(e.c[0], e.c[1], e.c[2], e.c[3]);
-}
-__device__ __forceinline__ Ext w_fold(const Ext& a, const Ext& b, const Ext& r) { return ext_add(a, ext_mul(r, ext_sub(b, a))); }
-__device__ __forceinline__ uint32_t w_wave_sum(uint32_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = madd(x, __shfl_xor(x, off, 64));
-    return x;
-}
-// a 256-thread workgroup's sum of 4 words per thread -> partial[q * WHIR_NB + slot]
-__device__ __forceinline__ void w_block_sum4(const Ext& acc, uint32_t* partial, unsigned slot, uint32_t (*red)[4]) {
-    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t x = w_wave_sum(acc.c[q]);
-        if (lane == 0) red[wave][q] = x;
-    }
-    zk_syncthreads();
-    if (tid < 4) partial[(size_t)tid * WHIR_NB + slot] = madd(madd(red[0][tid], red[1][tid]), madd(red[2][tid], red[3][tid]));
-    zk_syncthreads();
 }
 
 // ---- commit ------------------------------------------------------------------------------------------------------------------
@@ -153,38 +123,37 @@ __global__ __launch_bounds__(256) void k_whir_weight(uint32_t* __restrict__ w, u
     for (unsigned t0 = 0; t0 < np; t0 += 256) {
         const unsigned t = t0 + tid;
         if (t < np) {
-            Ext c = gamma ? ext_pow(w_ld(gamma, 0), (uint64_t)t + 1) : one;
+            Ext c = gamma ? ext_pow(sc_ld(gamma, 0), (uint64_t)t + 1) : one;
             for (unsigned j = lb; j < mv; j++) {
-                const Ext pj = w_ld(pts, (size_t)t * mv + j);
+                const Ext pj = sc_ld(pts, (size_t)t * mv + j);
                 c = ext_mul(c, ((bhi >> (j - 8)) & 1) ? pj : ext_sub(one, pj));
             }
-            hic[tid] = make_uint4(c.c[0], c.c[1], c.c[2], c.c[3]);
+            hic[tid] = ext_pack(c);
         }
         zk_syncthreads();
         const unsigned nt = np - t0 < 256 ? np - t0 : 256;
         for (unsigned u = 0; u < nt; u++) {
-            const uint4 h = hic[u];
-            Ext e{{h.x, h.y, h.z, h.w}};
+            Ext e = ext_unpack(hic[u]);
             for (unsigned j = 0; j < lb; j++) {
-                const Ext pj = w_ld(pts, (size_t)(t0 + u) * mv + j);
+                const Ext pj = sc_ld(pts, (size_t)(t0 + u) * mv + j);
                 e = ext_mul(e, ((b >> j) & 1) ? pj : ext_sub(one, pj));
             }
             acc = ext_add(acc, e);
         }
         zk_syncthreads();
     }
-    if (b < n) w_st(w, b, assign ? acc : ext_add(w_ld(w, b), acc));
+    if (b < n) sc_st(w, b, assign ? acc : ext_add(sc_ld(w, b), acc));
 }
 
 // partial sums of sum_i col_c[i] w[i] for every column (slot c * 4 + q of the partials)
 __global__ __launch_bounds__(256) void k_whir_dot(WhirCols src, unsigned n_cols, const uint32_t* __restrict__ w, size_t n,
                                                   uint32_t* __restrict__ partial) {
-    __shared__ uint32_t red[4][4];
     for (unsigned c = 0; c < n_cols; c++) {
-        Ext acc = ext_zero();
+        Ext acc[1] = {ext_zero()};
         for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-            acc = ext_add(acc, ext_mul_base(w_ld(w, i), src.p[c][i * src.es[c]]));
-        w_block_sum4(acc, partial + (size_t)c * 4 * WHIR_NB, blockIdx.x, red);
+            acc[0] = ext_add(acc[0], ext_mul_base(sc_ld(w, i), src.p[c][i * src.es[c]]));
+        sc_block_sum(acc, partial + (size_t)c * 4 * SC_NB + blockIdx.x);
+        zk_syncthreads();
     }
 }
 
@@ -193,7 +162,7 @@ __global__ __launch_bounds__(256) void k_whir_reduce(const uint32_t* __restrict_
                                                      uint32_t* __restrict__ out) {
     for (unsigned j = threadIdx.x; j < 4 * nvals; j += 256) {
         uint32_t s = 0;
-        for (unsigned b = 0; b < nb; b++) s = madd(s, partial[(size_t)j * WHIR_NB + b]);
+        for (unsigned b = 0; b < nb; b++) s = madd(s, partial[(size_t)j * SC_NB + b]);
         out[j] = from_monty(s);
     }
 }
@@ -201,146 +170,54 @@ __global__ __launch_bounds__(256) void k_whir_reduce(const uint32_t* __restrict_
 // out[i] = sum_c alpha^c col_c[i] (extension)
 __global__ __launch_bounds__(256) void k_whir_combine(WhirCols src, unsigned n_cols, size_t n, const uint32_t* __restrict__ alpha,
                                                       uint32_t* __restrict__ out) {
-    const Ext a = w_ld(alpha, 0);
+    const Ext a = sc_ld(alpha, 0);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         Ext acc = ext_zero(), ap = ext_one();
         for (unsigned c = 0; c < n_cols; c++) {
             acc = ext_add(acc, ext_mul_base(ap, src.p[c][i * src.es[c]]));
             ap = ext_mul(ap, a);
         }
-        w_st(out, i, acc);
+        sc_st(out, i, acc);
     }
 }
 
-// one sum-check round over n_pairs pairs: with r, first fold f, w (4 n_pairs entries) into fo, wo (2 n_pairs); without r the tables
-// are read as they are.  partial (may be null: fold only): s(0) = sum f0 w0, s(2) = sum (2 f1 - f0)(2 w1 - w0), slots 0..7.
-__global__ __launch_bounds__(256) void k_whir_pass(const uint32_t* __restrict__ f, const uint32_t* __restrict__ w, uint32_t* __restrict__ fo,
-                                                   uint32_t* __restrict__ wo, size_t n_pairs, const uint32_t* __restrict__ r_p,
-                                                   uint32_t* __restrict__ partial) {
-    __shared__ uint32_t red[4][4];
-    const Ext r = r_p ? w_ld(r_p, 0) : ext_zero();
-    Ext s0 = ext_zero(), s2 = ext_zero();
-    for (size_t y = (size_t)blockIdx.x * 256 + threadIdx.x; y < n_pairs; y += (size_t)gridDim.x * 256) {
-        Ext f0, f1, w0, w1;
-        if (r_p) {
-            f0 = w_fold(w_ld(f, 4 * y), w_ld(f, 4 * y + 1), r), f1 = w_fold(w_ld(f, 4 * y + 2), w_ld(f, 4 * y + 3), r);
-            w0 = w_fold(w_ld(w, 4 * y), w_ld(w, 4 * y + 1), r), w1 = w_fold(w_ld(w, 4 * y + 2), w_ld(w, 4 * y + 3), r);
-            w_st(fo, 2 * y, f0), w_st(fo, 2 * y + 1, f1), w_st(wo, 2 * y, w0), w_st(wo, 2 * y + 1, w1);
-        } else {
-            f0 = w_ld(f, 2 * y), f1 = w_ld(f, 2 * y + 1), w0 = w_ld(w, 2 * y), w1 = w_ld(w, 2 * y + 1);
-        }
-        if (partial) {
-            s0 = ext_add(s0, ext_mul(f0, w0));
-            s2 = ext_add(s2, ext_mul(ext_sub(ext_add(f1, f1), f0), ext_sub(ext_add(w1, w1), w0)));
-        }
-    }
-    if (!partial) return;   // uniform across the workgroup
-    w_block_sum4(s0, partial, blockIdx.x, red);
-    w_block_sum4(s2, partial + 4 * WHIR_NB, blockIdx.x, red);
-}
+// a round of the opening's sum-check: s(x) = sum_y f w at 0, 2 over the tables f, w
+struct WhirRound {
+    static constexpr unsigned T = 2, E = 2;
+    __device__ __forceinline__ void load() {}
+    __device__ __forceinline__ Ext operator()(const Ext* v) const { return ext_mul(v[0], v[1]); }
+};
+using WhirPass = ScPass<ScTables<2>, WhirRound>;
 
-// the partials of a pass -> s(0), s(2): written into the proof (canonical), observed, and the round challenge sampled (Montgomery)
-__global__ __launch_bounds__(64) void k_whir_round_tr(DevTranscript* tr, const uint32_t* __restrict__ partial, unsigned nb,
-                                                      uint32_t* __restrict__ proof_out, uint32_t* __restrict__ r_out) {
-    const unsigned lane = threadIdx.x;
-    const CoopConsts cc = coop_load_consts(lane & 15u);
-    uint32_t s[8] = {};
-    for (unsigned b = lane; b < nb; b += 64)
-#pragma unroll
-        for (int k = 0; k < 8; k++) s[k] = madd(s[k], partial[(size_t)k * WHIR_NB + b]);
-#pragma unroll
-    for (int k = 0; k < 8; k++) s[k] = w_wave_sum(s[k]);
-    TrRegs R = tr_load(tr, lane);
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        if (lane == 0) proof_out[k] = from_monty(s[k]);
-        tr_observe1(R, lane, s[k], cc);
-    }
-    for (int q = 0; q < 4; q++) {
-        const uint32_t v = tr_sample1(R, lane, cc);
-        if (lane == 0) r_out[q] = v;
-    }
-    tr_store(tr, R, lane);
-}
-
-// The rest of a round's sum-check in ONE workgroup, tables of n <= 2^WHIR_LT entries (after folding with r_prev, if given) in LDS:
+// The rest of a round's sum-check in ONE workgroup, tables of n <= SC_T entries (after folding with r_prev, if given) in LDS:
 // `rounds` rounds, each a reduction, the transcript step on wave 0 and a fold.  fo / wo (may be null): the folded tables at the end.
-__global__ __launch_bounds__(WHIR_SW) void k_whir_small(DevTranscript* tr, const uint32_t* __restrict__ f, const uint32_t* __restrict__ w,
-                                                        const uint32_t* __restrict__ r_prev, unsigned n, unsigned rounds,
-                                                        uint32_t* __restrict__ proof_out, uint32_t* __restrict__ r_out,
-                                                        uint32_t* __restrict__ fo, uint32_t* __restrict__ wo) {
-    __shared__ uint4 sf[1u << WHIR_LT], sw[1u << WHIR_LT];
-    __shared__ uint32_t red[WHIR_SW / 64][8];
-    __shared__ uint4 rsh;
+__global__ __launch_bounds__(SC_SW) void k_whir_small(DevTranscript* tr, const uint32_t* __restrict__ f, const uint32_t* __restrict__ w,
+                                                       const uint32_t* __restrict__ r_prev, unsigned n, unsigned rounds,
+                                                       uint32_t* __restrict__ proof_out, uint32_t* __restrict__ r_out,
+                                                       uint32_t* __restrict__ fo, uint32_t* __restrict__ wo) {
+    __shared__ uint4 X4[2 * SC_T];   // f, then w
+    __shared__ uint32_t s_r[4];
+    uint32_t* X = reinterpret_cast<uint32_t*>(X4);
     const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     {
-        const Ext r = r_prev ? w_ld(r_prev, 0) : ext_zero();
-        for (unsigned i = tid; i < n; i += WHIR_SW) {
-            Ext a, b;
-            if (r_prev) a = w_fold(w_ld(f, 2 * i), w_ld(f, 2 * i + 1), r), b = w_fold(w_ld(w, 2 * i), w_ld(w, 2 * i + 1), r);
-            else a = w_ld(f, i), b = w_ld(w, i);
-            sf[i] = make_uint4(a.c[0], a.c[1], a.c[2], a.c[3]);
-            sw[i] = make_uint4(b.c[0], b.c[1], b.c[2], b.c[3]);
+        const Ext r = r_prev ? sc_ld(r_prev, 0) : ext_zero();
+        for (unsigned i = tid; i < n; i += SC_SW) {
+            if (r_prev) {
+                sc_st(X, i, sc_fold(sc_ld(f, 2 * i), sc_ld(f, 2 * i + 1), r));
+                sc_st(X, SC_T + i, sc_fold(sc_ld(w, 2 * i), sc_ld(w, 2 * i + 1), r));
+            } else {
+                sc_st(X, i, sc_ld(f, i)), sc_st(X, SC_T + i, sc_ld(w, i));
+            }
         }
     }
     CoopConsts cc;
     TrRegs R{};
     if (wave == 0) cc = coop_load_consts(lane & 15u), R = tr_load(tr, lane);
     zk_syncthreads();
-    for (unsigned t = 0; t < rounds; t++, n >>= 1) {
-        const unsigned np = n >> 1;
-        Ext s0 = ext_zero(), s2 = ext_zero();
-        if (tid < np) {
-            const uint4 a0 = sf[2 * tid], a1 = sf[2 * tid + 1], b0 = sw[2 * tid], b1 = sw[2 * tid + 1];
-            const Ext f0{{a0.x, a0.y, a0.z, a0.w}}, f1{{a1.x, a1.y, a1.z, a1.w}}, w0{{b0.x, b0.y, b0.z, b0.w}}, w1{{b1.x, b1.y, b1.z, b1.w}};
-            s0 = ext_mul(f0, w0);
-            s2 = ext_mul(ext_sub(ext_add(f1, f1), f0), ext_sub(ext_add(w1, w1), w0));
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t x0 = w_wave_sum(s0.c[q]), x2 = w_wave_sum(s2.c[q]);
-            if (lane == 0) red[wave][q] = x0, red[wave][4 + q] = x2;
-        }
-        zk_syncthreads();
-        if (wave == 0) {
-            uint32_t s[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                uint32_t x = 0;
-                for (unsigned v = 0; v < WHIR_SW / 64; v++) x = madd(x, red[v][q]);
-                s[q] = x;
-            }
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                if (lane == 0) proof_out[8 * t + q] = from_monty(s[q]);
-                tr_observe1(R, lane, s[q], cc);
-            }
-            uint32_t rv[4];
-            for (int q = 0; q < 4; q++) rv[q] = tr_sample1(R, lane, cc);
-            if (lane == 0) {
-                for (int q = 0; q < 4; q++) r_out[4 * t + q] = rv[q];
-                rsh = make_uint4(rv[0], rv[1], rv[2], rv[3]);
-            }
-        }
-        zk_syncthreads();
-        const Ext r{{rsh.x, rsh.y, rsh.z, rsh.w}};
-        uint4 nf, nw;
-        if (tid < np) {
-            const uint4 a0 = sf[2 * tid], a1 = sf[2 * tid + 1], b0 = sw[2 * tid], b1 = sw[2 * tid + 1];
-            const Ext x = w_fold(Ext{{a0.x, a0.y, a0.z, a0.w}}, Ext{{a1.x, a1.y, a1.z, a1.w}}, r);
-            const Ext y = w_fold(Ext{{b0.x, b0.y, b0.z, b0.w}}, Ext{{b1.x, b1.y, b1.z, b1.w}}, r);
-            nf = make_uint4(x.c[0], x.c[1], x.c[2], x.c[3]), nw = make_uint4(y.c[0], y.c[1], y.c[2], y.c[3]);
-        }
-        zk_syncthreads();
-        if (tid < np) sf[tid] = nf, sw[tid] = nw;
-        zk_syncthreads();
-    }
+    for (unsigned t = 0; t < rounds; t++, n >>= 1) sc_small_round(WhirRound{}, X, SC_T, n, R, cc, proof_out + 8 * t, r_out + 4 * t, s_r);
     if (wave == 0) tr_store(tr, R, lane);
     if (fo)
-        for (unsigned i = tid; i < n; i += WHIR_SW) {
-            const uint4 a = sf[i], b = sw[i];
-            reinterpret_cast<uint4*>(fo)[i] = a, reinterpret_cast<uint4*>(wo)[i] = b;
-        }
+        for (unsigned i = tid; i < n; i += SC_SW) sc_st(fo, i, sc_ld(X, i)), sc_st(wo, i, sc_ld(X, SC_T + i));
 }
 
 // coefficients folded by 2^k in one pass: out[y] = the k binary folds c_even + r_j c_odd of c[y 2^k ..]; cols (may be null): also
@@ -350,12 +227,12 @@ __global__ __launch_bounds__(256) void k_whir_cfold(const uint32_t* __restrict__
     for (size_t y = (size_t)blockIdx.x * 256 + threadIdx.x; y < n_out; y += (size_t)gridDim.x * 256) {
         Ext v[16];
         const unsigned s = 1u << k;
-        for (unsigned t = 0; t < s; t++) v[t] = w_ld(c, (y << k) + t);
+        for (unsigned t = 0; t < s; t++) v[t] = sc_ld(c, (y << k) + t);
         for (unsigned j = 0; j < k; j++) {
-            const Ext r = w_ld(rs, j);
+            const Ext r = sc_ld(rs, j);
             for (unsigned t = 0; t < (s >> (j + 1)); t++) v[t] = ext_add(v[2 * t], ext_mul(r, v[2 * t + 1]));
         }
-        w_st(out, y, v[0]);
+        sc_st(out, y, v[0]);
         if (cols)
             for (int q = 0; q < 4; q++) cols[q * col_stride + y] = v[0].c[q];
     }
@@ -364,28 +241,23 @@ __global__ __launch_bounds__(256) void k_whir_cfold(const uint32_t* __restrict__
 // partial sums of sum_i c_i zeta^i: thread g takes the `per` consecutive coefficients from g * per and raises zeta to g * per itself
 __global__ __launch_bounds__(256) void k_whir_ood(const uint32_t* __restrict__ c, size_t n, size_t per, const uint32_t* __restrict__ zeta_p,
                                                   uint32_t* __restrict__ partial) {
-    __shared__ uint32_t red[4][4];
-    const Ext z = w_ld(zeta_p, 0);
+    const Ext z = sc_ld(zeta_p, 0);
     const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x, i0 = g * per;
-    Ext acc = ext_zero();
+    Ext acc[1] = {ext_zero()};
     if (i0 < n) {
         Ext x = ext_pow(z, i0);
         const size_t i1 = i0 + per < n ? i0 + per : n;
         for (size_t i = i0; i < i1; i++) {
-            acc = ext_add(acc, ext_mul(w_ld(c, i), x));
+            acc[0] = ext_add(acc[0], ext_mul(sc_ld(c, i), x));
             x = ext_mul(x, z);
         }
     }
-    w_block_sum4(acc, partial, blockIdx.x, red);
+    sc_block_sum(acc, partial + blockIdx.x);
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 namespace {
-unsigned grid_of(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>(WHIR_NB, (n + 255) / 256)); }
-Ext canon_ext(const uint32_t* p) { return Ext{{to_monty(p[0]), to_monty(p[1]), to_monty(p[2]), to_monty(p[3])}}; }
-void put_ext(uint32_t* out, const Ext& e) {
-    for (int q = 0; q < 4; q++) out[q] = from_monty(e.c[q]);
-}
+unsigned grid_of(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>(SC_NB, (n + 255) / 256)); }
 std::vector<Ext> pow_point(Ext x, unsigned n) {
     std::vector<Ext> out(n);
     for (unsigned j = 0; j < n; j++) out[j] = x, x = ext_mul(x, x);
@@ -507,7 +379,7 @@ int whir_open_device(zkhip_ctx* ctx, zkhip_whir_commitment* com, DevTranscript* 
     uint32_t *fA = B.get(4 * n), *wA = B.get(4 * n), *fB = B.get(2 * n), *wB = B.get(2 * n), *cA = B.get(4 * n), *cB = B.get(4 * (n >> k));
     uint32_t *ntt = sh.R > 1 ? B.get(4 * ((size_t)1 << ln1)) : nullptr;
     uint32_t *mat[2] = {sh.R > 1 ? B.get(4 * ((size_t)1 << ln1)) : nullptr, sh.R > 2 ? B.get(4 * ((size_t)1 << (ln1 - 1))) : nullptr};
-    uint32_t *partial = B.get(4 * (size_t)ZKHIP_WHIR_MAX_COLS * WHIR_NB), *dP = B.get(L.total), *rs = B.get(4 * (size_t)k * sh.R);
+    uint32_t *partial = B.get(4 * (size_t)ZKHIP_WHIR_MAX_COLS * SC_NB), *dP = B.get(L.total), *rs = B.get(4 * (size_t)k * sh.R);
     uint32_t *misc = B.get(64), *idx = B.get(max_q), *pts = B.get(4 * (size_t)(1 + max_q) * m);
     if (!fA || !wA || !fB || !wB || !cA || !cB || (sh.R > 1 && (!ntt || !mat[0])) || (sh.R > 2 && !mat[1]) || !partial || !dP || !rs ||
         !misc || !idx || !pts)
@@ -555,18 +427,20 @@ int whir_open_device(zkhip_ctx* ctx, zkhip_whir_commitment* com, DevTranscript* 
         // the k sum-check rounds
         size_t sz = (size_t)1 << mi;   // entries after the pending fold
         const uint32_t* pending = nullptr;
+        auto pass = [&](uint32_t* fo, uint32_t* wo, uint32_t* part) {   // sz / 2 pairs
+            WhirPass p{};
+            p.src.tab[0] = f, p.src.tab[1] = w, p.dst[0] = fo, p.dst[1] = wo, p.r = pending, p.n_pairs = sz / 2, p.partial = part;
+            KernelScope ks(ctx, "whir_pass");
+            hipLaunchKernelGGL(k_sc_pass, dim3(grid_of(sz / 2)), dim3(256), 0, st, p);
+        };
         unsigned t = 0;
-        for (; t < k && sz > (1u << WHIR_LT); t++, sz >>= 1) {
+        for (; t < k && sz > SC_T; t++, sz >>= 1) {
             uint32_t *fo = f == fA ? fB : fA, *wo = w == wA ? wB : wA;
-            const size_t np = sz / 2;
-            const unsigned nb = grid_of(np);
-            {
-                KernelScope ks(ctx, "whir_pass");
-                hipLaunchKernelGGL(k_whir_pass, dim3(nb), dim3(256), 0, st, (const uint32_t*)f, (const uint32_t*)w, fo, wo, np, pending, partial);
-            }
+            pass(fo, wo, partial);
             {
                 KernelScope ks(ctx, "whir_round_tr");
-                hipLaunchKernelGGL(k_whir_round_tr, dim3(1), dim3(64), 0, st, d_t, (const uint32_t*)partial, nb, dP + L.sc[i] + 8 * t, r_i + 4 * t);
+                hipLaunchKernelGGL(k_sc_round_tr<8>, dim3(1), dim3(64), 0, st, d_t, (const uint32_t*)partial, grid_of(sz / 2), dP + L.sc[i] + 8 * t,
+                                   r_i + 4 * t);
             }
             ZK_HIP_CHECK(ctx, hipGetLastError());
             if (pending) f = fo, w = wo;
@@ -575,15 +449,13 @@ int whir_open_device(zkhip_ctx* ctx, zkhip_whir_commitment* com, DevTranscript* 
         if (t < k) {   // the rest in one workgroup
             uint32_t *fo = last ? nullptr : (f == fA ? fB : fA), *wo = last ? nullptr : (w == wA ? wB : wA);
             KernelScope ks(ctx, "whir_small");
-            hipLaunchKernelGGL(k_whir_small, dim3(1), dim3(WHIR_SW), 0, st, d_t, (const uint32_t*)f, (const uint32_t*)w, pending, (unsigned)sz,
+            hipLaunchKernelGGL(k_whir_small, dim3(1), dim3(SC_SW), 0, st, d_t, (const uint32_t*)f, (const uint32_t*)w, pending, (unsigned)sz,
                                k - t, dP + L.sc[i] + 8 * t, r_i + 4 * t, fo, wo);
             ZK_HIP_CHECK(ctx, hipGetLastError());
             if (!last) f = fo, w = wo;
         } else if (!last) {   // fold with the last challenge
             uint32_t *fo = f == fA ? fB : fA, *wo = w == wA ? wB : wA;
-            KernelScope ks(ctx, "whir_pass");
-            hipLaunchKernelGGL(k_whir_pass, dim3(grid_of(sz / 2)), dim3(256), 0, st, (const uint32_t*)f, (const uint32_t*)w, fo, wo, sz / 2,
-                               pending, (uint32_t*)nullptr);
+            pass(fo, wo, nullptr);
             ZK_HIP_CHECK(ctx, hipGetLastError());
             f = fo, w = wo;
         }
@@ -615,7 +487,7 @@ int whir_open_device(zkhip_ctx* ctx, zkhip_whir_commitment* com, DevTranscript* 
             ZK_TRY(convert_repr(ctx, dP + L.mid[i], 8, false));
             ZK_TRY(transcript_observe(ctx, d_t, dP + L.mid[i], 8, true));
             ZK_TRY(transcript_sample(ctx, d_t, zeta, nullptr, 4));
-            const size_t per = (nn + 256 * WHIR_NB - 1) / (256 * WHIR_NB);   // coefficients per thread
+            const size_t per = (nn + 256 * SC_NB - 1) / (256 * SC_NB);   // coefficients per thread
             const unsigned nb = (unsigned)(((nn + per - 1) / per + 255) / 256);
             {
                 KernelScope ks(ctx, "whir_ood");
@@ -672,21 +544,6 @@ int whir_open_device(zkhip_ctx* ctx, zkhip_whir_commitment* com, DevTranscript* 
 
 // ---- the host verifier ------------------------------------------------------------------------------------------------------
 namespace {
-Ext wconst(uint32_t c) { return ext_from_base(to_monty(c)); }
-// the quadratic through (0, s0), (1, s1), (2, s2), at r
-Ext quad(const Ext& s0, const Ext& s1, const Ext& s2, const Ext& r) {
-    const Ext inv2 = wconst(1006632961u), r1 = ext_sub(r, wconst(1)), r2 = ext_sub(r, wconst(2));
-    const Ext l0 = ext_mul(ext_mul(r1, r2), inv2), l1 = ext_neg(ext_mul(r, r2)), l2 = ext_mul(ext_mul(r, r1), inv2);
-    return ext_add(ext_add(ext_mul(l0, s0), ext_mul(l1, s1)), ext_mul(l2, s2));
-}
-Ext eq_eval(const Ext* p, const Ext* x, size_t n) {
-    Ext acc = ext_one();
-    for (size_t j = 0; j < n; j++) {
-        const Ext px = ext_mul(p[j], x[j]);   // p x + (1 - p)(1 - x) = 1 - p - x + 2 p x
-        acc = ext_mul(acc, ext_add(ext_sub(ext_sub(ext_one(), p[j]), x[j]), ext_add(px, px)));
-    }
-    return acc;
-}
 Ext coeff_eval(const std::vector<Ext>& c, const Ext* pt, unsigned n) {   // f~(pt) from 2^n monomial coefficients
     std::vector<Ext> t(c);
     for (unsigned j = 0; j < n; j++) {   // bind the lowest variable: c_even + x c_odd
@@ -694,16 +551,6 @@ Ext coeff_eval(const std::vector<Ext>& c, const Ext* pt, unsigned n) {   // f~(p
         t.resize(t.size() / 2);
     }
     return t[0];
-}
-// position `index` of a bit-reversed layer of 2^(log_height+1) values folded to 2^log_height (the fri_fold formula)
-Ext fold_pair(const Ext& e0, const Ext& e1, const Ext& beta, uint64_t index, unsigned log_height) {
-    const uint32_t x = mpow((two_adic_generator(log_height + 1)), bitrev32((uint32_t)index, log_height));
-    const uint32_t c = minv(mneg(madd(x, x)));
-    Ext d = ext_sub(e1, e0);
-    for (int q = 0; q < 4; q++) d.c[q] = mmul(d.c[q], c);
-    Ext bx = beta;
-    bx.c[0] = msub(bx.c[0], x);
-    return ext_add(e0, ext_mul(bx, d));
 }
 struct Cons {
     Ext coef;
@@ -729,10 +576,10 @@ int whir_verify_host(HostChallenger& ch, const zkhip_whir_params* prm, const uin
     const Ext alpha = ch.sample_ext();
     std::vector<Ext> apow(n_cols);
     Ext sigma = ext_zero(), a = ext_one();
-    for (size_t c = 0; c < n_cols; c++) apow[c] = a, sigma = ext_add(sigma, ext_mul(a, canon_ext(proof + 4 * c))), a = ext_mul(a, alpha);
+    for (size_t c = 0; c < n_cols; c++) apow[c] = a, sigma = ext_add(sigma, ext_mul(a, ext_from_canon(proof + 4 * c))), a = ext_mul(a, alpha);
     std::vector<Cons> cons;
     cons.push_back(Cons{ext_one(), std::vector<Ext>(m), 0});
-    for (unsigned j = 0; j < m; j++) cons[0].pt[j] = canon_ext(point + 4 * j);
+    for (unsigned j = 0; j < m; j++) cons[0].pt[j] = ext_from_canon(point + 4 * j);
     std::vector<Ext> rs_all;
     std::vector<Ext> final_c;
     uint32_t cur_root[8];
@@ -744,21 +591,22 @@ int whir_verify_host(HostChallenger& ch, const zkhip_whir_params* prm, const uin
         std::vector<Ext> rs(k);
         for (unsigned t = 0; t < k; t++) {
             const uint32_t* sw = proof + L.sc[i] + 8 * t;
-            const Ext s0 = canon_ext(sw), s2 = canon_ext(sw + 4);
+            const Ext s0 = ext_from_canon(sw), s2 = ext_from_canon(sw + 4);
             ch.observe_canon(sw, 8);
             rs[t] = ch.sample_ext();
-            sigma = quad(s0, ext_sub(sigma, s0), s2, rs[t]);
+            const Ext sv[3] = {s0, ext_sub(sigma, s0), s2};
+            sigma = poly_at(sv, 2, rs[t]);
         }
         rs_all.insert(rs_all.end(), rs.begin(), rs.end());
         Ext zeta{}, ood{};
         if (!last) {
             ch.observe_canon(proof + L.mid[i], 8);
             zeta = ch.sample_ext();
-            ood = canon_ext(proof + L.mid[i] + 8);
+            ood = ext_from_canon(proof + L.mid[i] + 8);
             ch.observe_canon(proof + L.mid[i] + 8, 4);
         } else {
             final_c.resize((size_t)1 << sh.mf);
-            for (size_t j = 0; j < final_c.size(); j++) final_c[j] = canon_ext(proof + L.mid[i] + 4 * j);
+            for (size_t j = 0; j < final_c.size(); j++) final_c[j] = ext_from_canon(proof + L.mid[i] + 4 * j);
             ch.observe_canon(proof + L.mid[i], (size_t)4 << sh.mf);
         }
         if (!ch.check_witness(prm->pow_bits[i], proof[L.pow[i]])) return ZKHIP_ERR_VERIFY;
@@ -779,12 +627,12 @@ int whir_verify_host(HostChallenger& ch, const zkhip_whir_params* prm, const uin
                     for (size_t c = 0; c < n_cols; c++) e = ext_add(e, ext_mul_base(apow[c], to_monty(op[c * s + t])));
                     v[t] = e;
                 } else {
-                    v[t] = canon_ext(op + 4 * t);
+                    v[t] = ext_from_canon(op + 4 * t);
                 }
             }
             for (unsigned j = 0; j < k; j++) {
                 const uint64_t base = id << (k - j - 1);
-                for (unsigned u = 0; u < (s >> (j + 1)); u++) v[u] = fold_pair(v[2 * u], v[2 * u + 1], rs[j], base + u, ln - j - 1);
+                for (unsigned u = 0; u < (s >> (j + 1)); u++) v[u] = fold_row(base + u, ln - j - 1, rs[j], v[2 * u], v[2 * u + 1]);
             }
             folded[q] = v[0];
             ys[q] = ext_from_base(mpow(g, bitrev32((uint32_t)id, lh)));
@@ -825,7 +673,7 @@ Ext coords_to_ext(const uint32_t* v4) {   // sum_c X^c v_c, v_c = 4 canonical wo
     for (int c = 0; c < 4; c++) {
         Ext xc = ext_zero();
         xc.c[c] = to_monty(1);
-        acc = ext_add(acc, ext_mul(xc, canon_ext(v4 + 4 * c)));
+        acc = ext_add(acc, ext_mul(xc, ext_from_canon(v4 + 4 * c)));
     }
     return acc;
 }
@@ -933,11 +781,11 @@ int zkhip_gkr_committed_verify(const zkhip_whir_params* params, const uint32_t* 
     const size_t nc = ext ? 8 : 5;
     std::vector<uint32_t> vals(4 * nc);
     ZK_TRY(whir_verify_host(ch, params, proof, log_n, nc, point.data(), proof + 8 + gw, words - 8 - gw, vals.data()));
-    const Ext num_v = ext ? coords_to_ext(vals.data()) : canon_ext(vals.data());
+    const Ext num_v = ext ? coords_to_ext(vals.data()) : ext_from_canon(vals.data());
     const Ext den_v = coords_to_ext(vals.data() + 4 * (nc - 4));
-    if (!ext_eq(num_v, canon_ext(claims)) || !ext_eq(den_v, canon_ext(claims + 4))) return ZKHIP_ERR_VERIFY;
+    if (!ext_eq(num_v, ext_from_canon(claims)) || !ext_eq(den_v, ext_from_canon(claims + 4))) return ZKHIP_ERR_VERIFY;
     if (root_out) memcpy(root_out, proof, 32);
-    if (pq_out) put_ext(pq_out, root_pq[0]), put_ext(pq_out + 4, root_pq[1]);
+    if (pq_out) ext_to_canon(pq_out, root_pq[0]), ext_to_canon(pq_out + 4, root_pq[1]);
     return ZKHIP_OK;
 }
 
