@@ -593,6 +593,38 @@ int zkhip_gkr_committed_prove(zkhip_ctx *ctx, zkhip_transcript *transcript, cons
 int zkhip_gkr_committed_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const uint32_t *proof,
                                size_t words, unsigned log_n, int num_is_ext, uint32_t *root_out, uint32_t *pq_out);
 
+/* ---- the stacked WHIR commitment (docs/stacking.md): n_cols base-field columns of mixed heights 2^log_heights[j] (0 <= log_heights[j])
+ *      are sorted stably by non-increasing height, laid end to end and cut into n_stack stacked columns of height 2^log_stack, the
+ *      tail zero; the stacked columns are ONE WHIR commitment at m = log_stack.  An opening sends every column's value at a point of
+ *      its own dimension, reduces all of them to the stacked columns at one point r by a sum-check of log_stack rounds, and opens
+ *      the WHIR commitment at r.  Shapes refused: n_stack > ZKHIP_WHIR_MAX_COLS, log_stack outside [fold_log, ZKHIP_WHIR_MAX_LOG_N],
+ *      n_cols outside [1, ZKHIP_STACK_MAX_COLS]; openings with more than ZKHIP_STACK_MAX_POINTS points. ---- */
+#define ZKHIP_STACK_MAX_COLS 1024
+#define ZKHIP_STACK_MAX_POINTS 64
+typedef struct zkhip_stack_commitment zkhip_stack_commitment;
+/* n_stack = ceil(sum_j 2^log_heights[j] / 2^log_stack), or 0 if the shape does not fit the limits above */
+size_t zkhip_stack_width(const zkhip_whir_params *params, const unsigned *log_heights, size_t n_cols, unsigned log_stack);
+/* words of an opening proof: 4 n_cols + 8 log_stack + zkhip_whir_proof_words(params, log_stack, n_stack); 0 if the shape does not fit */
+size_t zkhip_stack_proof_words(const zkhip_whir_params *params, const unsigned *log_heights, size_t n_cols, unsigned log_stack);
+/* d_cols: HOST array of n_cols device pointers, column j = 2^log_heights[j] Montgomery words.  The commitment owns a gathered copy:
+ * the columns need not outlive the call.  root_out: HOST, 8 canonical words (synchronises). */
+int zkhip_stack_commit(zkhip_ctx *ctx, const zkhip_whir_params *params, const uint32_t *const *d_cols, const unsigned *log_heights,
+                       size_t n_cols, unsigned log_stack, zkhip_stack_commitment **out, uint32_t *root_out);
+/* opens every column j at point col_point[j], continuing `transcript` -- which must already hold the root.  points (HOST, canonical):
+ * the n_points points end to end, point p = point_dims[p] extension elements (lowest variable first); point_dims[col_point[j]] must
+ * equal log_heights[j].  values_out (HOST, 4 n_cols words, caller order) = the columns' multilinear extensions at their points;
+ * proof_out (HOST, cap >= zkhip_stack_proof_words) canonical: [values | sum-check (8 log_stack) | WHIR opening at r].  One host
+ * synchronisation (r) before the WHIR opening.  The commitment can be opened more than once. */
+int zkhip_stack_open(zkhip_ctx *ctx, zkhip_stack_commitment *scom, zkhip_transcript *transcript, const uint32_t *points,
+                     const unsigned *point_dims, size_t n_points, const unsigned *col_point, uint32_t *values_out, uint32_t *proof_out,
+                     size_t cap);
+void zkhip_stack_commitment_destroy(zkhip_ctx *ctx, zkhip_stack_commitment *scom);
+/* host verifier: a fresh challenger observes `prefix`, then replays the opening of `root` with the claimed `values` (4 n_cols words,
+ * which must equal the proof's).  ZKHIP_OK / ZKHIP_ERR_VERIFY (ZKHIP_ERR_INVALID for a malformed call).  Needs no device. */
+int zkhip_stack_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const uint32_t *root,
+                       const unsigned *log_heights, size_t n_cols, unsigned log_stack, const uint32_t *points, const unsigned *point_dims,
+                       size_t n_points, const unsigned *col_point, const uint32_t *values, const uint32_t *proof, size_t words);
+
 /* Field offsets of a proof, in 32-bit words from its start (the layout is static for given parameters and AIR shapes:
  * DESIGN.md section 4).  The counterpart of `Proof::<SC>::decode_from_bytes` (crates/verifier/src/verifier.rs:62) for this
  * backend's proofs: commitments, opened values, FRI layers and query openings are read in place.  Needs no device. */

@@ -28,6 +28,8 @@ pub const ZKHIP_WHIR_MAX_ROUNDS: usize = 32;
 pub const ZKHIP_WHIR_MAX_COLS: usize = 64;
 pub const ZKHIP_WHIR_MAX_LOG_N: c_uint = 26;
 pub const ZKHIP_WHIR_MAX_QUERIES: u32 = 256;
+pub const ZKHIP_STACK_MAX_COLS: usize = 1024;
+pub const ZKHIP_STACK_MAX_POINTS: usize = 64;
 pub const ZKHIP_SHA256_WIDTH: usize = 433;
 pub const ZKHIP_SHA256_PREP_WIDTH: usize = 6;
 pub const ZKHIP_SHA256_ROWS_PER_BLOCK: usize = 65;
@@ -78,6 +80,10 @@ pub struct zkhip_pk {
 }
 #[repr(C)]
 pub struct zkhip_whir_commitment {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct zkhip_stack_commitment {
     _private: [u8; 0],
 }
 
@@ -409,6 +415,19 @@ extern "C" {
                                      cap: usize) -> c_int;
     pub fn zkhip_gkr_committed_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, proof: *const u32,
                                       words: usize, log_n: c_uint, num_is_ext: c_int, root_out: *mut u32, pq_out: *mut u32) -> c_int;
+
+    // the stacked WHIR commitment (docs/stacking.md)
+    pub fn zkhip_stack_width(params: *const zkhip_whir_params, log_heights: *const c_uint, n_cols: usize, log_stack: c_uint) -> usize;
+    pub fn zkhip_stack_proof_words(params: *const zkhip_whir_params, log_heights: *const c_uint, n_cols: usize, log_stack: c_uint) -> usize;
+    pub fn zkhip_stack_commit(ctx: *mut zkhip_ctx, params: *const zkhip_whir_params, d_cols: *const *const u32, log_heights: *const c_uint,
+                              n_cols: usize, log_stack: c_uint, out: *mut *mut zkhip_stack_commitment, root_out: *mut u32) -> c_int;
+    pub fn zkhip_stack_open(ctx: *mut zkhip_ctx, scom: *mut zkhip_stack_commitment, transcript: *mut zkhip_transcript, points: *const u32,
+                            point_dims: *const c_uint, n_points: usize, col_point: *const c_uint, values_out: *mut u32, proof_out: *mut u32,
+                            cap: usize) -> c_int;
+    pub fn zkhip_stack_commitment_destroy(ctx: *mut zkhip_ctx, scom: *mut zkhip_stack_commitment);
+    pub fn zkhip_stack_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, root: *const u32,
+                              log_heights: *const c_uint, n_cols: usize, log_stack: c_uint, points: *const u32, point_dims: *const c_uint,
+                              n_points: usize, col_point: *const c_uint, values: *const u32, proof: *const u32, words: usize) -> c_int;
 
     // the reference's stored-proof container (OpenVM-v1 Proof<SC>, bincode)
     pub fn zkhip_proof_decode_v1(bytes: *const u8, len: usize, kind: c_int, out: *mut zkhip_v1_summary) -> c_int;

@@ -114,7 +114,7 @@ def load_library():
     import torch  # noqa: F401
 
     lib = C.CDLL(path)
-    vp, sz, u32p = C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)
+    vp, sz, u32p, uip = C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint)
     sig = {
         "zkhip_version": (C.c_uint32, []),
         "zkhip_ctx_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
@@ -319,6 +319,12 @@ def load_library():
         "zkhip_gkr_committed_proof_words": (sz, [C.POINTER(WhirParams), C.c_uint, C.c_int]),
         "zkhip_gkr_committed_prove": (C.c_int, [vp, vp, C.POINTER(WhirParams), vp, C.c_int, vp, C.c_uint, u32p, sz]),
         "zkhip_gkr_committed_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, u32p, sz, C.c_uint, C.c_int, u32p, u32p]),
+        "zkhip_stack_width": (sz, [C.POINTER(WhirParams), uip, sz, C.c_uint]),
+        "zkhip_stack_proof_words": (sz, [C.POINTER(WhirParams), uip, sz, C.c_uint]),
+        "zkhip_stack_commit": (C.c_int, [vp, C.POINTER(WhirParams), C.POINTER(vp), uip, sz, C.c_uint, C.POINTER(vp), u32p]),
+        "zkhip_stack_open": (C.c_int, [vp, vp, vp, u32p, uip, sz, uip, u32p, u32p, sz]),
+        "zkhip_stack_commitment_destroy": (None, [vp, vp]),
+        "zkhip_stack_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, u32p, uip, sz, C.c_uint, u32p, uip, sz, uip, u32p, u32p, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -998,6 +1004,45 @@ class Context:
         tr.close()
         return proof[:words]
 
+    # ---- the stacked WHIR commitment (docs/stacking.md) ------------------------------------------------------------
+    def stack_commit(self, params, cols, log_stack):
+        """Stacked WHIR commitment of the device tensors `cols` (column j: 2^m_j Montgomery words), laid end to end at height
+        2^log_stack.  The commitment owns a copy: the columns need not be kept.  Returns the StackCommitment; its `root` is 8
+        canonical words."""
+        heights = []
+        for c in cols:
+            m = c.numel().bit_length() - 1
+            assert c.numel() == 1 << m and c.is_contiguous(), "a column holds 2^m words"
+            heights.append(m)
+        lh = np.ascontiguousarray(heights, dtype=np.uint32)
+        ptrs = (C.c_void_p * max(len(cols), 1))(*[c.data_ptr() for c in cols])
+        h = C.c_void_p()
+        root = np.zeros(8, dtype=np.uint32)
+        self._check(self.lib.zkhip_stack_commit(self.h, C.byref(params), ptrs, _uip(lh), len(cols), log_stack, C.byref(h), _u32p(root)))
+        return StackCommitment(self, h, params, heights, log_stack, root)
+
+    def stack_open(self, scom, points, col_point, prefix=None, transcript=None):
+        """Opening of `scom`: column j at point col_point[j] (points: a list of (d_p x 4) canonical arrays, d_p = the column's log
+        height).  Without `transcript`, a fresh one observes `prefix` (default: the root) first.  Returns (values (n_cols x 4), proof
+        words), canonical numpy uint32."""
+        own = transcript is None
+        tr = Transcript(self) if own else transcript
+        if own:
+            pre = np.ascontiguousarray(scom.root if prefix is None else prefix, dtype=np.uint32)
+            if pre.size:
+                tr.observe(pre)
+        pts, dims, cp = _stack_points(points, col_point)
+        n_cols = len(scom.heights)
+        words = stack_proof_words(scom.params, scom.heights, scom.log_stack)
+        proof = np.zeros(max(words, 1), dtype=np.uint32)
+        values = np.zeros(4 * n_cols, dtype=np.uint32)
+        rc = self.lib.zkhip_stack_open(self.h, scom.h, tr.h, _u32p(pts), _uip(dims), dims.size, _uip(cp), _u32p(values), _u32p(proof),
+                                       proof.size)
+        if own:
+            tr.close()
+        self._check(rc)
+        return values.reshape(n_cols, 4), proof[:words]
+
     # ---- profiling -----------------------------------------------------------------------------
     def profile_enable(self, on=True):
         self._check(self.lib.zkhip_profile_enable(self.h, int(on)))
@@ -1261,6 +1306,66 @@ class WhirCommitment:
             self.close()
         except Exception:
             pass
+
+
+class StackCommitment:
+    """A stacked WHIR commitment on the device (zkhip_stack_commitment); owns its gathered copy of the columns."""
+
+    def __init__(self, ctx, h, params, heights, log_stack, root):
+        self.ctx, self.h, self.params, self.heights, self.log_stack, self.root = ctx, h, params, list(heights), log_stack, root
+        self.n_stack = stack_width(params, heights, log_stack)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.zkhip_stack_commitment_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _uip(arr):
+    return arr.ctypes.data_as(C.POINTER(C.c_uint))
+
+
+def _stack_points(points, col_point):
+    """(all points' words end to end, the dimensions, col_point) as contiguous arrays"""
+    flat = [np.ascontiguousarray(p, dtype=np.uint32).reshape(-1) for p in points]
+    pts = np.concatenate(flat + [np.zeros(0, dtype=np.uint32)])
+    dims = np.ascontiguousarray([f.size // 4 for f in flat], dtype=np.uint32)
+    cp = np.ascontiguousarray(col_point, dtype=np.uint32)
+    return np.ascontiguousarray(pts if pts.size else np.zeros(1, dtype=np.uint32)), dims, cp
+
+
+def stack_width(params, log_heights, log_stack):
+    """n_stack of the stacked layout, 0 if the shape does not fit the limits"""
+    lh = np.ascontiguousarray(log_heights, dtype=np.uint32)
+    return int(load_library().zkhip_stack_width(C.byref(params), _uip(lh), lh.size, log_stack))
+
+
+def stack_proof_words(params, log_heights, log_stack):
+    lh = np.ascontiguousarray(log_heights, dtype=np.uint32)
+    return int(load_library().zkhip_stack_proof_words(C.byref(params), _uip(lh), lh.size, log_stack))
+
+
+def stack_verify(params, prefix, root, log_heights, log_stack, points, col_point, values, proof):
+    """Host verifier of a stacked opening (needs no GPU): a fresh challenger observes `prefix`, then the opening of `root` with the
+    claimed `values` (n_cols x 4) is replayed; raises ZkhipError."""
+    lib = load_library()
+    pre, pw = _gkr_words(prefix, proof)
+    rt = np.ascontiguousarray(root, dtype=np.uint32).reshape(-1)
+    lh = np.ascontiguousarray(log_heights, dtype=np.uint32)
+    pts, dims, cp = _stack_points(points, col_point)
+    vals = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+    if rt.size != 8 or vals.size != 4 * lh.size or cp.size != lh.size:
+        raise ZkhipError("stack_verify: root, values or col_point of the wrong size")
+    rc = lib.zkhip_stack_verify(C.byref(params), _u32p(pre), pre.size, _u32p(rt), _uip(lh), lh.size, log_stack, _u32p(pts), _uip(dims),
+                                dims.size, _uip(cp), _u32p(vals), _u32p(pw), pw.size)
+    if rc != 0:
+        raise ZkhipError("zkhip_stack_verify refused the proof (%d)" % rc)
 
 
 def whir_proof_words(params, m, n_cols):

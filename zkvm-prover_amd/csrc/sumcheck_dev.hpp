@@ -1,6 +1,7 @@
 // sumcheck_dev.hpp -- the device core of the library's sum-checks: extension loads and stores, the fold, the wave and workgroup
 // sums, the streaming round pass, the one-wave transcript step and the round of the single-workgroup form.  Its users are the
-// LogUp-GKR layers (csrc/logup_gkr.hip), the WHIR opening (csrc/whir.hip) and the stage kernels of csrc/sumcheck.hip.
+// LogUp-GKR layers (csrc/logup_gkr.hip), the WHIR opening (csrc/whir.hip), the stacking reduction (csrc/stacking.hip) and the
+// stage kernels of csrc/sumcheck.hip.
 //
 // A round description G names the round's tables and its summand: G::T tables, the round polynomial s(x) = sum_y G(f_y(x)) evaluated
 // at the E points 0, 2, 3, .., E (s(1) follows from the claim), G(v) the summand on one value of every table, and G::load(), which
@@ -110,6 +111,13 @@ __global__ __launch_bounds__(256) void k_sc_pass(ScPass<Src, G> a) {
     if (!a.partial) return;   // uniform across the grid
     sc_block_sum(acc, a.partial + blockIdx.x);
 }
+
+// the product of two tables (the WHIR opening's and the stacking reduction's sum-check): s(x) = sum_y f w at 0, 2
+struct WhirRound {
+    static constexpr unsigned T = 2, E = 2;
+    __device__ __forceinline__ void load() {}
+    __device__ __forceinline__ Ext operator()(const Ext* v) const { return ext_mul(v[0], v[1]); }
+};
 
 // ---- the transcript step -------------------------------------------------------------------------------------------------------
 // one wave: the round polynomial's NW words (Montgomery) into the proof (canonical) and observed, the round challenge sampled into

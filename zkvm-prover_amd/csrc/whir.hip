@@ -22,11 +22,6 @@ namespace zk {
 
 constexpr unsigned WHIR_ZT = 12;           // a zeta-transform tile holds 2^12 words of LDS
 
-struct WhirCols {   // column c, entry i: p[c][i * es[c]]
-    const uint32_t* p[ZKHIP_WHIR_MAX_COLS];
-    uint32_t es[ZKHIP_WHIR_MAX_COLS];
-};
-
 // ---- shape -----------------------------------------------------------------------------------------------------------------
 struct WhirShape {
     unsigned R = 0, mf = 0;
@@ -181,12 +176,6 @@ __global__ __launch_bounds__(256) void k_whir_combine(WhirCols src, unsigned n_c
     }
 }
 
-// a round of the opening's sum-check: s(x) = sum_y f w at 0, 2 over the tables f, w
-struct WhirRound {
-    static constexpr unsigned T = 2, E = 2;
-    __device__ __forceinline__ void load() {}
-    __device__ __forceinline__ Ext operator()(const Ext* v) const { return ext_mul(v[0], v[1]); }
-};
 using WhirPass = ScPass<ScTables<2>, WhirRound>;
 
 // The rest of a round's sum-check in ONE workgroup, tables of n <= SC_T entries (after folding with r_prev, if given) in LDS:
@@ -256,6 +245,11 @@ __global__ __launch_bounds__(256) void k_whir_ood(const uint32_t* __restrict__ c
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
+void whir_eq_launch(hipStream_t st, uint32_t* w, unsigned mv, const uint32_t* pts) {
+    hipLaunchKernelGGL(k_whir_weight, dim3((unsigned)((((size_t)1 << mv) + 255) / 256)), dim3(256), 0, st, w, mv, pts, 1u,
+                       (const uint32_t*)nullptr, 1);
+}
+
 namespace {
 unsigned grid_of(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>(SC_NB, (n + 255) / 256)); }
 std::vector<Ext> pow_point(Ext x, unsigned n) {

@@ -225,4 +225,22 @@ int gkr_prove_device(zkhip_ctx* ctx, DevTranscript* d_t, const uint32_t* d_num, 
 struct HostChallenger;
 int gkr_verify_host(HostChallenger& ch, const uint32_t* proof, size_t words, unsigned L, uint32_t* point_out, uint32_t* claims_out,
                     Ext root_out[2]);
+
+// whir.hip
+struct WhirCols {   // column c, entry i: p[c][i * es[c]]
+    const uint32_t* p[ZKHIP_WHIR_MAX_COLS];
+    uint32_t es[ZKHIP_WHIR_MAX_COLS];
+};
+// the commitment of n_cols columns of 2^m Montgomery words; the opening reads the columns, so they must outlive the commitment
+int whir_commit_cols(zkhip_ctx* ctx, const zkhip_whir_params* params, const WhirCols& cols, size_t n_cols, unsigned m,
+                     zkhip_whir_commitment** out, uint32_t* root_out);
+void whir_destroy(zkhip_ctx* ctx, zkhip_whir_commitment* com);
+// the opening at `point` (HOST, canonical), continuing d_t; proof_out / values_out HOST, canonical
+int whir_open_device(zkhip_ctx* ctx, zkhip_whir_commitment* com, DevTranscript* d_t, const uint32_t* point, uint32_t* values_out,
+                     uint32_t* proof_out, size_t cap);
+// the host verifier on a challenger the caller primed; values_out (4 n_cols canonical words, may be null) = the opened values
+int whir_verify_host(HostChallenger& ch, const zkhip_whir_params* prm, const uint32_t* root, unsigned m, size_t n_cols, const uint32_t* point,
+                     const uint32_t* proof, size_t words, uint32_t* values_out);
+// w = eq(pts, .) over 2^mv entries (one point of mv extension coordinates, Montgomery) on stream st (k_whir_weight)
+void whir_eq_launch(hipStream_t st, uint32_t* w, unsigned mv, const uint32_t* pts);
 }  // namespace zk
