@@ -87,3 +87,74 @@ for k in (1, 2, 3, 4):
 with open(os.path.join(HERE, "kat_v1.json"), "w") as f:
     json.dump(out, f, separators=(",", ":"))
 print("wrote kat_v1.json", os.path.getsize(os.path.join(HERE, "kat_v1.json")), "bytes")
+
+# ---- boundary-input cases, in a file of their own (kat_v1.json and its random stream stay as they are) -------------------------
+# Cells from the extremes of the canonical range and from the canonical values whose Montgomery words are extreme (x * 2^-32 mod p for
+# the words p-1, (p+-1)/2, 2^32 mod p): constant, alternating, one-hot and drawn vectors.
+brnd = random.Random(0xB0B0DA47)
+RINV = pow(1 << 32, -1, P)
+M1 = (1 << 32) % P
+BSET = sorted(set([0, 1, 2, P - 1, P - 2, (P - 1) // 2, (P + 1) // 2, M1, P - M1, 1 << 27, 1 << 30] +
+                  [w * RINV % P for w in (1, P - 1, (P - 1) // 2, (P + 1) // 2, M1, P - M1, 1 << 27)]))
+
+
+def bvec(kind, n):
+    if kind == "top":
+        return [P - 1] * n
+    if kind == "raw_top":
+        return [(P - 1) * RINV % P] * n
+    if kind == "alt":
+        return [P - 1 if i % 2 == 0 else 0 for i in range(n)]
+    if kind == "raw_alt_half":
+        return [(P - 1) * RINV % P if i < max(1, n // 2) else 0 for i in range(n)]
+    if kind == "delta":
+        return [P - 1 if i == n - 1 else 0 for i in range(n)]
+    return [brnd.choice(BSET) for _ in range(n)]
+
+
+KINDS = ("top", "raw_top", "alt", "raw_alt_half", "delta", "drawn")
+bout = {"p": P, "dft": [], "coset_lde": [], "fri_fold": [], "sumcheck_round": [], "mle_fold": []}
+for log_n in (1, 3, 6):
+    for kind in KINDS:
+        xs = bvec(kind, 1 << log_n)
+        bout["dft"].append({"log_n": log_n, "kind": kind, "in": xs, "fwd": m.dft_naive(xs), "inv": m.dft_naive(xs, inverse=True)})
+for log_n, added, shift in ((2, 1, 31), (5, 1, 31), (4, 2, 7)):
+    for kind in KINDS:
+        xs = bvec(kind, 1 << log_n)
+        nat = m.coset_lde_naive(xs, added, shift)
+        bits = log_n + added
+        bout["coset_lde"].append({"log_n": log_n, "added_bits": added, "shift": shift, "kind": kind, "in": xs, "natural": nat,
+                                  "bitrev": [nat[m.bitrev(r, bits)] for r in range(1 << bits)]})
+bout["poseidon2_perm"] = [[s, m.permute(s)] for s in [[c] * 16 for c in BSET] + [bvec("alt", 16), bvec("delta", 16)] + [bvec("drawn", 16) for _ in range(6)]]
+bel = [[c] * 4 for c in BSET if c] + [[c, 0, 0, 0] for c in BSET if c] + [bvec("drawn", 4) for _ in range(12)]
+bel = [e for e in bel if any(e)]
+bout["ext_inv"] = [[e, m.ext_inv(e)] for e in bel]
+bout["ext_mul"] = [[a, b, m.ext_mul(a, b)] for a, b in [([P - 1] * 4, [P - 1] * 4), (bvec("raw_top", 4), bvec("raw_top", 4))] + [(brnd.choice(bel), brnd.choice(bel)) for _ in range(12)]]
+bch = [[P - 1] * 4, bvec("raw_top", 4), [0] * 4, [1, 0, 0, 0], bvec("drawn", 4)]
+
+
+def btable(kind, n):
+    """n extension entries: drawn coefficients; one constant table (a fold returns it unchanged: one case per stage is enough); tables
+    alternating between an all-(p-1) entry and zero, canonical and raw, so that lo - hi = +-(p-1) in every coefficient of every pair"""
+    if kind == "alt":
+        return [[P - 1] * 4 if i % 2 == 0 else [0] * 4 for i in range(n)]
+    if kind == "raw_alt":
+        return [[0] * 4 if i % 2 == 0 else bvec("raw_top", 4) for i in range(n)]
+    return [bvec(kind, 4) for _ in range(n)]
+
+
+for log_n_out in (0, 2, 4):
+    for kind in ("drawn", "alt", "raw_alt") + (("top",) if log_n_out == 2 else ()):
+        vals = btable(kind, 2 << log_n_out)
+        for beta in (bch[:1] if kind == "top" else bch):
+            bout["fri_fold"].append({"log_n_out": log_n_out, "in": vals, "beta": beta, "out": m.fri_fold(vals, beta)})
+for kind in ("drawn", "alt", "raw_alt", "top"):
+    fv = btable(kind, 16)
+    for r in (bch[:1] if kind == "top" else bch):
+        bout["mle_fold"].append({"in": fv, "r": r, "out": m.mle_fold(fv, r)})
+    for k in ((1,) if kind == "top" else (1, 2, 4)):
+        tabs = [btable(kind, 8) for _ in range(k)]
+        bout["sumcheck_round"].append({"tables": tabs, "out": m.sumcheck_round(tabs)})
+with open(os.path.join(HERE, "kat_boundary_v1.json"), "w") as f:
+    json.dump(bout, f, separators=(",", ":"))
+print("wrote kat_boundary_v1.json", os.path.getsize(os.path.join(HERE, "kat_boundary_v1.json")), "bytes")

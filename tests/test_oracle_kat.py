@@ -151,3 +151,37 @@ def test_proof_digests_are_stable(ora):
     want = json.load(open(os.path.join(here, "proof_digests_v3.json")))
     got = gen.digests(ora)
     assert got == want
+
+
+def test_boundary_vectors(ora):
+    """tests/golden/kat_boundary_v1.json: the same stages at boundary inputs (cells p-1, (p+-1)/2, the canonical values whose Montgomery
+    words are extreme; constant, alternating and one-hot vectors; all four coefficients p-1) -- the oracle against the big-int model."""
+    with open(os.path.join(HERE, "golden", "kat_boundary_v1.json")) as f:
+        kat = json.load(f)
+    l = ora.lib()
+    assert len(kat["dft"]) >= 18 and len(kat["coset_lde"]) >= 18 and len(kat["poseidon2_perm"]) >= 20 and len(kat["ext_inv"]) >= 30
+    for case in kat["dft"]:
+        x = u32(case["in"])[None, :]
+        assert ora.dft_batch(x, case["log_n"]).tolist()[0] == case["fwd"], case["kind"]
+        assert ora.dft_batch(x, case["log_n"], inverse=True).tolist()[0] == case["inv"], case["kind"]
+    for case in kat["coset_lde"]:
+        x = u32(case["in"])[None, :]
+        assert ora.coset_lde_batch(x, case["log_n"], case["added_bits"], case["shift"], bitrev_out=False).tolist()[0] == case["natural"], case["kind"]
+        assert ora.coset_lde_batch(x, case["log_n"], case["added_bits"], case["shift"], bitrev_out=True).tolist()[0] == case["bitrev"], case["kind"]
+    for s, exp in kat["poseidon2_perm"]:
+        assert ora.permute(s).tolist() == exp
+    for a, b, c in kat["ext_mul"]:
+        out = np.zeros(4, np.uint32)
+        l.ora_ext_mul(ora.p32(u32(a)), ora.p32(u32(b)), ora.p32(out))
+        assert out.tolist() == c
+    for a, ai in kat["ext_inv"]:
+        out = np.zeros(4, np.uint32)
+        l.ora_ext_inv(ora.p32(u32(a)), ora.p32(out))
+        assert out.tolist() == ai
+    assert ora.ext_batch_inverse(u32([a for a, _ in kat["ext_inv"]])).reshape(-1, 4).tolist() == [ai for _, ai in kat["ext_inv"]]
+    for case in kat["fri_fold"]:
+        assert ora.fri_fold(u32(case["in"]).reshape(-1), case["log_n_out"], case["beta"]).reshape(-1, 4).tolist() == case["out"]
+    for c in kat["mle_fold"]:
+        assert ora.mle_fold(u32(c["in"]), c["r"]).reshape(-1, 4).tolist() == c["out"]
+    for c in kat["sumcheck_round"]:
+        assert ora.sumcheck_round([u32(t) for t in c["tables"]]).reshape(-1, 4).tolist() == c["out"]

@@ -48,7 +48,8 @@ ZK_HD uint32_t red_2p(uint32_t x) {
     return y < x ? y : x;  // unsigned min(x, x-p): if x < p, x-p wraps to a huge value
 #endif
 }
-// product in [0, 2p) given a*b < 2.417 p^2  (a*b + 2^32 p must fit 64 bits)
+// r == a*b * 2^-32 (mod p) with r < a*b / 2^32 + p, given a*b < 2.417 p^2  (a*b + 2^32 p must fit 64 bits).  That is [0, 2p) while
+// a*b <= 2^32 p (one operand <= p); at the 2.417 p^2 limit r reaches 2.13 p.
 ZK_HD uint32_t mmul_lazy(uint32_t a, uint32_t b) {
     uint64_t t = (uint64_t)a * b;
     uint32_t m = (uint32_t)t * MONTY_NEG_MU;
