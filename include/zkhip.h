@@ -1083,6 +1083,13 @@ typedef struct {
      * beside the large ones instead of one after the other; 0 (the default) = all on the proof's stream; <= 4.  Off while the per-kernel timing of
      * zkhip_profile_enable is on (it times the proof's stream) [ZKHIP_QUOT_STREAMS] */
     uint32_t quot_streams;
+    /* body of the transform passes.  0 (the default): passes of the two-pass 2^22-point transform (2^11 rows x 8 columns, both digits eleven
+     * bits: every pass of the flagship's LDEs) run k_ntt_pass4_ct_sq, whose shape is a compile-time constant and whose HBM reads are all
+     * issued before its first wait; every other pass runs the run-time-shaped k_ntt_pass4_ct.  1: k_ntt_pass4_ct for every shape (the body
+     * of rounds 1 - 6, kept for the A/B and for tests/test_gpu_ntt_pass_forms.py).  2: the radix-2 passes k_ntt_dif_pass and the
+     * bit-reversal scaling of the LDE for EVERY size (the slow reference form of the same test; transforms of several matrices' columns as
+     * one batch keep form 1) [ZKHIP_NTT_PASS_FORM] */
+    uint32_t ntt_pass_form;
 } zkhip_config;
 /* While `on`, the trace generators treat the shared lookup-count tables handed to them (the 8-bit bitwise table, the range-tuple table, the
  * range table) as canonical counts and leave them canonical -- none converts a table from Montgomery form and back around its increments.
@@ -1101,7 +1108,7 @@ void zkhip_config_default(zkhip_config *out);
 unsigned zkhip_host_cpus(void);
 /* a context's configuration (set at zkhip_ctx_create from zkhip_config_default); the witness fields are process-wide:
  * zkhip_set_process_config stores them (and the rest as the default of contexts created later).  zkhip_ctx_set_config applies every
- * field or refuses the call (ZKHIP_ERR_INVALID: jit 0..2, coop_* <= 27, rows_coop_max_log <= 27, ntt_log_lanes 8..10, quot_streams <= 4, jit_min_log_work <= 62, top_max_log <= 8, grind_sweep_shift <= 8,
+ * field or refuses the call (ZKHIP_ERR_INVALID: jit 0..2, coop_* <= 27, rows_coop_max_log <= 27, ntt_log_lanes 8..10, ntt_pass_form <= 2, quot_streams <= 4, jit_min_log_work <= 62, top_max_log <= 8, grind_sweep_shift <= 8,
  * commit_parts <= 8, side_cus < the device's CUs, hash_block a multiple of 64 in 64..768); a changed side_cus re-partitions as zkhip_set_cu_partition does. */
 int zkhip_ctx_get_config(zkhip_ctx *ctx, zkhip_config *out);
 /* 1 in libzkhip_test.so (the A/B bodies behind zkhip_config.tree_store_early are compiled in), 0 in the library that ships */

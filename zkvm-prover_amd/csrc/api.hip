@@ -237,6 +237,7 @@ void zkhip_config_default(zkhip_config* c) {
     c->rows_in_bulk = getenv("ZKHIP_NO_ROWS_IN_BULK") ? 0 : 1;
     c->rows_coop_max_log = num("ZKHIP_ROWS_COOP_MAX_LOG", 15u, 0, 27);
     c->ntt_log_lanes = num("ZKHIP_NTT_LOG_LANES", 10u, 8, 10);
+    c->ntt_pass_form = num("ZKHIP_NTT_PASS_FORM", 0u, 0, 2);   // (0: shape-specialised flagship passes; 1: the run-time-shaped body everywhere; 2: radix-2 reference passes)
     c->quot_streams = num("ZKHIP_QUOT_STREAMS", 0u, 0, 4);   // (measured: + 7 % for ONE lane of the mixed guest, nothing with three lanes: docs/round5_b.md 6)
     // compiled constraint kernels across processes: the variable if set (empty = none), else `jit_cache` beside this library if it exists
     std::string dir;
@@ -300,9 +301,9 @@ int zkhip_ctx_get_config(zkhip_ctx* ctx, zkhip_config* out) {
 int zkhip_ctx_set_config(zkhip_ctx* ctx, const zkhip_config* cfg) {
     if (!ctx || !cfg) return ZKHIP_ERR_INVALID;
     // every field is applied or refused: nothing is silently clamped at its place of use
-    if (cfg->jit < 0 || cfg->jit > 2 || cfg->coop_max_log > 27 || cfg->coop_inj_max_log > 27 || cfg->rows_coop_max_log > 27 || cfg->ntt_log_lanes < 8 || cfg->ntt_log_lanes > 10 || cfg->quot_streams > 4 || cfg->jit_min_log_work > 62 || cfg->top_max_log > 8 || cfg->grind_sweep_shift > 8 ||
+    if (cfg->jit < 0 || cfg->jit > 2 || cfg->coop_max_log > 27 || cfg->coop_inj_max_log > 27 || cfg->rows_coop_max_log > 27 || cfg->ntt_log_lanes < 8 || cfg->ntt_log_lanes > 10 || cfg->ntt_pass_form > 2 || cfg->quot_streams > 4 || cfg->jit_min_log_work > 62 || cfg->top_max_log > 8 || cfg->grind_sweep_shift > 8 ||
         cfg->commit_parts > 8 || cfg->side_cus >= (unsigned)ctx->cu_count || cfg->hash_block < 64 || cfg->hash_block > 768 || cfg->hash_block % 64)
-        return set_error(ctx, ZKHIP_ERR_INVALID, "zkhip_ctx_set_config: field out of range (jit 0..2, coop_* <= 27, rows_coop_max_log <= 27, ntt_log_lanes 8..10, quot_streams <= 4, jit_min_log_work <= 62, top_max_log <= 8, grind_sweep_shift <= 8, commit_parts <= 8, side_cus < CUs, hash_block a multiple of 64 in 64..768)");
+        return set_error(ctx, ZKHIP_ERR_INVALID, "zkhip_ctx_set_config: field out of range (jit 0..2, coop_* <= 27, rows_coop_max_log <= 27, ntt_log_lanes 8..10, ntt_pass_form <= 2, quot_streams <= 4, jit_min_log_work <= 62, top_max_log <= 8, grind_sweep_shift <= 8, commit_parts <= 8, side_cus < CUs, hash_block a multiple of 64 in 64..768)");
 #ifndef ZKHIP_TEST_KERNELS
     if (cfg->tree_store_early)
         return set_error(ctx, ZKHIP_ERR_INVALID, "zkhip_ctx_set_config: tree_store_early names TEST kernels that this library was built without (libzkhip_test.so holds them)");

@@ -548,7 +548,133 @@ __global__ __launch_bounds__(1 << LOG_T) void k_ntt_pass4_ct(Pass4Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// The LDE's middle, fused (round 6).  A coset LDE of 2^(2 LOG_R) points was four passes over HBM: inverse pass 1, inverse pass 2
+// Shape-specialised pass (round 7; zkhip_config.ntt_pass_form = 0): the passes of a TWO-pass transform whose digits both have SH::LOG_R
+// bits -- 2^22 points as [2^11 x 8] tiles, the four passes of the flagship's LDEs.  Same butterflies, same LDS rounds and the same words
+// out as k_ntt_pass4_ct; what changes is what a tile's waves wait for and what they issue around the butterflies:
+//  * k_ntt_pass4_ct reads HBM in up to five dependent steps -- the twiddle table (wait, LDS store, barrier), the sixteen operands (wait),
+//    the input twiddle t behind a divergent branch (wait), its ratio rho behind another (wait) -- and with two workgroups on a CU nothing
+//    hides those round trips.  Here every read of the round is issued before the first wait: table entry, t / rho (or the coset scales),
+//    then the operands; the barrier that publishes the table comes after the scaling products, where only the butterflies need it.
+//    (In this shape the exponents kc * (j + k 2^LOG_RQ) stay below 2^(2 LOG_R - 1): the table's second half, and with it the branch on
+//    e0 < half and the negation, is never reached.)
+//  * the pass's mode (plain / input twiddle / bit-reversed scaled source) is a template parameter, and log_f, log_lo, log_m, the tile
+//    grid, the strides and the twiddle parameters are constants: tile and column bases are scalar shifts, and the write-out's sixteen
+//    column bases cost one scalar addition each instead of two 64-bit scalar products.
+struct ShapeSq11 {
+    static constexpr int LOG_R = 11, LOG_C = 3, LOG_T = 10;
+};
+enum : int { P4_PLAIN = 0, P4_IN_TW = 1, P4_BR_SRC = 2 };
+
+// v[k] <- v[k] t rho^k, canonical.  t, rho in [0, p); v[k] in [0, p).  Every product is a signed Montgomery product of two words in
+// (-p, p): |d| <= p^2 / 2^32 + p / 2 < 0.97 p, so the running power stays in (-p, p) with no conditional step between products; one
+// conditional addition brings each scaled operand back to [0, p), which the additions of the first butterfly stage need.
+// (The powers as a tree -- rho^2, rho^4, rho^8, dependent depth 4 instead of 15, three products more -- were measured and moved nothing:
+// 16.09 against 16.05 ms for the 2^22 x 302 LDE, docs/kernels_2.md round 7.  With eight waves on a SIMD the chain's latency is covered.)
+__device__ __forceinline__ void scale_geometric(uint32_t (&v)[16], uint32_t t, uint32_t rho) {
+    int32_t ts = (int32_t)t;
+    v[0] = canon_signed(smml((int32_t)v[0], ts));
+#pragma unroll
+    for (int k = 1; k < 16; k++) {
+        ts = smml(ts, (int32_t)rho);
+        v[k] = canon_signed(smml((int32_t)v[k], ts));
+    }
+}
+
+// A column base is the same for every lane of the workgroup and points to device memory, whether it is computed from the arguments or
+// read from a table of column pointers (which the compiler must take for a generic address: flat loads with a 64-bit address per lane).
+// Said so here: the base lives in scalar registers and every access is a global one with a 32-bit lane offset.
+typedef __attribute__((address_space(1))) uint32_t* global_words;
+__device__ __forceinline__ global_words uniform_global(const uint32_t* p) {
+    const uint64_t x = (uint64_t)p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)(x >> 32));
+    return (global_words)(((uint64_t)hi << 32) | lo);
+}
+// (a base per access, each held in scalar registers: without this the compiler folds the sixteen bases of a round into one 64-bit
+// vector address and pays two vector additions per access)
+__device__ __forceinline__ global_words uniform_global(global_words p) {
+    const uint64_t x = (uint64_t)p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)(x >> 32));
+    return (global_words)(((uint64_t)hi << 32) | lo);
+}
+
+template <class SH, int MODE>
+__global__ __launch_bounds__(1 << SH::LOG_T, 8) void k_ntt_pass4_ct_sq(Pass4Args a) {
+    constexpr int LOG_R = SH::LOG_R, LOG_C = SH::LOG_C, LOG_T = SH::LOG_T;
+    constexpr int LOG_F = LOG_R, LOG_M = 2 * LOG_R, LOG_RQ = LOG_R - 4;
+    constexpr unsigned NT = 1u << LOG_T, R = 1u << LOG_R, C = 1u << LOG_C, pitch = C + 1u;
+    static_assert(LOG_C == 3 && LOG_RQ + LOG_C == LOG_T && LOG_R >= LOG_T && (R >> 1) % NT == 0 && LOG_F - LOG_C >= 7, "[2^11 x 8] tiles of 1024 lanes");
+    if (a.prio == 3) __builtin_amdgcn_s_setprio(3);
+    else if (a.prio == 2) __builtin_amdgcn_s_setprio(2);
+    else if (a.prio == 1) __builtin_amdgcn_s_setprio(1);
+    extern __shared__ uint32_t sm[];
+    uint32_t* lv = sm;
+    uint32_t* twl = sm + R * pitch;
+    const unsigned tid = threadIdx.x;
+    const unsigned col = blockIdx.y;
+    const unsigned sub = col & ((1u << a.log_sub) - 1u);
+    const size_t mcol = col >> a.log_sub;
+    // XCD-aware tile order of k_ntt_pass4_ct for a grid of 2^(LOG_F - LOG_C) >= 128 tiles: groups of 128, 16 adjacent tiles per XCD
+    unsigned tile = blockIdx.x;
+    tile = (tile & ~127u) | ((tile & 7u) << 4) | ((tile & 127u) >> 3);
+    const unsigned F0 = tile << LOG_C;
+    const unsigned c = tid & (C - 1u), jj = tid >> LOG_C;
+    // (bank-friendly unit order: as k_ntt_pass4_ct)
+    const unsigned j = ((jj & 3u) << 3) | ((jj >> 2) & 7u) | (jj & ~31u);
+    // ---- every HBM read of the first round, before the first wait ----
+    uint32_t twe[(R >> 1) / NT];
+#pragma unroll
+    for (unsigned i = 0; i < (R >> 1) / NT; i++) twe[i] = a.tw[(size_t)(tid + i * NT) << (a.tw_log - LOG_R)];
+    uint32_t t = 0, rho = 0, v[16];
+    if constexpr (MODE == P4_BR_SRC) {
+        // rows j + k 2^LOG_RQ of tile column c sit in ONE 64-byte chunk of the bit-reversed coefficient array (as k_ntt_pass4_ct)
+        const uint32_t sc = a.scale_col[((size_t)sub << LOG_F) + F0 + c], sr = a.scale_row[((size_t)sub << LOG_RQ) + j];
+        rho = a.scale_rho[sub];
+        const uint32_t* run = a.src + mcol * a.src_col_stride + ((size_t)bitrev32(F0 + c, LOG_F) << LOG_R);
+        const uint4* ch = reinterpret_cast<const uint4*>(run + ((size_t)bitrev32(j, LOG_RQ) << 4));
+        const uint4 q0 = ch[0], q1 = ch[1], q2 = ch[2], q3 = ch[3];
+        const uint32_t wv[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[k] = wv[((k & 1) << 3) | ((k & 2) << 1) | ((k & 4) >> 1) | ((k & 8) >> 3)];
+        t = mmul(sc, sr);
+    } else {
+        if constexpr (MODE == P4_IN_TW) {
+            // element (row r, column F) *= w_M^(bitrev(F) r), r = j + k 2^LOG_RQ: exponents kc j + k (kc 2^LOG_RQ) < 2^(LOG_M - 1)
+            const uint32_t kc = bitrev32(F0 + c, LOG_F);
+            const unsigned sh = a.tw_log - LOG_M;
+            t = a.tw[(size_t)(kc * j) << sh];
+            rho = a.tw[(size_t)(kc << LOG_RQ) << sh];
+        }
+        const global_words tile_src = uniform_global((a.src_cols ? a.src_cols[mcol] : a.src + mcol * a.src_col_stride) + ((size_t)sub << LOG_M) + F0);
+        const uint32_t lane_off = (j << LOG_F) + c;
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[k] = uniform_global(tile_src + ((size_t)k << (LOG_RQ + LOG_F)))[lane_off];
+    }
+#pragma unroll
+    for (unsigned i = 0; i < (R >> 1) / NT; i++) twl[tid + i * NT] = twe[i];
+    if constexpr (MODE != P4_PLAIN) scale_geometric(v, t, rho);
+    zk_syncthreads();   // (the twiddle table)
+    {
+        uint32_t w[15];
+        load_unit_twiddles<4, LOG_RQ, 0>(twl, j, w);
+        dif_unit_w<4>(v, w);
+        uint32_t* base = lv + j * pitch + c;
+#pragma unroll
+        for (int k = 0; k < 16; k++) base[(k << LOG_RQ) * pitch] = v[k];
+    }
+    zk_syncthreads();
+    lds_rounds_ct<LOG_R, LOG_C, LOG_RQ, NT>(lv, twl, tid);
+    // ---- write-out: tile column cc is one contiguous run of R words at [F0 + cc][p] ----
+    const global_words dst = uniform_global((a.dst_cols ? a.dst_cols[mcol] : a.dst + mcol * a.dst_col_stride) + ((size_t)sub << LOG_M) + ((size_t)F0 << LOG_R));
+    const uint32_t* lrow = lv + tid * pitch;
+#pragma unroll
+    for (unsigned i = 0; i < (R * C) / NT; i++) {
+        const unsigned cc = (NT * i) >> LOG_R, p0 = (NT * i) & (R - 1u);
+        uniform_global(dst + ((size_t)cc << LOG_R) + p0)[tid] = lrow[p0 * pitch + cc];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The LDE's middle, fused (round 6). A coset LDE of 2^(2 LOG_R) points was four passes over HBM: inverse pass 1, inverse pass 2
 // (coefficients, bit-reversed, written to scratch), then per coset forward pass 1 (which read those coefficients back, once per coset)
 // and forward pass 2 -- 12 N words moved for N read and 2 N written.  The inverse's last pass leaves in its LDS tile, per tile column
 // p1, ALL coefficients whose bit-reversed index begins with p1 -- exactly one column F = bitrev(p1) of the forward transform's first pass
@@ -737,6 +863,9 @@ static int ntt_dif_fourstep(zkhip_ctx* ctx, const uint32_t* src, size_t src_stri
         ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct<8, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
         ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct<7, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
         ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct_sq<ShapeSq11, P4_PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct_sq<ShapeSq11, P4_IN_TW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct_sq<ShapeSq11, P4_BR_SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
         attr_set.mark(ctx->device);
     }
     unsigned a[3];
@@ -790,7 +919,15 @@ static int ntt_dif_fourstep(zkhip_ctx* ctx, const uint32_t* src, size_t src_stri
         else if (log_t == 8 && pa.log_r == 8 && pa.log_c == 4) ZK_NTT_CT(8, 4, 8);
         else if (log_t == 8 && pa.log_r == 7 && pa.log_c == 5) ZK_NTT_CT(7, 5, 8);
 #undef ZK_NTT_CT
-        else if (pa.log_r == 11 && pa.log_c == 3 && !legacy)
+        // the passes of the two-pass 2^22-point transform in their shape-specialised form (zkhip_config.ntt_pass_form = 0): everything
+        // k_ntt_pass4_ct_sq holds as a constant is checked here
+        else if (ctx->cfg.ntt_pass_form == 0 && !legacy && n_pass == 2 && n_x == 1 && log_n == 22 && pa.log_r == 11 && pa.log_f == 11 && pa.log_c == 3 &&
+                 pa.log_lo == 0 && pa.in_x_stride == 0 && pa.out_x_stride == 0 && pa.out_hi_stride == ((size_t)1 << 11) && !(pa.br_src && pa.in_tw) &&
+                 (!pa.in_tw || (pa.log_prev == 11 && pa.log_tt == 22 && pa.tw_a == 1 && pa.tw_bx == 0))) {
+            if (pa.br_src) hipLaunchKernelGGL((k_ntt_pass4_ct_sq<ShapeSq11, P4_BR_SRC>), grid, dim3(1024), lds, ctx->stream, pa);
+            else if (pa.in_tw) hipLaunchKernelGGL((k_ntt_pass4_ct_sq<ShapeSq11, P4_IN_TW>), grid, dim3(1024), lds, ctx->stream, pa);
+            else hipLaunchKernelGGL((k_ntt_pass4_ct_sq<ShapeSq11, P4_PLAIN>), grid, dim3(1024), lds, ctx->stream, pa);
+        } else if (pa.log_r == 11 && pa.log_c == 3 && !legacy)
             hipLaunchKernelGGL((k_ntt_pass4_ct<11, 3>), grid, dim3(threads), lds, ctx->stream, pa);
         else if (pa.log_r == 10 && pa.log_c == 4 && !legacy)
             hipLaunchKernelGGL((k_ntt_pass4_ct<10, 4>), grid, dim3(threads), lds, ctx->stream, pa);
@@ -868,7 +1005,7 @@ int ntt_dif_inplace(zkhip_ctx* ctx, const uint32_t* src, size_t src_stride, uint
                     unsigned log_n, size_t width, unsigned log_sub, bool inverse) {
     if (width == 0) return ZKHIP_OK;
     ZK_TRY(ensure_twiddles(ctx, log_n));
-    if (log_n >= P4_MIN_LOG_M) {
+    if (log_n >= P4_MIN_LOG_M && ctx->cfg.ntt_pass_form != 2) {
         const size_t per_col = (size_t)1 << (log_n + log_sub);
         const bool three = log_n > 2 * p4_log_r_limit();
         void* tmp;
@@ -1243,12 +1380,12 @@ int lde_batch(zkhip_ctx* ctx, const uint32_t* d_in, size_t in_stride, uint32_t* 
     if (in_stride < n || out_stride < (n << added_bits)) return set_error(ctx, ZKHIP_ERR_INVALID, "stride < height");
     if (log_n + added_bits > 27) return set_error(ctx, ZKHIP_ERR_INVALID, "LDE size exceeds two-adicity");
     ZK_TRY(ensure_twiddles(ctx, log_n + added_bits));
-    if (lde_fused_applies(log_n)) return lde_fused(ctx, d_in, in_stride, nullptr, d_out, out_stride, nullptr, log_n, added_bits, width, shift_monty);
+    if (lde_fused_applies(log_n) && ctx->cfg.ntt_pass_form != 2) return lde_fused(ctx, d_in, in_stride, nullptr, d_out, out_stride, nullptr, log_n, added_bits, width, shift_monty);
     // 1. inverse DIF into scratch: coefficients (unnormalised) in bit-reversed order
     void* coeffs;
     ZK_TRY(get_scratch(ctx, 0, n * width * 4, &coeffs));
     ZK_TRY(ntt_dif_inplace(ctx, d_in, in_stride, (uint32_t*)coeffs, n, log_n, width, 0, true));
-    if (log_n >= P4_MIN_LOG_M) {
+    if (log_n >= P4_MIN_LOG_M && ctx->cfg.ntt_pass_form != 2) {
         // 2'. forward four-step straight from the bit-reversed coefficients: the first pass reads each
         //     lane's 16 operands as one 64-byte chunk and applies shift_j^i / N as a geometric sequence
         unsigned a[3];
