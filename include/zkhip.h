@@ -625,6 +625,30 @@ int zkhip_stack_verify(const zkhip_whir_params *params, const uint32_t *prefix, 
                        const unsigned *log_heights, size_t n_cols, unsigned log_stack, const uint32_t *points, const unsigned *point_dims,
                        size_t n_points, const unsigned *col_point, const uint32_t *values, const uint32_t *proof, size_t words);
 
+/* ---- the AIR zero-check (docs/zerocheck.md): a proof that the main traces of n_airs AIRs satisfy, on every row, the constraints of
+ *      their programs that reach no PERM / CHAL / EXPOSED leaf (what air.py check_trace checks; the LogUp-phase constraints are the
+ *      bus proof's business).  All main columns (AIRs in caller order, columns in column order; a cached-main section is ignored) are
+ *      ONE stacked WHIR commitment at log_stack; per AIR a sum-check of log_height rounds of degree D = d + 1 (d = the largest
+ *      multilinear degree of a proven constraint: cells, is_first, is_last, is_transition count 1), the column values at its point,
+ *      a degree-2 reduction of the next-row values to the same columns, and one stacked opening with one point per AIR.
+ *      Proof words: [root (8) | per AIR: 4 D m + 4 w + 4 n_rot (+ 8 m + 4 w if n_rot > 0) | stacked opening].
+ *      Refused (ZKHIP_ERR_INVALID; zkhip_zerocheck_proof_words returns 0): a program with a PREP section, log_height outside
+ *      [1, ZKHIP_WHIR_MAX_LOG_N], more than ZKHIP_STACK_MAX_POINTS AIRs, a column total zkhip_stack_width refuses, D above
+ *      ZKHIP_ZEROCHECK_MAX_DEGREE. ---- */
+#define ZKHIP_ZEROCHECK_MAX_DEGREE 8
+size_t zkhip_zerocheck_proof_words(const zkhip_whir_params *params, const zkhip_air *airs, size_t n_airs, unsigned log_stack);
+/* d_traces / pvs as in zkhip_prove (device, column-major Montgomery, stride 1 << log_height; host canonical public values).  The
+ * transcript holds the caller's prefix (the place to bind programs and heights).  proof_out (HOST, cap >= zkhip_zerocheck_proof_words)
+ * canonical; root_out (HOST, 8 canonical words, may be NULL).  Allocates its workspace per call and frees it (ZKHIP_ERR_NOMEM if it
+ * does not fit); a zkhip_prove on the same context is unaffected. */
+int zkhip_zerocheck_prove(zkhip_ctx *ctx, const zkhip_whir_params *params, const zkhip_air *airs, size_t n_airs,
+                          const uint32_t *const *d_traces, const uint32_t *const *pvs, unsigned log_stack, zkhip_transcript *transcript,
+                          uint32_t *proof_out, size_t cap, uint32_t *root_out);
+/* host verifier: a fresh challenger observes `prefix`, then replays the proof.  ZKHIP_OK with root_out (8 canonical words, may be
+ * NULL) / ZKHIP_ERR_VERIFY (ZKHIP_ERR_INVALID for a refused shape or a malformed call).  Needs no device. */
+int zkhip_zerocheck_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const zkhip_air *airs, size_t n_airs,
+                           const uint32_t *const *pvs, unsigned log_stack, const uint32_t *proof, size_t words, uint32_t *root_out);
+
 /* Field offsets of a proof, in 32-bit words from its start (the layout is static for given parameters and AIR shapes:
  * DESIGN.md section 4).  The counterpart of `Proof::<SC>::decode_from_bytes` (crates/verifier/src/verifier.rs:62) for this
  * backend's proofs: commitments, opened values, FRI layers and query openings are read in place.  Needs no device. */

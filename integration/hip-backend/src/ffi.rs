@@ -30,6 +30,7 @@ pub const ZKHIP_WHIR_MAX_LOG_N: c_uint = 26;
 pub const ZKHIP_WHIR_MAX_QUERIES: u32 = 256;
 pub const ZKHIP_STACK_MAX_COLS: usize = 1024;
 pub const ZKHIP_STACK_MAX_POINTS: usize = 64;
+pub const ZKHIP_ZEROCHECK_MAX_DEGREE: c_uint = 8;
 pub const ZKHIP_SHA256_WIDTH: usize = 433;
 pub const ZKHIP_SHA256_PREP_WIDTH: usize = 6;
 pub const ZKHIP_SHA256_ROWS_PER_BLOCK: usize = 65;
@@ -429,6 +430,14 @@ extern "C" {
     pub fn zkhip_stack_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, root: *const u32,
                               log_heights: *const c_uint, n_cols: usize, log_stack: c_uint, points: *const u32, point_dims: *const c_uint,
                               n_points: usize, col_point: *const c_uint, values: *const u32, proof: *const u32, words: usize) -> c_int;
+
+    // the AIR zero-check over the stacked commitment (docs/zerocheck.md)
+    pub fn zkhip_zerocheck_proof_words(params: *const zkhip_whir_params, airs: *const zkhip_air, n_airs: usize, log_stack: c_uint) -> usize;
+    pub fn zkhip_zerocheck_prove(ctx: *mut zkhip_ctx, params: *const zkhip_whir_params, airs: *const zkhip_air, n_airs: usize,
+                                 d_traces: *const *const u32, pvs: *const *const u32, log_stack: c_uint, transcript: *mut zkhip_transcript,
+                                 proof_out: *mut u32, cap: usize, root_out: *mut u32) -> c_int;
+    pub fn zkhip_zerocheck_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, airs: *const zkhip_air, n_airs: usize,
+                                  pvs: *const *const u32, log_stack: c_uint, proof: *const u32, words: usize, root_out: *mut u32) -> c_int;
 
     // the reference's stored-proof container (OpenVM-v1 Proof<SC>, bincode)
     pub fn zkhip_proof_decode_v1(bytes: *const u8, len: usize, kind: c_int, out: *mut zkhip_v1_summary) -> c_int;

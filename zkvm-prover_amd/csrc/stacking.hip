@@ -258,7 +258,6 @@ struct zkhip_stack_commitment {
 };
 
 namespace zk {
-namespace {
 
 void stack_destroy(zkhip_ctx* ctx, zkhip_stack_commitment* sc) {
     if (!sc) return;
@@ -462,7 +461,6 @@ int stack_verify_host(HostChallenger& ch, const zkhip_whir_params* prm, const ui
     return ext_eq(total, claim) ? ZKHIP_OK : ZKHIP_ERR_VERIFY;
 }
 
-}  // namespace
 }  // namespace zk
 
 using namespace zk;

@@ -243,4 +243,15 @@ int whir_verify_host(HostChallenger& ch, const zkhip_whir_params* prm, const uin
                      const uint32_t* proof, size_t words, uint32_t* values_out);
 // w = eq(pts, .) over 2^mv entries (one point of mv extension coordinates, Montgomery) on stream st (k_whir_weight)
 void whir_eq_launch(hipStream_t st, uint32_t* w, unsigned mv, const uint32_t* pts);
+
+// stacking.hip: the entry points of include/zkhip.h on a live transcript / challenger (the zero-check continues its own with them)
+int stack_commit(zkhip_ctx* ctx, const zkhip_whir_params* prm, const uint32_t* const* d_cols, const unsigned* lh, size_t n_cols, unsigned l,
+                 zkhip_stack_commitment** out, uint32_t* root_out);
+void stack_destroy(zkhip_ctx* ctx, zkhip_stack_commitment* sc);
+// points HOST, canonical; values_out (may be null) / proof_out HOST, canonical; the transcript must already hold the root
+int stack_open(zkhip_ctx* ctx, zkhip_stack_commitment* sc, DevTranscript* d_t, const uint32_t* points, const unsigned* dims, size_t n_points,
+               const unsigned* col_point, uint32_t* values_out, uint32_t* proof_out, size_t cap);
+// the host verifier on a challenger the caller primed (the root included); the values it accepted are the proof's first 4 n_cols words
+int stack_verify_host(HostChallenger& ch, const zkhip_whir_params* prm, const uint32_t* root, const unsigned* lh, size_t n_cols, unsigned l,
+                      const uint32_t* points, const unsigned* dims, size_t n_points, const unsigned* col_point, const uint32_t* proof, size_t words);
 }  // namespace zk
