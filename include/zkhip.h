@@ -649,6 +649,27 @@ int zkhip_zerocheck_prove(zkhip_ctx *ctx, const zkhip_whir_params *params, const
 int zkhip_zerocheck_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const zkhip_air *airs, size_t n_airs,
                            const uint32_t *const *pvs, unsigned log_stack, const uint32_t *proof, size_t words, uint32_t *root_out);
 
+/* ---- the AIR-set proof (docs/airset.md): constraints AND bus balance of n_airs AIRs over one stacked commitment of their main
+ *      traces.  One LogUp-GKR proof whose leaves are computed from the committed traces (blocks sorted by non-increasing height, 2^L
+ *      leaves), per AIR with interactions one leaf claim B_a (4 words), per active AIR (a proven constraint or an interaction) ONE
+ *      sum-check of degree D_a = max(d_cons, d_bus) + 1 that carries the zero-check and the reduction of the leaf claims to column
+ *      values, the zero-check's rotation reduction, one stacked opening.  Argument forms as for the zero-check.
+ *      Proof words: [root (8) | GKR words for L | 4 per AIR with interactions | per active AIR the zero-check's layout with D_a |
+ *      stacked opening].  Refused (ZKHIP_ERR_INVALID; zkhip_airset_proof_words returns 0): everything the zero-check refuses (PREP
+ *      included), a set in which no AIR has an interaction, a set for which the per-bus row bound of the LogUp argument fails, L above
+ *      ZKHIP_GKR_MAX_LOG_N, D above ZKHIP_ZEROCHECK_MAX_DEGREE. ---- */
+size_t zkhip_airset_proof_words(const zkhip_whir_params *params, const zkhip_air *airs, size_t n_airs, unsigned log_stack);
+/* Device prover; arguments as zkhip_zerocheck_prove.  Workspace per call, freed: the zero-check's plus 20 B per leaf (2^L), one
+ * eq table (16 B x 2^m) per distinct height of an AIR with interactions, and the GKR workspace of the context. */
+int zkhip_airset_prove(zkhip_ctx *ctx, const zkhip_whir_params *params, const zkhip_air *airs, size_t n_airs,
+                       const uint32_t *const *d_traces, const uint32_t *const *pvs, unsigned log_stack, zkhip_transcript *transcript,
+                       uint32_t *proof_out, size_t cap, uint32_t *root_out);
+/* Host verifier, needs no device: requires P = 0 and Q != 0.  root_out (8 canonical words) and pq_out (P, Q: 8 canonical words) may
+ * be NULL. */
+int zkhip_airset_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const zkhip_air *airs, size_t n_airs,
+                        const uint32_t *const *pvs, unsigned log_stack, const uint32_t *proof, size_t words, uint32_t *root_out,
+                        uint32_t *pq_out);
+
 /* Field offsets of a proof, in 32-bit words from its start (the layout is static for given parameters and AIR shapes:
  * DESIGN.md section 4).  The counterpart of `Proof::<SC>::decode_from_bytes` (crates/verifier/src/verifier.rs:62) for this
  * backend's proofs: commitments, opened values, FRI layers and query openings are read in place.  Needs no device. */

@@ -1,0 +1,114 @@
+"""The AIR-set proof on the device (docs/airset.md): launches, kernel time per kernel name (the library's kernel stats,
+zkhip_profile_*), wall time and proof words of zkhip_airset_prove, split into the bus part (as_* and gkr_*), the sum-checks (zc_*) and
+commit plus opening (stack_*, whir_*), and beside it the fair comparison on the same key and the same library build: the two separate
+calls zkhip_zerocheck_prove plus zkhip_bus_gkr_prove (which prove less: their bus proof is not tied to the committed traces), and
+zkhip_prove.  Shapes: the lookup key of tools/gkr_bench.py (a sender of 2^20 rows, a table of 2^16) and the 42-chip ChipSet with a
+main-column range table in place of its preprocessed one.  Parameters (b, k, final_log) = (1, 4, 6), 80 queries and 16 bits of
+grinding in every round; v1 parameters z.DEFAULT_PARAMS.  Every figure is the median of --reps runs after one warm-up.  Prints one
+JSON object.
+
+  python tools/airset_bench.py [--reps 3] [--shapes lookup20x16,chipset42] [--no-v1]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import zkvm_prover_amd as z  # noqa: E402
+from whir_bench import _profiled  # noqa: E402
+from zkvm_prover_amd import air  # noqa: E402
+
+NOPV = np.zeros(0, np.uint32)
+
+
+def _lookup(ls, lt):
+    snd, tab = air.lookup_traces(ls, lt, seed=1)
+    return [dict(program=air.lookup_sender_air().program(), log_height=ls, width=3, n_pvs=0, trace=snd, pvs=NOPV),
+            dict(program=air.lookup_table_air().program(), log_height=lt, width=3, n_pvs=0, trace=tab, pvs=NOPV)]
+
+
+def _chipset():
+    """the 42 chips; the set's range table has preprocessed keys (out of scope): a two-row table with its keys in a main column"""
+    chips = air.ChipSet().gen()[:-1]
+    counts = sum(np.bincount(c["trace"][1].astype(np.int64), minlength=2)[:2] for c in chips)
+    tb = air.AirBuilder(2, 0)
+    tb.push_interaction(air.ChipSet.RANGE_BUS, [tb.var(0)], tb.var(1), "receive")
+    return chips + [dict(program=tb.program(), log_height=1, width=2, n_pvs=0, trace=np.array([[0, 1], counts % z.P], dtype=np.uint32), pvs=NOPV)]
+
+
+SHAPES = {
+    # (AIRs, log_stack)
+    "lookup20x16": (lambda: _lookup(20, 16), 20),
+    "chipset42": (_chipset, 20),
+}
+
+
+def _group(by_name):
+    g = {k: {"launches": 0, "ms": 0.0} for k in ("bus", "sumchecks", "commit_and_opening")}
+    for n, v in by_name.items():
+        k = "bus" if n.startswith(("as_", "gkr_")) else "sumchecks" if n.startswith("zc_") else "commit_and_opening"
+        g[k]["launches"] += v["launches"]
+        g[k]["ms"] = round(g[k]["ms"] + v["ms"], 3)
+    return g
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--no-v1", action="store_true")
+    a = ap.parse_args()
+    zk = z.Context(0)
+    prm = z.WhirParams.make(1, 4, 6, 16, 80)
+    out = {"airset": [], "zerocheck": [], "bus_gkr": [], "v1": []}
+
+    def note(r):
+        print(json.dumps({k: v for k, v in r.items() if k != "by_name"}), file=sys.stderr)
+
+    for name in [s for s in a.shapes.split(",") if s]:
+        airs_fn, l = SHAPES[name]
+        airs = airs_fn()
+        vairs = [{k: x[k] for k in ("program", "log_height", "width", "n_pvs")} for x in airs]
+        pvs = [x["pvs"] for x in airs]
+        d = [zk.upload(np.asarray(x["trace"], dtype=np.uint32).reshape(-1)) for x in airs]
+        words = z.airset_proof_words(prm, vairs, l)
+        common = dict(shape=name, n_airs=len(airs), log_stack=l, total_cells=sum(x["width"] << x["log_height"] for x in airs))
+        if not words:
+            out["airset"].append(dict(common, refused=True))
+            continue
+        proof = {}
+
+        def airset():
+            proof["p"] = zk.airset_prove(prm, vairs, d, pvs, l, [1])[1]
+
+        r = _profiled(zk, airset, a.reps)
+        z.airset_verify(prm, [1], vairs, pvs, l, proof["p"])
+        r.update(common, proof_words=words, split=_group(r["by_name"]))
+        out["airset"].append(r)
+        note(r)
+        r = _profiled(zk, lambda: zk.zerocheck_prove(prm, vairs, d, pvs, l, [1]), a.reps)
+        r.update(common, proof_words=z.zerocheck_proof_words(prm, vairs, l))
+        out["zerocheck"].append(r)
+        note(r)
+        pk = z.ProvingKey(zk, z.DEFAULT_PARAMS, airs)
+        r = _profiled(zk, lambda: pk.bus_gkr_prove(d, pvs, [1]), a.reps)
+        r.update(common, proof_words=int(pk.bus_gkr_prove(d, pvs, [1]).size))
+        out["bus_gkr"].append(r)
+        note(r)
+        if not a.no_v1:
+            r = _profiled(zk, lambda: pk.prove(d, pvs), a.reps)
+            r.update(common, proof_words=pk.proof_size // 4)
+            out["v1"].append(r)
+            note(r)
+        pk.close()
+        del d
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -329,6 +329,11 @@ def load_library():
         "zkhip_zerocheck_prove": (C.c_int, [vp, C.POINTER(WhirParams), C.POINTER(_Air), sz, C.POINTER(vp), C.POINTER(u32p), C.c_uint, vp, u32p, sz,
                                             u32p]),
         "zkhip_zerocheck_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, C.POINTER(_Air), sz, C.POINTER(u32p), C.c_uint, u32p, sz, u32p]),
+        "zkhip_airset_proof_words": (sz, [C.POINTER(WhirParams), C.POINTER(_Air), sz, C.c_uint]),
+        "zkhip_airset_prove": (C.c_int, [vp, C.POINTER(WhirParams), C.POINTER(_Air), sz, C.POINTER(vp), C.POINTER(u32p), C.c_uint, vp, u32p, sz,
+                                         u32p]),
+        "zkhip_airset_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, C.POINTER(_Air), sz, C.POINTER(u32p), C.c_uint, u32p, sz, u32p,
+                                          u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -1068,6 +1073,25 @@ class Context:
         self._check(rc)
         return root, proof[:words]
 
+    # ---- the AIR-set proof (docs/airset.md) ------------------------------------------------------------------------
+    def airset_prove(self, params, airs, traces, pvs, log_stack, prefix):
+        """Constraints and bus balance of `airs` over one stacked commitment of the device traces (arguments as zerocheck_prove) after
+        a fresh transcript observed `prefix`.  Returns (root (8 words), proof words), canonical numpy uint32; check with airset_verify."""
+        words = airset_proof_words(params, airs, log_stack)
+        arr, keep = _air_structs(airs)
+        tr = Transcript(self)
+        pre = np.ascontiguousarray(prefix, dtype=np.uint32)
+        if pre.size:
+            tr.observe(pre)
+        tp = (C.c_void_p * len(traces))(*[t.data_ptr() for t in traces])
+        pa, keep2 = _pvs_array(pvs)
+        proof = np.zeros(max(words, 1), dtype=np.uint32)
+        root = np.zeros(8, dtype=np.uint32)
+        rc = self.lib.zkhip_airset_prove(self.h, C.byref(params), arr, len(airs), tp, pa, log_stack, tr.h, _u32p(proof), proof.size, _u32p(root))
+        tr.close()
+        self._check(rc)
+        return root, proof[:words]
+
     # ---- profiling -----------------------------------------------------------------------------
     def profile_enable(self, on=True):
         self._check(self.lib.zkhip_profile_enable(self.h, int(on)))
@@ -1413,6 +1437,29 @@ def zerocheck_verify(params, prefix, airs, pvs, log_stack, proof):
         e.code = rc
         raise e
     return root
+
+
+def airset_proof_words(params, airs, log_stack):
+    """words of an AIR-set proof of these AIR shapes; 0 for a refused shape"""
+    arr, keep = _air_structs(airs)
+    return int(load_library().zkhip_airset_proof_words(C.byref(params), arr, len(airs), log_stack))
+
+
+def airset_verify(params, prefix, airs, pvs, log_stack, proof):
+    """Host verifier of an AIR-set proof (needs no GPU): a fresh challenger observes `prefix`, then the proof is replayed.  Returns
+    (root of the trace commitment (8 canonical words), (P, Q) of the fraction sum (8 canonical words)); raises ZkhipError (its `code`
+    is the library's status)."""
+    lib = load_library()
+    pre, pw = _gkr_words(prefix, proof)
+    arr, keep = _air_structs(airs)
+    pa, keep2 = _pvs_array(pvs)
+    root, pq = np.zeros(8, dtype=np.uint32), np.zeros(8, dtype=np.uint32)
+    rc = lib.zkhip_airset_verify(C.byref(params), _u32p(pre), pre.size, arr, len(airs), pa, log_stack, _u32p(pw), pw.size, _u32p(root), _u32p(pq))
+    if rc != 0:
+        e = ZkhipError("zkhip_airset_verify refused the proof (%d)" % rc)
+        e.code = rc
+        raise e
+    return root, pq
 
 
 def whir_proof_words(params, m, n_cols):

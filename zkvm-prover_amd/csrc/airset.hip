@@ -1,0 +1,602 @@
+// airset.hip -- constraints and bus balance of a set of AIRs over ONE stacked WHIR commitment: the LogUp-GKR leaves are computed from
+// the committed traces, and per AIR one sum-check carries the constraint zero-check and the reduction of the GKR's leaf claims to
+// column values.  Protocol, layout, limits and measurements: docs/airset.md.  The independent model is tests/airset_model.py.
+//
+// Device side: the leaves of all blocks in one launch (k_as_leaves), the fraction-sum proof (gkr_prove_device, its result stays on
+// the device), the blocks' eq factors and the roots' coefficients from rho, kappa and beta (k_as_coefs), the per-AIR leaf claims in
+// one pass over the leaf buffers (k_as_claims, k_as_claims_out), then per AIR the joint sum-check, the values and the rotation
+// reduction (zc_prove_air<true>, zerocheck_dev.hpp) and one stacked opening.  The host verifier is at the end of the file.
+#include <map>
+
+#include "zerocheck_dev.hpp"
+
+namespace zk {
+
+constexpr unsigned AS_BS = 256;          // threads of a leaf workgroup: 256 rows of one block
+constexpr unsigned AS_CLAIM_NB = 64;     // workgroups per AIR of the leaf-claim pass
+
+// one block of leaves: interaction j of an AIR, 2^m leaves from `off` on; the last descriptor is the padding (pad = 1)
+struct AsBlock {
+    const uint32_t* trace;   // the AIR's columns, stride 2^m, Montgomery
+    const uint32_t* pvs;     // Montgomery
+    const uint32_t* code;    // the interaction's operand program: roots = its fields, then its count
+    const uint32_t* consts;
+    uint64_t off, n;         // first leaf, leaves
+    uint32_t n_ins, bus1, sign, n_fields, pad;
+    uint32_t first_wg;       // its first workgroup in the flattened grid
+};
+
+// gamma, beta^1 .. beta^LOGUP_MAX_FIELDS (k_logup_chal's layout)
+__global__ void k_as_chal(const uint32_t* __restrict__ gb, uint32_t* __restrict__ lchal) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    sc_st(lchal, 0, sc_ld(gb, 0));
+    const Ext beta = sc_ld(gb, 1);
+    Ext cur = beta;
+    for (unsigned i = 1; i <= LOGUP_MAX_FIELDS; i++) sc_st(lchal, i, cur), cur = ext_mul(cur, beta);
+}
+
+// the block of a workgroup: the last one whose first_wg is <= wg (prover.hip's chip_of_block on the descriptors themselves)
+__device__ __forceinline__ uint32_t as_block_of(const AsBlock* __restrict__ blk, uint32_t n, uint32_t wg) {
+    uint32_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1) >> 1;
+        if (blk[mid].first_wg <= wg) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// num = +-count and den = gamma + bus + 1 + sum_i beta^(i+1) f_i of one row of one block, straight into the sorted layout; the
+// padding's leaves are (0, 1).  The operand program is k_logup_denoms' form: ASSERT k < n_fields is field k, the last one the count.
+__global__ __launch_bounds__(AS_BS) void k_as_leaves(const AsBlock* __restrict__ blk, uint32_t n_blk, const uint32_t* __restrict__ lchal,
+                                                     uint32_t* __restrict__ num, uint32_t* __restrict__ den) {
+    extern __shared__ uint32_t as_slots[];   // [slot][lane]
+    const AsBlock& b = blk[as_block_of(blk, n_blk, blockIdx.x)];
+    const unsigned tid = threadIdx.x;
+    const uint64_t r = (uint64_t)(blockIdx.x - b.first_wg) * AS_BS + tid;
+    if (r >= b.n) return;
+    if (b.pad) {
+        num[b.off + r] = 0;
+        sc_st(den, b.off + r, ext_one());
+        return;
+    }
+    Ext d = sc_ld(lchal, 0);
+    d.c[0] = madd(d.c[0], b.bus1);
+    uint32_t cnt = 0;
+    auto fetch = [&](uint32_t w) -> uint32_t {
+        const uint32_t idx = w & 0x07ffffffu;
+        switch (w >> 28) {
+            case K_SLOT: return as_slots[idx * AS_BS + tid];
+            case K_VAR: return b.trace[(size_t)idx * b.n + r];
+            case K_PUB: return b.pvs[idx];
+            default: return b.consts[idx];
+        }
+    };
+    for (uint32_t pc = 0; pc < b.n_ins; pc++) {
+        const uint32_t w0 = b.code[3 * pc], op = w0 & 0xffu, dst = w0 >> 8;
+        const uint32_t va = fetch(b.code[3 * pc + 1]);
+        if (op == Q_ASSERT) {
+            if (dst < b.n_fields) d = ext_add(d, ext_mul_base(sc_ld(lchal, dst + 1), va));
+            else cnt = b.sign ? mneg(va) : va;
+        } else if (op == Q_NEG) {
+            as_slots[dst * AS_BS + tid] = mneg(va);
+        } else {
+            const uint32_t vb = fetch(b.code[3 * pc + 2]);
+            as_slots[dst * AS_BS + tid] = op == Q_ADD ? madd(va, vb) : op == Q_SUB ? msub(va, vb) : mmul(va, vb);
+        }
+    }
+    num[b.off + r] = cnt;
+    sc_st(den, b.off + r, d);
+}
+
+// what the coefficient kernel knows of a block / of a root of an AIR's joint program
+struct AsBlockPos {
+    uint32_t m, hi;   // height, off >> m
+};
+struct AsRoot {
+    uint32_t block, kind;   // kind 0: a count sent (+), 1: a count received (-), 2 + i: field i
+};
+// From the GKR's point (canonical, at `point`), kappa and the beta powers: rho in Montgomery form, e_b = eq(rho[m_b..L), bits of
+// off_b >> m_b) per block, and per root e s (count) or kappa e beta^(i+1) (field i).
+__global__ __launch_bounds__(256) void k_as_coefs(const uint32_t* __restrict__ point, unsigned L, const uint32_t* __restrict__ kappa,
+                                                  const uint32_t* __restrict__ lchal, const AsBlockPos* __restrict__ pos, unsigned n_blk,
+                                                  const AsRoot* __restrict__ roots, unsigned n_roots, uint32_t* __restrict__ rho,
+                                                  uint32_t* __restrict__ eb, uint32_t* __restrict__ coef) {
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 4 * L) rho[i] = to_monty(point[i]);
+    auto e_of = [&](unsigned b) {
+        const AsBlockPos p = pos[b];
+        const Ext one = ext_one();
+        Ext e = one;
+        for (unsigned t = 0; p.m + t < L; t++) {
+            Ext x;
+            for (int q = 0; q < 4; q++) x.c[q] = to_monty(point[4 * (p.m + t) + q]);
+            e = ext_mul(e, (p.hi >> t) & 1u ? x : ext_sub(one, x));
+        }
+        return e;
+    };
+    if (i < n_blk) sc_st(eb, i, e_of(i));
+    if (i < n_roots) {
+        const AsRoot r = roots[i];
+        const Ext e = e_of(r.block);
+        sc_st(coef, i, r.kind == 0 ? e : r.kind == 1 ? ext_neg(e) : ext_mul(ext_mul(sc_ld(kappa, 0), e), sc_ld(lchal, r.kind - 1)));
+    }
+}
+
+// an AIR with interactions in the leaf-claim pass: its blocks ids[first .. first + n), eq(rho[0..m), .) at E
+struct AsClaim {
+    const uint32_t* E;
+    uint32_t m, first, n;
+};
+// stage 1: workgroup (x, a) sums e_b eq(rho_a, r) (num + kappa den) over its share of AIR a's leaves: 4 words at
+// partial[(4 a + q) AS_CLAIM_NB + x]
+__global__ __launch_bounds__(256) void k_as_claims(const AsClaim* __restrict__ cl, const uint32_t* __restrict__ ids, const AsBlock* __restrict__ blk,
+                                                   const uint32_t* __restrict__ eb, const uint32_t* __restrict__ kappa,
+                                                   const uint32_t* __restrict__ num, const uint32_t* __restrict__ den, uint32_t* __restrict__ partial) {
+    const AsClaim c = cl[blockIdx.y];
+    const Ext k = sc_ld(kappa, 0);
+    const uint64_t n = (uint64_t)1 << c.m, total = (uint64_t)c.n << c.m;
+    Ext acc[1] = {ext_zero()};
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)AS_CLAIM_NB * 256) {
+        const uint32_t b = ids[c.first + (uint32_t)(i >> c.m)];
+        const uint64_t r = i & (n - 1), at = blk[b].off + r;
+        Ext v = ext_mul(k, sc_ld(den, at));
+        v.c[0] = madd(v.c[0], num[at]);
+        acc[0] = ext_add(acc[0], ext_mul(sc_ld(eb, b), ext_mul(sc_ld(c.E, r), v)));
+    }
+    sc_block_sum(acc, partial + (size_t)4 * blockIdx.y * AS_CLAIM_NB + blockIdx.x, AS_CLAIM_NB);
+}
+// stage 2: wave a adds AIR a's partial sums up; B_a, canonical, to out[4 a ..]
+__global__ __launch_bounds__(64) void k_as_claims_out(const uint32_t* __restrict__ partial, uint32_t* __restrict__ out) {
+    for (int q = 0; q < 4; q++) {
+        const uint32_t x = sc_wave_sum(partial[(size_t)(4 * blockIdx.x + q) * AS_CLAIM_NB + threadIdx.x]);
+        if (threadIdx.x == 0) out[4 * blockIdx.x + q] = from_monty(x);
+    }
+}
+
+namespace {
+// ---- host side: the shape ---------------------------------------------------------------------------------------------------------
+struct AsBlk {
+    unsigned a, j, m;
+    uint64_t off;
+};
+struct AsShape {
+    std::vector<ZcPlan> plans;
+    std::vector<unsigned> lh, col_point, dims;
+    std::vector<AsBlk> blocks;   // sorted stably by non-increasing height, laid end to end
+    std::vector<size_t> b_at;    // per AIR: its place among the AIRs with interactions, or -1
+    unsigned L = 0;
+    size_t n_bus = 0, gkr_words = 0, head = 0, total = 0;   // head: the words before the stacked opening
+};
+bool as_shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, AsShape* S) {
+    if (!prm || !airs || n_airs < 1 || n_airs > ZKHIP_STACK_MAX_POINTS) return false;
+    S->plans.resize(n_airs);
+    std::vector<AirProgram> progs;
+    size_t n_cols = 0, air_words = 0;
+    for (size_t a = 0; a < n_airs; a++) {
+        ZcPlan& pl = S->plans[a];
+        if (!zc_plan(airs[a], &pl, true)) return false;
+        n_cols += airs[a].width;
+        if (n_cols > ZKHIP_STACK_MAX_COLS) return false;
+        air_words += pl.active() ? pl.words() : 0;
+        S->dims.push_back(airs[a].log_height);
+        for (size_t c = 0; c < airs[a].width; c++) S->lh.push_back(airs[a].log_height), S->col_point.push_back((unsigned)a);
+        S->b_at.push_back(pl.prog.ints.empty() ? (size_t)-1 : S->n_bus++);
+        for (size_t j = 0; j < pl.prog.ints.size(); j++) S->blocks.push_back({(unsigned)a, (unsigned)j, pl.m, 0});
+        progs.push_back(pl.prog);
+    }
+    if (S->blocks.empty()) return false;   // no interaction anywhere: zkhip_zerocheck_prove's case
+    if (!logup_bus_counts_bounded(progs.data(), S->dims.data(), n_airs)) return false;
+    std::stable_sort(S->blocks.begin(), S->blocks.end(), [](const AsBlk& x, const AsBlk& y) { return x.m > y.m; });
+    uint64_t T = 0;
+    for (AsBlk& b : S->blocks) b.off = T, T += (uint64_t)1 << b.m;
+    S->L = 1;
+    while (((uint64_t)1 << S->L) < T) S->L++;
+    if (S->L > ZKHIP_GKR_MAX_LOG_N) return false;
+    const size_t sw = zkhip_stack_proof_words(prm, S->lh.data(), S->lh.size(), l);
+    if (!sw) return false;
+    S->gkr_words = zkhip_gkr_proof_words(S->L);
+    S->head = 8 + S->gkr_words + 4 * S->n_bus + air_words;
+    S->total = S->head + sw;
+    return true;
+}
+
+// ---- the device prover ---------------------------------------------------------------------------------------------------------
+int as_prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
+             const uint32_t* const* pvs, unsigned l, DevTranscript* d_t, uint32_t* proof_out, size_t cap, uint32_t* root_out) {
+    AsShape S;
+    if (!as_shape(prm, airs, n_airs, l, &S)) return set_error(ctx, ZKHIP_ERR_INVALID, "airset: the shape does not fit the limits");
+    if (cap < S.total) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, "airset: proof buffer too small");
+    size_t n_pv = 0, pt_words = 0;
+    for (size_t a = 0; a < n_airs; a++) {
+        if (!d_traces[a] || (airs[a].n_pvs && !pvs[a])) return set_error(ctx, ZKHIP_ERR_INVALID, "airset: null trace or public values");
+        for (size_t i = 0; i < airs[a].n_pvs; i++)
+            if (pvs[a][i] >= P) return set_error(ctx, ZKHIP_ERR_INVALID, "airset: public value not canonical");
+        n_pv += airs[a].n_pvs, pt_words += 4 * (size_t)airs[a].log_height;
+    }
+    hipStream_t st = ctx->stream;
+    const unsigned L = S.L;
+    const size_t n_blk = S.blocks.size(), NL = (size_t)1 << L;
+    // 1. commit: every main column, AIRs in caller order
+    std::vector<const uint32_t*> cols;
+    for (size_t a = 0; a < n_airs; a++)
+        for (size_t c = 0; c < airs[a].width; c++) cols.push_back(d_traces[a] + (c << airs[a].log_height));
+    struct Com {
+        zkhip_ctx* ctx;
+        zkhip_stack_commitment* sc = nullptr;
+        ~Com() { stack_destroy(ctx, sc); }
+    } com{ctx};
+    uint32_t root[8];
+    ZK_TRY(stack_commit(ctx, prm, cols.data(), S.lh.data(), cols.size(), l, &com.sc, root));
+    // the interactions' operand programs, the descriptors and the roots of the joint programs: one upload
+    //   words: [code | consts | pvs (Montgomery) | ids]; then the three descriptor arrays in buffers of their own
+    std::vector<uint32_t> code, consts, pvm, ids;
+    std::vector<size_t> pv_at(n_airs);
+    for (size_t a = 0; a < n_airs; a++) {
+        pv_at[a] = pvm.size();
+        for (size_t i = 0; i < airs[a].n_pvs; i++) pvm.push_back(to_monty(pvs[a][i]));
+    }
+    struct Lowered {
+        size_t code_at, const_at, n_ins;
+    };
+    std::vector<Lowered> low(n_blk);
+    unsigned max_slots = 1;
+    for (size_t b = 0; b < n_blk; b++) {
+        const AsBlk& k = S.blocks[b];
+        const Interaction& it = S.plans[k.a].prog.ints[k.j];
+        std::vector<uint32_t> roots(it.fields, it.fields + it.n_fields);
+        roots.push_back(it.count);
+        CompiledAir ca;
+        std::string err;
+        if (compile_air(S.plans[k.a].prog, &ca, &err, &roots) != 0 || ca.n_slots > ZC_MAX_SLOTS)
+            return set_error(ctx, ZKHIP_ERR_INVALID, "airset: " + (err.empty() ? "an interaction needs more than 64 live intermediates" : err));
+        low[b] = {code.size() / 3, consts.size(), ca.code.size() / 3};
+        code.insert(code.end(), ca.code.begin(), ca.code.end());
+        consts.insert(consts.end(), ca.consts.begin(), ca.consts.end());
+        max_slots = std::max(max_slots, ca.n_slots);
+    }
+    // per AIR with interactions: its blocks in program order (ids), the roots of its bus part (count, then fields, per interaction)
+    std::vector<AsRoot> roots;
+    std::vector<size_t> root_at(n_airs, 0), ids_at(n_airs, 0);
+    {
+        std::vector<std::vector<uint32_t>> of(n_airs);
+        for (size_t a = 0; a < n_airs; a++) of[a].resize(S.plans[a].prog.ints.size());
+        for (size_t b = 0; b < n_blk; b++) of[S.blocks[b].a][S.blocks[b].j] = (uint32_t)b;
+        for (size_t a = 0; a < n_airs; a++) {
+            root_at[a] = roots.size(), ids_at[a] = ids.size();
+            for (size_t j = 0; j < of[a].size(); j++) {
+                const Interaction& it = S.plans[a].prog.ints[j];
+                ids.push_back(of[a][j]);
+                roots.push_back({of[a][j], it.sign});
+                for (uint32_t i = 0; i < it.n_fields; i++) roots.push_back({of[a][j], 2 + i});
+            }
+        }
+    }
+    std::vector<uint32_t> up(code);
+    const size_t o_consts = up.size();
+    up.insert(up.end(), consts.begin(), consts.end());
+    const size_t o_pvs = up.size();
+    up.insert(up.end(), pvm.begin(), pvm.end());
+    const size_t o_ids = up.size();
+    up.insert(up.end(), ids.begin(), ids.end());
+    ZcBufs B(ctx);
+    // device: [the words before the opening | the points r'_a (Montgomery)]; the root and the public values to observe; challenges
+    // [gamma | beta | kappa]; the beta powers; rho (Montgomery); e_b; the roots' coefficients; the leaves (20 B each)
+    uint32_t *dP = B.get(S.head + pt_words), *d_obs = B.get(8 + n_pv), *d_up = B.get(up.size()), *ch = B.get(12);
+    uint32_t *lchal = B.get(4 * (LOGUP_MAX_FIELDS + 1)), *rho = B.get(4 * (size_t)L), *eb = B.get(4 * n_blk), *coef = B.get(4 * roots.size());
+    uint32_t *d_num = B.get(NL), *d_den = B.get(4 * NL), *partial = B.get(4 * S.n_bus * AS_CLAIM_NB);
+    AsBlock* d_blk = (AsBlock*)B.get((n_blk + 1) * sizeof(AsBlock) / 4);
+    AsBlockPos* d_pos = (AsBlockPos*)B.get(n_blk * sizeof(AsBlockPos) / 4);
+    AsRoot* d_roots = (AsRoot*)B.get(roots.size() * sizeof(AsRoot) / 4);
+    AsClaim* d_cl = (AsClaim*)B.get(S.n_bus * sizeof(AsClaim) / 4);
+    if (!dP || !d_obs || !d_up || !ch || !lchal || !rho || !eb || !coef || !d_num || !d_den || !partial || !d_blk || !d_pos || !d_roots || !d_cl)
+        return set_error(ctx, ZKHIP_ERR_NOMEM, "airset: the leaves do not fit");
+    // one eq(rho[0..m), .) table per distinct height of an AIR with interactions
+    std::map<unsigned, uint32_t*> eq_of;
+    for (const AsBlk& k : S.blocks)
+        if (!eq_of.count(k.m) && !(eq_of[k.m] = B.get(4 * ((size_t)1 << k.m)))) return set_error(ctx, ZKHIP_ERR_NOMEM, "airset: the eq tables do not fit");
+    std::vector<AsBlock> hb(n_blk + 1);
+    std::vector<AsBlockPos> hpos(n_blk);
+    uint64_t wg = 0;
+    for (size_t b = 0; b <= n_blk; b++) {
+        AsBlock& d = hb[b];
+        d = AsBlock{};
+        d.first_wg = (uint32_t)wg;
+        if (b == n_blk) {   // the padding [T, 2^L)
+            const uint64_t T = S.blocks.back().off + ((uint64_t)1 << S.blocks.back().m);
+            d.off = T, d.n = NL - T, d.pad = 1;
+        } else {
+            const AsBlk& k = S.blocks[b];
+            const Interaction& it = S.plans[k.a].prog.ints[k.j];
+            d.trace = d_traces[k.a], d.pvs = d_up + o_pvs + pv_at[k.a];
+            d.code = d_up + 3 * low[b].code_at, d.consts = d_up + o_consts + low[b].const_at;
+            d.off = k.off, d.n = (uint64_t)1 << k.m;
+            d.n_ins = (uint32_t)low[b].n_ins, d.bus1 = to_monty(it.bus + 1), d.sign = it.sign, d.n_fields = it.n_fields;
+            hpos[b] = {k.m, (uint32_t)(k.off >> k.m)};
+        }
+        wg += (d.n + AS_BS - 1) / AS_BS;
+    }
+    std::vector<AsClaim> hcl;
+    for (size_t a = 0; a < n_airs; a++)
+        if (!S.plans[a].prog.ints.empty()) hcl.push_back({eq_of[S.plans[a].m], S.plans[a].m, (uint32_t)ids_at[a], (uint32_t)S.plans[a].prog.ints.size()});
+    std::vector<uint32_t> obs(root, root + 8);
+    for (size_t a = 0; a < n_airs; a++) obs.insert(obs.end(), pvs[a], pvs[a] + airs[a].n_pvs);
+    ZK_TRY(zkhip_h2d(ctx, d_obs, obs.data(), obs.size() * 4));
+    ZK_TRY(zkhip_h2d(ctx, d_up, up.data(), up.size() * 4));
+    ZK_TRY(zkhip_h2d(ctx, d_blk, hb.data(), hb.size() * sizeof(AsBlock)));
+    ZK_TRY(zkhip_h2d(ctx, d_pos, hpos.data(), hpos.size() * sizeof(AsBlockPos)));
+    ZK_TRY(zkhip_h2d(ctx, d_roots, roots.data(), roots.size() * sizeof(AsRoot)));
+    ZK_TRY(zkhip_h2d(ctx, d_cl, hcl.data(), hcl.size() * sizeof(AsClaim)));
+    ZK_TRY(transcript_observe(ctx, d_t, d_obs, (uint32_t)obs.size(), true));
+    // 2. gamma, beta   3. the leaves
+    ZK_TRY(transcript_sample(ctx, d_t, ch, nullptr, 4));
+    ZK_TRY(transcript_sample(ctx, d_t, ch + 4, nullptr, 4));
+    {
+        KernelScope ks(ctx, "as_chal");
+        hipLaunchKernelGGL(k_as_chal, dim3(1), dim3(64), 0, st, (const uint32_t*)ch, lchal);
+    }
+    {
+        KernelScope ks(ctx, "as_leaves");
+        hipLaunchKernelGGL(k_as_leaves, dim3((unsigned)wg), dim3(AS_BS), (size_t)max_slots * AS_BS * 4, st, (const AsBlock*)d_blk, (uint32_t)(n_blk + 1),
+                           (const uint32_t*)lchal, d_num, d_den);
+    }
+    ZK_HIP_CHECK(ctx, hipGetLastError());
+    // 4. the fraction-sum proof; its words, rho and the claims stay on the device
+    const uint32_t* d_res = nullptr;
+    ZK_TRY(gkr_prove_device(ctx, d_t, d_num, false, d_den, L, &d_res));
+    ZK_HIP_CHECK(ctx, hipMemcpyAsync(dP + 8, d_res, S.gkr_words * 4, hipMemcpyDeviceToDevice, st));
+    // 5. kappa, the coefficients, the eq tables, the leaf claims
+    uint32_t* kappa = ch + 8;
+    ZK_TRY(transcript_sample(ctx, d_t, kappa, nullptr, 4));
+    {
+        KernelScope ks(ctx, "as_coefs");
+        const size_t nthr = std::max<size_t>(std::max<size_t>(4 * L, n_blk), roots.size());
+        hipLaunchKernelGGL(k_as_coefs, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, d_res + S.gkr_words, L, (const uint32_t*)kappa,
+                           (const uint32_t*)lchal, (const AsBlockPos*)d_pos, (unsigned)n_blk, (const AsRoot*)d_roots, (unsigned)roots.size(), rho, eb,
+                           coef);
+    }
+    for (auto& e : eq_of) {
+        KernelScope ks(ctx, "as_eq");
+        whir_eq_launch(st, e.second, e.first, rho);
+    }
+    uint32_t* dB = dP + 8 + S.gkr_words;
+    {
+        KernelScope ks(ctx, "as_claims");
+        hipLaunchKernelGGL(k_as_claims, dim3(AS_CLAIM_NB, (unsigned)S.n_bus), dim3(256), 0, st, (const AsClaim*)d_cl, (const uint32_t*)(d_up + o_ids),
+                           (const AsBlock*)d_blk, (const uint32_t*)eb, (const uint32_t*)kappa, (const uint32_t*)d_num, (const uint32_t*)d_den, partial);
+    }
+    {
+        KernelScope ks(ctx, "as_claims");
+        hipLaunchKernelGGL(k_as_claims_out, dim3((unsigned)S.n_bus), dim3(64), 0, st, (const uint32_t*)partial, dB);
+    }
+    ZK_HIP_CHECK(ctx, hipGetLastError());
+    ZK_TRY(transcript_observe(ctx, d_t, dB, (uint32_t)(4 * S.n_bus), true));
+    // 6. - 8. per AIR
+    size_t off = 8 + S.gkr_words + 4 * S.n_bus, poff = S.head;
+    for (size_t a = 0; a < n_airs; a++) {
+        const ZcPlan& pl = S.plans[a];
+        if (pl.prog.ints.empty()) ZK_TRY(zc_prove_air<false>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff));
+        else ZK_TRY(zc_prove_air<true>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff, ZcBus{eq_of[pl.m], coef + 4 * root_at[a]}));
+        off += pl.active() ? pl.words() : 0;
+        poff += 4 * (size_t)pl.m;
+    }
+    // 9. the one read-back before the opening: the words so far and the points
+    std::vector<uint32_t> h(S.head + pt_words);
+    ZK_TRY(zkhip_d2h(ctx, h.data(), dP, h.size() * 4));
+    for (size_t i = S.head; i < h.size(); i++) h[i] = from_monty(h[i]);
+    ZK_TRY(stack_open(ctx, com.sc, d_t, h.data() + S.head, S.dims.data(), n_airs, S.col_point.data(), nullptr, proof_out + S.head, cap - S.head));
+    memcpy(proof_out, root, 32);
+    memcpy(proof_out + 8, h.data() + 8, (S.head - 8) * 4);
+    if (root_out) memcpy(root_out, root, 32);
+    return ZKHIP_OK;
+}
+
+// ---- the host verifier ---------------------------------------------------------------------------------------------------------
+// sum_j (cc_j count_j + sum_i cf_{j,i} f_{j,i}) on the column values v; coef in pl.bus_roots' order
+Ext as_bus_eval_host(const ZcPlan& pl, const Ext* v, const uint32_t* pvs, const Ext* coef) {
+    const AirProgram& g = pl.prog;
+    std::vector<char> reach(g.n_nodes, 0);
+    for (uint32_t r : pl.bus_roots) reach[r] = 1;
+    for (uint32_t i = g.n_nodes; i-- > 0;) {
+        const uint32_t op = g.nodes[3 * i];
+        if (!reach[i] || op < A_ADD || op > A_NEG) continue;
+        reach[g.nodes[3 * i + 1]] = 1;
+        if (op != A_NEG) reach[g.nodes[3 * i + 2]] = 1;
+    }
+    std::vector<Ext> val(g.n_nodes, ext_zero());
+    for (uint32_t i = 0; i < g.n_nodes; i++) {
+        if (!reach[i]) continue;
+        const uint32_t op = g.nodes[3 * i], x = g.nodes[3 * i + 1], y = g.nodes[3 * i + 2];
+        switch (op) {   // parse_air: operands of the current row only
+            case A_VAR: val[i] = v[x]; break;
+            case A_PUB: val[i] = ext_from_base(to_monty(pvs[x])); break;
+            case A_CONST: val[i] = ext_from_base(to_monty(x)); break;
+            case A_ADD: val[i] = ext_add(val[x], val[y]); break;
+            case A_SUB: val[i] = ext_sub(val[x], val[y]); break;
+            case A_MUL: val[i] = ext_mul(val[x], val[y]); break;
+            default: val[i] = ext_neg(val[x]);
+        }
+    }
+    Ext acc = ext_zero();
+    for (size_t k = 0; k < pl.bus_roots.size(); k++) acc = ext_add(acc, ext_mul(coef[k], val[pl.bus_roots[k]]));
+    return acc;
+}
+
+int as_verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
+              const uint32_t* const* pvs, unsigned l, const uint32_t* proof, size_t words, uint32_t* root_out, uint32_t* pq_out) {
+    AsShape S;
+    if (!as_shape(prm, airs, n_airs, l, &S)) return ZKHIP_ERR_INVALID;
+    for (size_t a = 0; a < n_airs; a++) {
+        if (airs[a].n_pvs && !pvs[a]) return ZKHIP_ERR_INVALID;
+        for (size_t i = 0; i < airs[a].n_pvs; i++)
+            if (pvs[a][i] >= P) return ZKHIP_ERR_INVALID;
+    }
+    for (size_t i = 0; i < n_prefix; i++)
+        if (prefix[i] >= P) return ZKHIP_ERR_INVALID;
+    if (words != S.total) return ZKHIP_ERR_VERIFY;
+    for (size_t i = 0; i < S.head; i++)
+        if (proof[i] >= P) return ZKHIP_ERR_VERIFY;
+    HostChallenger ch;
+    ch.observe_canon(prefix, n_prefix);
+    ch.observe_canon(proof, 8);
+    for (size_t a = 0; a < n_airs; a++) ch.observe_canon(pvs[a], airs[a].n_pvs);
+    const Ext one = ext_one();
+    const unsigned L = S.L;
+    // 2. - 4. gamma, beta, the fraction-sum proof: rho, (p*, q*), balance
+    const Ext gamma = ch.sample_ext(), beta = ch.sample_ext();
+    std::vector<uint32_t> pt(4 * (size_t)L);
+    uint32_t cl8[8];
+    Ext pq[2];
+    ZK_TRY(gkr_verify_host(ch, proof + 8, S.gkr_words, L, pt.data(), cl8, pq));
+    if (!ext_eq(pq[0], ext_zero()) || ext_eq(pq[1], ext_zero())) return ZKHIP_ERR_VERIFY;
+    std::vector<Ext> rho(L);
+    for (unsigned j = 0; j < L; j++) rho[j] = ext_from_canon(pt.data() + 4 * j);
+    const Ext pstar = ext_from_canon(cl8), qstar = ext_from_canon(cl8 + 4);
+    // 5. the leaf claims
+    const size_t n_blk = S.blocks.size();
+    std::vector<Ext> eb(n_blk);
+    Ext pad = one;
+    for (size_t b = 0; b < n_blk; b++) {
+        const AsBlk& k = S.blocks[b];
+        Ext e = one;
+        for (unsigned t = 0; k.m + t < L; t++) e = ext_mul(e, ((k.off >> k.m) >> t) & 1u ? rho[k.m + t] : ext_sub(one, rho[k.m + t]));
+        eb[b] = e, pad = ext_sub(pad, e);
+    }
+    const Ext kappa = ch.sample_ext();
+    const uint32_t* q = proof + 8 + S.gkr_words;
+    Ext lhs = ext_mul(kappa, pad);
+    for (size_t i = 0; i < S.n_bus; i++) lhs = ext_add(lhs, ext_from_canon(q + 4 * i));
+    ch.observe_canon(q, 4 * S.n_bus);
+    if (!ext_eq(lhs, ext_add(pstar, ext_mul(kappa, qstar)))) return ZKHIP_ERR_VERIFY;
+    const uint32_t* qB = q;
+    q += 4 * S.n_bus;
+    std::vector<Ext> bpow(LOGUP_MAX_FIELDS + 1);
+    bpow[0] = one;
+    for (unsigned i = 1; i <= LOGUP_MAX_FIELDS; i++) bpow[i] = ext_mul(bpow[i - 1], beta);
+    std::vector<std::vector<size_t>> blk_of(n_airs);   // AIR -> its blocks in program order
+    for (size_t a = 0; a < n_airs; a++) blk_of[a].resize(S.plans[a].prog.ints.size());
+    for (size_t b = 0; b < n_blk; b++) blk_of[S.blocks[b].a][S.blocks[b].j] = b;
+    std::vector<uint32_t> points;
+    std::vector<const uint32_t*> claimed(n_airs, nullptr);
+    for (size_t a = 0; a < n_airs; a++) {
+        const ZcPlan& pl = S.plans[a];
+        const unsigned m = pl.m, D = pl.D;
+        const size_t w = pl.w, n_rot = pl.rot.size();
+        const bool has_cons = !pl.proven.empty(), has_bus = !pl.prog.ints.empty();
+        std::vector<Ext> rp(m);
+        if (!pl.active()) {
+            for (unsigned j = 0; j < m; j++) rp[j] = ch.sample_ext();
+        } else {
+            // 6. the joint sum-check
+            std::vector<Ext> tau(m), r(m), coef;
+            Ext alpha = ext_zero(), claim = ext_zero();
+            if (has_cons) {
+                for (unsigned j = 0; j < m; j++) tau[j] = ch.sample_ext();
+                alpha = ch.sample_ext();
+            }
+            if (has_bus) {
+                Ext cst = ext_zero();   // sum_j e_{a,j} (gamma + bus_j + 1)
+                for (size_t j = 0; j < blk_of[a].size(); j++) {
+                    const Interaction& it = pl.prog.ints[j];
+                    const Ext e = eb[blk_of[a][j]], ke = ext_mul(kappa, e);
+                    Ext g1 = gamma;
+                    g1.c[0] = madd(g1.c[0], to_monty(it.bus + 1));
+                    cst = ext_add(cst, ext_mul(e, g1));
+                    coef.push_back(it.sign ? ext_neg(e) : e);
+                    for (uint32_t i = 0; i < it.n_fields; i++) coef.push_back(ext_mul(ke, bpow[i + 1]));
+                }
+                claim = ext_sub(ext_from_canon(qB + 4 * S.b_at[a]), ext_mul(kappa, cst));
+            }
+            for (unsigned i = 0; i < m; i++, q += 4 * D) {
+                Ext s[ZKHIP_ZEROCHECK_MAX_DEGREE + 1];
+                s[0] = ext_from_canon(q), s[1] = ext_sub(claim, s[0]);
+                for (unsigned e = 1; e < D; e++) s[e + 1] = ext_from_canon(q + 4 * e);
+                ch.observe_canon(q, 4 * D);
+                r[i] = ch.sample_ext();
+                claim = poly_at(s, D, r[i]);
+            }
+            // 7. the values
+            std::vector<Ext> v(w), vn(n_rot);
+            for (size_t j = 0; j < w; j++) v[j] = ext_from_canon(q + 4 * j);
+            for (size_t t = 0; t < n_rot; t++) vn[t] = ext_from_canon(q + 4 * (w + t));
+            ch.observe_canon(q, 4 * (w + n_rot));
+            const uint32_t* qv = q;
+            q += 4 * (w + n_rot);
+            Ext rhs = ext_zero();
+            if (has_cons) {
+                Ext first = one, last = one;
+                for (unsigned j = 0; j < m; j++) first = ext_mul(first, ext_sub(one, r[j])), last = ext_mul(last, r[j]);
+                rhs = ext_mul(eq_eval(tau.data(), r.data(), m), zc_eval_host(pl, v.data(), vn.data(), first, last, pvs[a], alpha));
+            }
+            if (has_bus) rhs = ext_add(rhs, ext_mul(eq_eval(rho.data(), r.data(), m), as_bus_eval_host(pl, v.data(), pvs[a], coef.data())));
+            if (!ext_eq(rhs, claim)) return ZKHIP_ERR_VERIFY;
+            // 8. the rotation reduction
+            if (n_rot == 0) {
+                rp = r, claimed[a] = qv;
+            } else {
+                const Ext lambda = ch.sample_ext();
+                std::vector<Ext> lp(w + n_rot);
+                Ext x = one;
+                claim = ext_zero();
+                for (size_t j = 0; j < w + n_rot; j++) lp[j] = x, claim = ext_add(claim, ext_mul(x, j < w ? v[j] : vn[j - w])), x = ext_mul(x, lambda);
+                for (unsigned i = 0; i < m; i++, q += 8) {
+                    const Ext s0 = ext_from_canon(q), s2 = ext_from_canon(q + 4);
+                    ch.observe_canon(q, 8);
+                    rp[i] = ch.sample_ext();
+                    const Ext sv[3] = {s0, ext_sub(claim, s0), s2};
+                    claim = poly_at(sv, 2, rp[i]);
+                }
+                Ext ua = ext_zero(), ub = ext_zero();
+                for (size_t j = 0; j < w; j++) ua = ext_add(ua, ext_mul(lp[j], ext_from_canon(q + 4 * j)));
+                for (size_t t = 0; t < n_rot; t++) ub = ext_add(ub, ext_mul(lp[w + t], ext_from_canon(q + 4 * pl.rot[t])));
+                ch.observe_canon(q, 4 * w);
+                claimed[a] = q, q += 4 * w;
+                const Ext want = ext_add(ext_mul(ua, eq_eval(r.data(), rp.data(), m)), ext_mul(ub, zc_rot_eval(r.data(), rp.data(), m)));
+                if (!ext_eq(want, claim)) return ZKHIP_ERR_VERIFY;
+            }
+        }
+        for (unsigned j = 0; j < m; j++) {
+            uint32_t c4[4];
+            ext_to_canon(c4, rp[j]);
+            points.insert(points.end(), c4, c4 + 4);
+        }
+    }
+    // 9. the stacked opening
+    const uint32_t* op = proof + S.head;
+    ZK_TRY(stack_verify_host(ch, prm, proof, S.lh.data(), S.lh.size(), l, points.data(), S.dims.data(), n_airs, S.col_point.data(), op, words - S.head));
+    size_t col = 0;
+    for (size_t a = 0; a < n_airs; col += airs[a].width, a++)
+        if (claimed[a] && memcmp(claimed[a], op + 4 * col, 16 * airs[a].width) != 0) return ZKHIP_ERR_VERIFY;
+    if (root_out) memcpy(root_out, proof, 32);
+    if (pq_out) memcpy(pq_out, proof + 8, 32);
+    return ZKHIP_OK;
+}
+}  // namespace
+
+}  // namespace zk
+
+using namespace zk;
+
+extern "C" {
+
+size_t zkhip_airset_proof_words(const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, unsigned log_stack) {
+    AsShape S;
+    return as_shape(params, airs, n_airs, log_stack, &S) ? S.total : 0;
+}
+
+int zkhip_airset_prove(zkhip_ctx* ctx, const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
+                       const uint32_t* const* pvs, unsigned log_stack, zkhip_transcript* transcript, uint32_t* proof_out, size_t cap,
+                       uint32_t* root_out) {
+    ZK_BIND_DEVICE(ctx);
+    if (!ctx || !params || !airs || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
+    return as_prove(ctx, params, airs, n_airs, d_traces, pvs, log_stack, transcript->d, proof_out, cap, root_out);
+}
+
+int zkhip_airset_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
+                        const uint32_t* const* pvs, unsigned log_stack, const uint32_t* proof, size_t words, uint32_t* root_out,
+                        uint32_t* pq_out) {
+    if (!params || (n_prefix && !prefix) || !airs || !pvs || !proof) return ZKHIP_ERR_INVALID;
+    return as_verify(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, root_out, pq_out);
+}
+
+}  // extern "C"
