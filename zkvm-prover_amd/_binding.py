@@ -400,7 +400,9 @@ class Context:
 
     def _check(self, rc):
         if rc != 0:
-            raise ZkhipError("zkhip error %d: %s" % (rc, self.lib.zkhip_last_error(self.h).decode()))
+            e = ZkhipError("zkhip error %d: %s" % (rc, self.lib.zkhip_last_error(self.h).decode()))
+            e.code = rc   # as the host verifiers' errors carry it
+            raise e
 
     def sync(self):
         self._check(self.lib.zkhip_sync(self.h))
