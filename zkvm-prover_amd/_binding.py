@@ -1059,27 +1059,17 @@ class Context:
         """Zero-check of the main-trace constraints of `airs` (dicts as for ProvingKey) on the device traces (column-major, Montgomery,
         as for ProvingKey.prove) after a fresh transcript observed `prefix`.  Returns (root (8 words), proof words), canonical numpy
         uint32; check with zerocheck_verify."""
-        words = zerocheck_proof_words(params, airs, log_stack)
-        arr, keep = _air_structs(airs)
-        tr = Transcript(self)
-        pre = np.ascontiguousarray(prefix, dtype=np.uint32)
-        if pre.size:
-            tr.observe(pre)
-        tp = (C.c_void_p * len(traces))(*[t.data_ptr() for t in traces])
-        pa, keep2 = _pvs_array(pvs)
-        proof = np.zeros(max(words, 1), dtype=np.uint32)
-        root = np.zeros(8, dtype=np.uint32)
-        rc = self.lib.zkhip_zerocheck_prove(self.h, C.byref(params), arr, len(airs), tp, pa, log_stack, tr.h, _u32p(proof), proof.size,
-                                            _u32p(root))
-        tr.close()
-        self._check(rc)
-        return root, proof[:words]
+        return self._air_prove("zkhip_zerocheck", params, airs, traces, pvs, log_stack, prefix)
 
     # ---- the AIR-set proof (docs/airset.md) ------------------------------------------------------------------------
     def airset_prove(self, params, airs, traces, pvs, log_stack, prefix):
         """Constraints and bus balance of `airs` over one stacked commitment of the device traces (arguments as zerocheck_prove) after
         a fresh transcript observed `prefix`.  Returns (root (8 words), proof words), canonical numpy uint32; check with airset_verify."""
-        words = airset_proof_words(params, airs, log_stack)
+        return self._air_prove("zkhip_airset", params, airs, traces, pvs, log_stack, prefix)
+
+    def _air_prove(self, sym, params, airs, traces, pvs, log_stack, prefix):
+        """zerocheck_prove / airset_prove: `sym`_prove (zkhip_zerocheck_prove, zkhip_airset_prove) after a fresh transcript observed `prefix`"""
+        words = _air_proof_words(sym, params, airs, log_stack)
         arr, keep = _air_structs(airs)
         tr = Transcript(self)
         pre = np.ascontiguousarray(prefix, dtype=np.uint32)
@@ -1089,7 +1079,8 @@ class Context:
         pa, keep2 = _pvs_array(pvs)
         proof = np.zeros(max(words, 1), dtype=np.uint32)
         root = np.zeros(8, dtype=np.uint32)
-        rc = self.lib.zkhip_airset_prove(self.h, C.byref(params), arr, len(airs), tp, pa, log_stack, tr.h, _u32p(proof), proof.size, _u32p(root))
+        rc = getattr(self.lib, sym + "_prove")(self.h, C.byref(params), arr, len(airs), tp, pa, log_stack, tr.h, _u32p(proof), proof.size,
+                                               _u32p(root))
         tr.close()
         self._check(rc)
         return root, proof[:words]
@@ -1419,49 +1410,50 @@ def stack_verify(params, prefix, root, log_heights, log_stack, points, col_point
         raise ZkhipError("zkhip_stack_verify refused the proof (%d)" % rc)
 
 
+def _air_proof_words(sym, params, airs, log_stack):
+    """zerocheck_proof_words / airset_proof_words: `sym`_proof_words (zkhip_zerocheck_proof_words, zkhip_airset_proof_words)"""
+    arr, keep = _air_structs(airs)
+    return int(getattr(load_library(), sym + "_proof_words")(C.byref(params), arr, len(airs), log_stack))
+
+
+def _air_verify(sym, params, prefix, airs, pvs, log_stack, proof, n_out):
+    """zerocheck_verify / airset_verify: `sym`_verify (zkhip_zerocheck_verify, zkhip_airset_verify) with n_out outputs of 8 words (the
+    root; airset: then (P, Q)); returns them"""
+    lib = load_library()
+    pre, pw = _gkr_words(prefix, proof)
+    arr, keep = _air_structs(airs)
+    pa, keep2 = _pvs_array(pvs)
+    outs = [np.zeros(8, dtype=np.uint32) for _ in range(n_out)]
+    rc = getattr(lib, sym + "_verify")(C.byref(params), _u32p(pre), pre.size, arr, len(airs), pa, log_stack, _u32p(pw), pw.size,
+                                       *[_u32p(o) for o in outs])
+    if rc != 0:
+        e = ZkhipError("%s_verify refused the proof (%d)" % (sym, rc))
+        e.code = rc
+        raise e
+    return outs
+
+
 def zerocheck_proof_words(params, airs, log_stack):
     """words of a zero-check proof of these AIR shapes; 0 for a refused shape"""
-    arr, keep = _air_structs(airs)
-    return int(load_library().zkhip_zerocheck_proof_words(C.byref(params), arr, len(airs), log_stack))
+    return _air_proof_words("zkhip_zerocheck", params, airs, log_stack)
 
 
 def zerocheck_verify(params, prefix, airs, pvs, log_stack, proof):
     """Host verifier of a zero-check proof (needs no GPU): a fresh challenger observes `prefix`, then the proof is replayed.  Returns
     the root of the trace commitment (8 canonical words); raises ZkhipError (its `code` is the library's status)."""
-    lib = load_library()
-    pre, pw = _gkr_words(prefix, proof)
-    arr, keep = _air_structs(airs)
-    pa, keep2 = _pvs_array(pvs)
-    root = np.zeros(8, dtype=np.uint32)
-    rc = lib.zkhip_zerocheck_verify(C.byref(params), _u32p(pre), pre.size, arr, len(airs), pa, log_stack, _u32p(pw), pw.size, _u32p(root))
-    if rc != 0:
-        e = ZkhipError("zkhip_zerocheck_verify refused the proof (%d)" % rc)
-        e.code = rc
-        raise e
-    return root
+    return _air_verify("zkhip_zerocheck", params, prefix, airs, pvs, log_stack, proof, 1)[0]
 
 
 def airset_proof_words(params, airs, log_stack):
     """words of an AIR-set proof of these AIR shapes; 0 for a refused shape"""
-    arr, keep = _air_structs(airs)
-    return int(load_library().zkhip_airset_proof_words(C.byref(params), arr, len(airs), log_stack))
+    return _air_proof_words("zkhip_airset", params, airs, log_stack)
 
 
 def airset_verify(params, prefix, airs, pvs, log_stack, proof):
     """Host verifier of an AIR-set proof (needs no GPU): a fresh challenger observes `prefix`, then the proof is replayed.  Returns
     (root of the trace commitment (8 canonical words), (P, Q) of the fraction sum (8 canonical words)); raises ZkhipError (its `code`
     is the library's status)."""
-    lib = load_library()
-    pre, pw = _gkr_words(prefix, proof)
-    arr, keep = _air_structs(airs)
-    pa, keep2 = _pvs_array(pvs)
-    root, pq = np.zeros(8, dtype=np.uint32), np.zeros(8, dtype=np.uint32)
-    rc = lib.zkhip_airset_verify(C.byref(params), _u32p(pre), pre.size, arr, len(airs), pa, log_stack, _u32p(pw), pw.size, _u32p(root), _u32p(pq))
-    if rc != 0:
-        e = ZkhipError("zkhip_airset_verify refused the proof (%d)" % rc)
-        e.code = rc
-        raise e
-    return root, pq
+    return tuple(_air_verify("zkhip_airset", params, prefix, airs, pvs, log_stack, proof, 2))
 
 
 def whir_proof_words(params, m, n_cols):

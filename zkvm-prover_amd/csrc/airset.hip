@@ -1,11 +1,18 @@
-// airset.hip -- constraints and bus balance of a set of AIRs over ONE stacked WHIR commitment: the LogUp-GKR leaves are computed from
-// the committed traces, and per AIR one sum-check carries the constraint zero-check and the reduction of the GKR's leaf claims to
-// column values.  Protocol, layout, limits and measurements: docs/airset.md.  The independent model is tests/airset_model.py.
+// airset.hip -- the host side of two proofs over ONE stacked WHIR commitment of the main traces of a set of AIRs.  The AIR zero-check
+// (zkhip_zerocheck_*, docs/zerocheck.md, model tests/zerocheck_model.py): the main-trace constraints hold on every row.  The AIR-set
+// proof (zkhip_airset_*, docs/airset.md, model tests/airset_model.py): the zero-check's steps plus a bus part that an AIR may lack;
+// the LogUp-GKR leaves are computed from the committed traces, and per AIR one sum-check carries the constraint zero-check and the
+// reduction of the GKR's leaf claims to column values.  Protocols, layouts, limits and measurements are in the two documents.
 //
-// Device side: the leaves of all blocks in one launch (k_as_leaves), the fraction-sum proof (gkr_prove_device, its result stays on
-// the device), the blocks' eq factors and the roots' coefficients from rho, kappa and beta (k_as_coefs), the per-AIR leaf claims in
-// one pass over the leaf buffers (k_as_claims, k_as_claims_out), then per AIR the joint sum-check, the values and the rotation
-// reduction (zc_prove_air<true>, zerocheck_dev.hpp) and one stacked opening.  The host verifier is at the end of the file.
+// Device side, per AIR (zc_prove_air, zerocheck_dev.hpp): eq(tau, .) (k_whir_weight); round 0 of the sum-check straight from the
+// base-field trace, the constraint program interpreted in the base field once per point (k_zc_round0); the later rounds as one
+// streaming pass each that folds every table with the previous challenge and interprets the program in the extension field
+// (k_zc_pass), to the last round; the values from the last fold; the rotation reduction on the sum-check core (k_sc_pass,
+// sc_small_round) and the columns' values at its point (k_zc_dot).  Then one stacked opening (stacking.hip).
+// The bus part, before the AIRs: the leaves of all blocks in one launch (k_as_leaves), the fraction-sum proof (gkr_prove_device, its
+// result stays on the device), the blocks' eq factors and the roots' coefficients from rho, kappa and beta (k_as_coefs), the per-AIR
+// leaf claims in one pass over the leaf buffers (k_as_claims, k_as_claims_out); an AIR with interactions then runs
+// zc_prove_air<true>.  One prover frame, one host verifier (at the end of the file) and one shape serve both proofs.
 #include <map>
 
 #include "zerocheck_dev.hpp"
@@ -160,74 +167,63 @@ struct AsBlk {
     unsigned a, j, m;
     uint64_t off;
 };
-struct AsShape {
+// the whole shape of either proof: plans, the stacked columns' heights and AIRs, the words before the stacked opening
+struct Shape {
     std::vector<ZcPlan> plans;
     std::vector<unsigned> lh, col_point, dims;
+    size_t head = 8, total = 0;   // head: the words before the stacked opening
+    // with_bus only
     std::vector<AsBlk> blocks;   // sorted stably by non-increasing height, laid end to end
     std::vector<size_t> b_at;    // per AIR: its place among the AIRs with interactions, or -1
     unsigned L = 0;
-    size_t n_bus = 0, gkr_words = 0, head = 0, total = 0;   // head: the words before the stacked opening
+    size_t n_bus = 0, gkr_words = 0;
 };
-bool as_shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, AsShape* S) {
+// false = refused.  Without with_bus the AIRs' interactions are ignored: their plans have no bus roots (and another D).
+bool shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus, Shape* S) {
     if (!prm || !airs || n_airs < 1 || n_airs > ZKHIP_STACK_MAX_POINTS) return false;
     S->plans.resize(n_airs);
     std::vector<AirProgram> progs;
-    size_t n_cols = 0, air_words = 0;
+    size_t n_cols = 0;
     for (size_t a = 0; a < n_airs; a++) {
         ZcPlan& pl = S->plans[a];
-        if (!zc_plan(airs[a], &pl, true)) return false;
+        if (!zc_plan(airs[a], &pl, with_bus)) return false;
         n_cols += airs[a].width;
         if (n_cols > ZKHIP_STACK_MAX_COLS) return false;
-        air_words += pl.active() ? pl.words() : 0;
+        S->head += pl.active() ? pl.words() : 0;
         S->dims.push_back(airs[a].log_height);
         for (size_t c = 0; c < airs[a].width; c++) S->lh.push_back(airs[a].log_height), S->col_point.push_back((unsigned)a);
+        if (!with_bus) continue;
         S->b_at.push_back(pl.prog.ints.empty() ? (size_t)-1 : S->n_bus++);
         for (size_t j = 0; j < pl.prog.ints.size(); j++) S->blocks.push_back({(unsigned)a, (unsigned)j, pl.m, 0});
         progs.push_back(pl.prog);
     }
-    if (S->blocks.empty()) return false;   // no interaction anywhere: zkhip_zerocheck_prove's case
-    if (!logup_bus_counts_bounded(progs.data(), S->dims.data(), n_airs)) return false;
-    std::stable_sort(S->blocks.begin(), S->blocks.end(), [](const AsBlk& x, const AsBlk& y) { return x.m > y.m; });
-    uint64_t T = 0;
-    for (AsBlk& b : S->blocks) b.off = T, T += (uint64_t)1 << b.m;
-    S->L = 1;
-    while (((uint64_t)1 << S->L) < T) S->L++;
-    if (S->L > ZKHIP_GKR_MAX_LOG_N) return false;
+    if (with_bus) {
+        if (S->blocks.empty()) return false;   // no interaction anywhere: zkhip_zerocheck_prove's case
+        if (!logup_bus_counts_bounded(progs.data(), S->dims.data(), n_airs)) return false;
+        std::stable_sort(S->blocks.begin(), S->blocks.end(), [](const AsBlk& x, const AsBlk& y) { return x.m > y.m; });
+        uint64_t T = 0;
+        for (AsBlk& b : S->blocks) b.off = T, T += (uint64_t)1 << b.m;
+        S->L = 1;
+        while (((uint64_t)1 << S->L) < T) S->L++;
+        if (S->L > ZKHIP_GKR_MAX_LOG_N) return false;
+        S->gkr_words = zkhip_gkr_proof_words(S->L);
+        S->head += S->gkr_words + 4 * S->n_bus;
+    }
     const size_t sw = zkhip_stack_proof_words(prm, S->lh.data(), S->lh.size(), l);
     if (!sw) return false;
-    S->gkr_words = zkhip_gkr_proof_words(S->L);
-    S->head = 8 + S->gkr_words + 4 * S->n_bus + air_words;
     S->total = S->head + sw;
     return true;
 }
 
 // ---- the device prover ---------------------------------------------------------------------------------------------------------
-int as_prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
-             const uint32_t* const* pvs, unsigned l, DevTranscript* d_t, uint32_t* proof_out, size_t cap, uint32_t* root_out) {
-    AsShape S;
-    if (!as_shape(prm, airs, n_airs, l, &S)) return set_error(ctx, ZKHIP_ERR_INVALID, "airset: the shape does not fit the limits");
-    if (cap < S.total) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, "airset: proof buffer too small");
-    size_t n_pv = 0, pt_words = 0;
-    for (size_t a = 0; a < n_airs; a++) {
-        if (!d_traces[a] || (airs[a].n_pvs && !pvs[a])) return set_error(ctx, ZKHIP_ERR_INVALID, "airset: null trace or public values");
-        for (size_t i = 0; i < airs[a].n_pvs; i++)
-            if (pvs[a][i] >= P) return set_error(ctx, ZKHIP_ERR_INVALID, "airset: public value not canonical");
-        n_pv += airs[a].n_pvs, pt_words += 4 * (size_t)airs[a].log_height;
-    }
+// The bus part of the AIR-set proof (docs/airset.md, steps 2 - 5), after the root and the public values were observed: the leaves,
+// the fraction-sum proof (its words to dP + 8), the leaf claims B_a (after them), and per AIR with interactions what its joint
+// sum-check needs (bus[a]).  Its buffers are B's: they live until the caller's per-AIR loop is done.
+int prove_bus(zkhip_ctx* ctx, const Shape& S, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces, const uint32_t* const* pvs,
+              DevTranscript* d_t, DevBufs& B, uint32_t* dP, std::vector<ZcBus>* bus) {
     hipStream_t st = ctx->stream;
     const unsigned L = S.L;
     const size_t n_blk = S.blocks.size(), NL = (size_t)1 << L;
-    // 1. commit: every main column, AIRs in caller order
-    std::vector<const uint32_t*> cols;
-    for (size_t a = 0; a < n_airs; a++)
-        for (size_t c = 0; c < airs[a].width; c++) cols.push_back(d_traces[a] + (c << airs[a].log_height));
-    struct Com {
-        zkhip_ctx* ctx;
-        zkhip_stack_commitment* sc = nullptr;
-        ~Com() { stack_destroy(ctx, sc); }
-    } com{ctx};
-    uint32_t root[8];
-    ZK_TRY(stack_commit(ctx, prm, cols.data(), S.lh.data(), cols.size(), l, &com.sc, root));
     // the interactions' operand programs, the descriptors and the roots of the joint programs: one upload
     //   words: [code | consts | pvs (Montgomery) | ids]; then the three descriptor arrays in buffers of their own
     std::vector<uint32_t> code, consts, pvm, ids;
@@ -279,17 +275,15 @@ int as_prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs
     up.insert(up.end(), pvm.begin(), pvm.end());
     const size_t o_ids = up.size();
     up.insert(up.end(), ids.begin(), ids.end());
-    ZcBufs B(ctx);
-    // device: [the words before the opening | the points r'_a (Montgomery)]; the root and the public values to observe; challenges
-    // [gamma | beta | kappa]; the beta powers; rho (Montgomery); e_b; the roots' coefficients; the leaves (20 B each)
-    uint32_t *dP = B.get(S.head + pt_words), *d_obs = B.get(8 + n_pv), *d_up = B.get(up.size()), *ch = B.get(12);
+    // device: challenges [gamma | beta | kappa]; the beta powers; rho (Montgomery); e_b; the roots' coefficients; the leaves (20 B each)
+    uint32_t *d_up = B.get(up.size()), *ch = B.get(12);
     uint32_t *lchal = B.get(4 * (LOGUP_MAX_FIELDS + 1)), *rho = B.get(4 * (size_t)L), *eb = B.get(4 * n_blk), *coef = B.get(4 * roots.size());
     uint32_t *d_num = B.get(NL), *d_den = B.get(4 * NL), *partial = B.get(4 * S.n_bus * AS_CLAIM_NB);
     AsBlock* d_blk = (AsBlock*)B.get((n_blk + 1) * sizeof(AsBlock) / 4);
     AsBlockPos* d_pos = (AsBlockPos*)B.get(n_blk * sizeof(AsBlockPos) / 4);
     AsRoot* d_roots = (AsRoot*)B.get(roots.size() * sizeof(AsRoot) / 4);
     AsClaim* d_cl = (AsClaim*)B.get(S.n_bus * sizeof(AsClaim) / 4);
-    if (!dP || !d_obs || !d_up || !ch || !lchal || !rho || !eb || !coef || !d_num || !d_den || !partial || !d_blk || !d_pos || !d_roots || !d_cl)
+    if (!d_up || !ch || !lchal || !rho || !eb || !coef || !d_num || !d_den || !partial || !d_blk || !d_pos || !d_roots || !d_cl)
         return set_error(ctx, ZKHIP_ERR_NOMEM, "airset: the leaves do not fit");
     // one eq(rho[0..m), .) table per distinct height of an AIR with interactions
     std::map<unsigned, uint32_t*> eq_of;
@@ -319,15 +313,11 @@ int as_prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs
     std::vector<AsClaim> hcl;
     for (size_t a = 0; a < n_airs; a++)
         if (!S.plans[a].prog.ints.empty()) hcl.push_back({eq_of[S.plans[a].m], S.plans[a].m, (uint32_t)ids_at[a], (uint32_t)S.plans[a].prog.ints.size()});
-    std::vector<uint32_t> obs(root, root + 8);
-    for (size_t a = 0; a < n_airs; a++) obs.insert(obs.end(), pvs[a], pvs[a] + airs[a].n_pvs);
-    ZK_TRY(zkhip_h2d(ctx, d_obs, obs.data(), obs.size() * 4));
     ZK_TRY(zkhip_h2d(ctx, d_up, up.data(), up.size() * 4));
     ZK_TRY(zkhip_h2d(ctx, d_blk, hb.data(), hb.size() * sizeof(AsBlock)));
     ZK_TRY(zkhip_h2d(ctx, d_pos, hpos.data(), hpos.size() * sizeof(AsBlockPos)));
     ZK_TRY(zkhip_h2d(ctx, d_roots, roots.data(), roots.size() * sizeof(AsRoot)));
     ZK_TRY(zkhip_h2d(ctx, d_cl, hcl.data(), hcl.size() * sizeof(AsClaim)));
-    ZK_TRY(transcript_observe(ctx, d_t, d_obs, (uint32_t)obs.size(), true));
     // 2. gamma, beta   3. the leaves
     ZK_TRY(transcript_sample(ctx, d_t, ch, nullptr, 4));
     ZK_TRY(transcript_sample(ctx, d_t, ch + 4, nullptr, 4));
@@ -371,12 +361,53 @@ int as_prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs
     }
     ZK_HIP_CHECK(ctx, hipGetLastError());
     ZK_TRY(transcript_observe(ctx, d_t, dB, (uint32_t)(4 * S.n_bus), true));
+    for (size_t a = 0; a < n_airs; a++)
+        if (!S.plans[a].prog.ints.empty()) (*bus)[a] = ZcBus{eq_of[S.plans[a].m], coef + 4 * root_at[a]};
+    return ZKHIP_OK;
+}
+
+// either proof: with_bus, the AIR-set proof of docs/airset.md (its step numbers below); without, the zero-check of docs/zerocheck.md
+int prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
+          const uint32_t* const* pvs, unsigned l, bool with_bus, DevTranscript* d_t, uint32_t* proof_out, size_t cap, uint32_t* root_out) {
+    const std::string who = with_bus ? "airset: " : "zerocheck: ";
+    Shape S;
+    if (!shape(prm, airs, n_airs, l, with_bus, &S)) return set_error(ctx, ZKHIP_ERR_INVALID, who + "the shape does not fit the limits");
+    if (cap < S.total) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, who + "proof buffer too small");
+    size_t n_pv = 0, pt_words = 0;
+    for (size_t a = 0; a < n_airs; a++) {
+        if (!d_traces[a] || (airs[a].n_pvs && !pvs[a])) return set_error(ctx, ZKHIP_ERR_INVALID, who + "null trace or public values");
+        for (size_t i = 0; i < airs[a].n_pvs; i++)
+            if (pvs[a][i] >= P) return set_error(ctx, ZKHIP_ERR_INVALID, who + "public value not canonical");
+        n_pv += airs[a].n_pvs, pt_words += 4 * (size_t)airs[a].log_height;
+    }
+    // 1. commit: every main column, AIRs in caller order
+    std::vector<const uint32_t*> cols;
+    for (size_t a = 0; a < n_airs; a++)
+        for (size_t c = 0; c < airs[a].width; c++) cols.push_back(d_traces[a] + (c << airs[a].log_height));
+    struct Com {
+        zkhip_ctx* ctx;
+        zkhip_stack_commitment* sc = nullptr;
+        ~Com() { stack_destroy(ctx, sc); }
+    } com{ctx};
+    uint32_t root[8];
+    ZK_TRY(stack_commit(ctx, prm, cols.data(), S.lh.data(), cols.size(), l, &com.sc, root));
+    DevBufs B(ctx);
+    // device: [the words before the opening | the points r'_a (Montgomery)], then the root and the public values to observe
+    uint32_t *dP = B.get(S.head + pt_words), *d_obs = B.get(8 + n_pv);
+    if (!dP || !d_obs) return set_error(ctx, ZKHIP_ERR_NOMEM, who + "proof staging");
+    std::vector<uint32_t> obs(root, root + 8);
+    for (size_t a = 0; a < n_airs; a++) obs.insert(obs.end(), pvs[a], pvs[a] + airs[a].n_pvs);
+    ZK_TRY(zkhip_h2d(ctx, d_obs, obs.data(), obs.size() * 4));
+    ZK_TRY(transcript_observe(ctx, d_t, d_obs, (uint32_t)obs.size(), true));
+    // 2. - 5. the bus part
+    std::vector<ZcBus> bus(n_airs);   // E2 null: an AIR without interactions, or the zero-check
+    if (with_bus) ZK_TRY(prove_bus(ctx, S, airs, n_airs, d_traces, pvs, d_t, B, dP, &bus));
     // 6. - 8. per AIR
     size_t off = 8 + S.gkr_words + 4 * S.n_bus, poff = S.head;
     for (size_t a = 0; a < n_airs; a++) {
         const ZcPlan& pl = S.plans[a];
-        if (pl.prog.ints.empty()) ZK_TRY(zc_prove_air<false>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff));
-        else ZK_TRY(zc_prove_air<true>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff, ZcBus{eq_of[pl.m], coef + 4 * root_at[a]}));
+        if (bus[a].E2) ZK_TRY(zc_prove_air<true>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff, bus[a]));
+        else ZK_TRY(zc_prove_air<false>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff));
         off += pl.active() ? pl.words() : 0;
         poff += 4 * (size_t)pl.m;
     }
@@ -392,40 +423,11 @@ int as_prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs
 }
 
 // ---- the host verifier ---------------------------------------------------------------------------------------------------------
-// sum_j (cc_j count_j + sum_i cf_{j,i} f_{j,i}) on the column values v; coef in pl.bus_roots' order
-Ext as_bus_eval_host(const ZcPlan& pl, const Ext* v, const uint32_t* pvs, const Ext* coef) {
-    const AirProgram& g = pl.prog;
-    std::vector<char> reach(g.n_nodes, 0);
-    for (uint32_t r : pl.bus_roots) reach[r] = 1;
-    for (uint32_t i = g.n_nodes; i-- > 0;) {
-        const uint32_t op = g.nodes[3 * i];
-        if (!reach[i] || op < A_ADD || op > A_NEG) continue;
-        reach[g.nodes[3 * i + 1]] = 1;
-        if (op != A_NEG) reach[g.nodes[3 * i + 2]] = 1;
-    }
-    std::vector<Ext> val(g.n_nodes, ext_zero());
-    for (uint32_t i = 0; i < g.n_nodes; i++) {
-        if (!reach[i]) continue;
-        const uint32_t op = g.nodes[3 * i], x = g.nodes[3 * i + 1], y = g.nodes[3 * i + 2];
-        switch (op) {   // parse_air: operands of the current row only
-            case A_VAR: val[i] = v[x]; break;
-            case A_PUB: val[i] = ext_from_base(to_monty(pvs[x])); break;
-            case A_CONST: val[i] = ext_from_base(to_monty(x)); break;
-            case A_ADD: val[i] = ext_add(val[x], val[y]); break;
-            case A_SUB: val[i] = ext_sub(val[x], val[y]); break;
-            case A_MUL: val[i] = ext_mul(val[x], val[y]); break;
-            default: val[i] = ext_neg(val[x]);
-        }
-    }
-    Ext acc = ext_zero();
-    for (size_t k = 0; k < pl.bus_roots.size(); k++) acc = ext_add(acc, ext_mul(coef[k], val[pl.bus_roots[k]]));
-    return acc;
-}
-
-int as_verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
-              const uint32_t* const* pvs, unsigned l, const uint32_t* proof, size_t words, uint32_t* root_out, uint32_t* pq_out) {
-    AsShape S;
-    if (!as_shape(prm, airs, n_airs, l, &S)) return ZKHIP_ERR_INVALID;
+// of either proof; pq_out: the fraction sum's (P, Q), with_bus only
+int verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs, const uint32_t* const* pvs,
+           unsigned l, const uint32_t* proof, size_t words, bool with_bus, uint32_t* root_out, uint32_t* pq_out) {
+    Shape S;
+    if (!shape(prm, airs, n_airs, l, with_bus, &S)) return ZKHIP_ERR_INVALID;
     for (size_t a = 0; a < n_airs; a++) {
         if (airs[a].n_pvs && !pvs[a]) return ZKHIP_ERR_INVALID;
         for (size_t i = 0; i < airs[a].n_pvs; i++)
@@ -441,53 +443,53 @@ int as_verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_pre
     ch.observe_canon(proof, 8);
     for (size_t a = 0; a < n_airs; a++) ch.observe_canon(pvs[a], airs[a].n_pvs);
     const Ext one = ext_one();
-    const unsigned L = S.L;
-    // 2. - 4. gamma, beta, the fraction-sum proof: rho, (p*, q*), balance
-    const Ext gamma = ch.sample_ext(), beta = ch.sample_ext();
-    std::vector<uint32_t> pt(4 * (size_t)L);
-    uint32_t cl8[8];
-    Ext pq[2];
-    ZK_TRY(gkr_verify_host(ch, proof + 8, S.gkr_words, L, pt.data(), cl8, pq));
-    if (!ext_eq(pq[0], ext_zero()) || ext_eq(pq[1], ext_zero())) return ZKHIP_ERR_VERIFY;
-    std::vector<Ext> rho(L);
-    for (unsigned j = 0; j < L; j++) rho[j] = ext_from_canon(pt.data() + 4 * j);
-    const Ext pstar = ext_from_canon(cl8), qstar = ext_from_canon(cl8 + 4);
-    // 5. the leaf claims
     const size_t n_blk = S.blocks.size();
-    std::vector<Ext> eb(n_blk);
-    Ext pad = one;
-    for (size_t b = 0; b < n_blk; b++) {
-        const AsBlk& k = S.blocks[b];
-        Ext e = one;
-        for (unsigned t = 0; k.m + t < L; t++) e = ext_mul(e, ((k.off >> k.m) >> t) & 1u ? rho[k.m + t] : ext_sub(one, rho[k.m + t]));
-        eb[b] = e, pad = ext_sub(pad, e);
-    }
-    const Ext kappa = ch.sample_ext();
-    const uint32_t* q = proof + 8 + S.gkr_words;
-    Ext lhs = ext_mul(kappa, pad);
-    for (size_t i = 0; i < S.n_bus; i++) lhs = ext_add(lhs, ext_from_canon(q + 4 * i));
-    ch.observe_canon(q, 4 * S.n_bus);
-    if (!ext_eq(lhs, ext_add(pstar, ext_mul(kappa, qstar)))) return ZKHIP_ERR_VERIFY;
-    const uint32_t* qB = q;
-    q += 4 * S.n_bus;
-    std::vector<Ext> bpow(LOGUP_MAX_FIELDS + 1);
-    bpow[0] = one;
-    for (unsigned i = 1; i <= LOGUP_MAX_FIELDS; i++) bpow[i] = ext_mul(bpow[i - 1], beta);
+    const uint32_t *q = proof + 8, *qB = nullptr;   // qB: the leaf claims B_a
+    Ext gamma = ext_zero(), kappa = ext_zero();
+    std::vector<Ext> rho(S.L), eb(n_blk), bpow(LOGUP_MAX_FIELDS + 1, one);
     std::vector<std::vector<size_t>> blk_of(n_airs);   // AIR -> its blocks in program order
-    for (size_t a = 0; a < n_airs; a++) blk_of[a].resize(S.plans[a].prog.ints.size());
-    for (size_t b = 0; b < n_blk; b++) blk_of[S.blocks[b].a][S.blocks[b].j] = b;
-    std::vector<uint32_t> points;
-    std::vector<const uint32_t*> claimed(n_airs, nullptr);
+    if (with_bus) {
+        // 2. - 4. gamma, beta, the fraction-sum proof: rho, (p*, q*), balance
+        gamma = ch.sample_ext();
+        const Ext beta = ch.sample_ext();
+        std::vector<uint32_t> pt(4 * (size_t)S.L);
+        uint32_t cl8[8];
+        Ext pq[2];
+        ZK_TRY(gkr_verify_host(ch, q, S.gkr_words, S.L, pt.data(), cl8, pq));
+        if (!ext_eq(pq[0], ext_zero()) || ext_eq(pq[1], ext_zero())) return ZKHIP_ERR_VERIFY;
+        for (unsigned j = 0; j < S.L; j++) rho[j] = ext_from_canon(pt.data() + 4 * j);
+        const Ext pstar = ext_from_canon(cl8), qstar = ext_from_canon(cl8 + 4);
+        // 5. the leaf claims
+        Ext pad = one;
+        for (size_t b = 0; b < n_blk; b++) {
+            const AsBlk& k = S.blocks[b];
+            Ext e = one;
+            for (unsigned t = 0; k.m + t < S.L; t++) e = ext_mul(e, ((k.off >> k.m) >> t) & 1u ? rho[k.m + t] : ext_sub(one, rho[k.m + t]));
+            eb[b] = e, pad = ext_sub(pad, e);
+        }
+        kappa = ch.sample_ext();
+        qB = q + S.gkr_words;
+        Ext lhs = ext_mul(kappa, pad);
+        for (size_t i = 0; i < S.n_bus; i++) lhs = ext_add(lhs, ext_from_canon(qB + 4 * i));
+        ch.observe_canon(qB, 4 * S.n_bus);
+        if (!ext_eq(lhs, ext_add(pstar, ext_mul(kappa, qstar)))) return ZKHIP_ERR_VERIFY;
+        q = qB + 4 * S.n_bus;
+        for (unsigned i = 1; i <= LOGUP_MAX_FIELDS; i++) bpow[i] = ext_mul(bpow[i - 1], beta);
+        for (size_t a = 0; a < n_airs; a++) blk_of[a].resize(S.plans[a].prog.ints.size());
+        for (size_t b = 0; b < n_blk; b++) blk_of[S.blocks[b].a][S.blocks[b].j] = b;
+    }
+    std::vector<uint32_t> points;                            // r'_a, canonical, end to end
+    std::vector<const uint32_t*> claimed(n_airs, nullptr);   // the w values the opening must show (null: none claimed)
     for (size_t a = 0; a < n_airs; a++) {
         const ZcPlan& pl = S.plans[a];
         const unsigned m = pl.m, D = pl.D;
         const size_t w = pl.w, n_rot = pl.rot.size();
-        const bool has_cons = !pl.proven.empty(), has_bus = !pl.prog.ints.empty();
+        const bool has_cons = !pl.proven.empty(), has_bus = !pl.bus_roots.empty();   // the zero-check's plans have no bus roots
         std::vector<Ext> rp(m);
         if (!pl.active()) {
             for (unsigned j = 0; j < m; j++) rp[j] = ch.sample_ext();
         } else {
-            // 6. the joint sum-check
+            // 6. the (joint) sum-check
             std::vector<Ext> tau(m), r(m), coef;
             Ext alpha = ext_zero(), claim = ext_zero();
             if (has_cons) {
@@ -522,13 +524,22 @@ int as_verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_pre
             ch.observe_canon(q, 4 * (w + n_rot));
             const uint32_t* qv = q;
             q += 4 * (w + n_rot);
+            Ext first = one, last = one;
+            for (unsigned j = 0; j < m; j++) first = ext_mul(first, ext_sub(one, r[j])), last = ext_mul(last, r[j]);
             Ext rhs = ext_zero();
-            if (has_cons) {
-                Ext first = one, last = one;
-                for (unsigned j = 0; j < m; j++) first = ext_mul(first, ext_sub(one, r[j])), last = ext_mul(last, r[j]);
-                rhs = ext_mul(eq_eval(tau.data(), r.data(), m), zc_eval_host(pl, v.data(), vn.data(), first, last, pvs[a], alpha));
+            if (has_cons) {   // eq(tau, r) sum_k alpha^k C_k
+                const std::vector<Ext> val = zc_eval_host(pl, pl.reach, v.data(), vn.data(), first, last, pvs[a]);
+                Ext c = ext_zero(), ap = one;
+                for (uint32_t k : pl.proven) c = ext_add(c, ext_mul(ap, val[k])), ap = ext_mul(ap, alpha);
+                rhs = ext_mul(eq_eval(tau.data(), r.data(), m), c);
             }
-            if (has_bus) rhs = ext_add(rhs, ext_mul(eq_eval(rho.data(), r.data(), m), as_bus_eval_host(pl, v.data(), pvs[a], coef.data())));
+            if (has_bus) {   // eq(rho_a, r) sum_j (cc_j count_j + sum_i cf_{j,i} f_{j,i}), coef in pl.bus_roots' order
+                // parse_air: interaction operands read the current row only, so neither v' nor first / last enters
+                const std::vector<Ext> val = zc_eval_host(pl, pl.bus_reach, v.data(), vn.data(), first, last, pvs[a]);
+                Ext c = ext_zero();
+                for (size_t k = 0; k < coef.size(); k++) c = ext_add(c, ext_mul(coef[k], val[pl.bus_roots[k]]));
+                rhs = ext_add(rhs, ext_mul(eq_eval(rho.data(), r.data(), m), c));
+            }
             if (!ext_eq(rhs, claim)) return ZKHIP_ERR_VERIFY;
             // 8. the rotation reduction
             if (n_rot == 0) {
@@ -571,6 +582,11 @@ int as_verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_pre
     if (pq_out) memcpy(pq_out, proof + 8, 32);
     return ZKHIP_OK;
 }
+
+size_t proof_words(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus) {
+    Shape S;
+    return shape(prm, airs, n_airs, l, with_bus, &S) ? S.total : 0;
+}
 }  // namespace
 
 }  // namespace zk
@@ -579,9 +595,20 @@ using namespace zk;
 
 extern "C" {
 
+size_t zkhip_zerocheck_proof_words(const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, unsigned log_stack) {
+    return proof_words(params, airs, n_airs, log_stack, false);
+}
+
 size_t zkhip_airset_proof_words(const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, unsigned log_stack) {
-    AsShape S;
-    return as_shape(params, airs, n_airs, log_stack, &S) ? S.total : 0;
+    return proof_words(params, airs, n_airs, log_stack, true);
+}
+
+int zkhip_zerocheck_prove(zkhip_ctx* ctx, const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
+                          const uint32_t* const* pvs, unsigned log_stack, zkhip_transcript* transcript, uint32_t* proof_out, size_t cap,
+                          uint32_t* root_out) {
+    ZK_BIND_DEVICE(ctx);
+    if (!ctx || !params || !airs || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
+    return prove(ctx, params, airs, n_airs, d_traces, pvs, log_stack, false, transcript->d, proof_out, cap, root_out);
 }
 
 int zkhip_airset_prove(zkhip_ctx* ctx, const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
@@ -589,14 +616,20 @@ int zkhip_airset_prove(zkhip_ctx* ctx, const zkhip_whir_params* params, const zk
                        uint32_t* root_out) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !params || !airs || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
-    return as_prove(ctx, params, airs, n_airs, d_traces, pvs, log_stack, transcript->d, proof_out, cap, root_out);
+    return prove(ctx, params, airs, n_airs, d_traces, pvs, log_stack, true, transcript->d, proof_out, cap, root_out);
+}
+
+int zkhip_zerocheck_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
+                           const uint32_t* const* pvs, unsigned log_stack, const uint32_t* proof, size_t words, uint32_t* root_out) {
+    if (!params || (n_prefix && !prefix) || !airs || !pvs || !proof) return ZKHIP_ERR_INVALID;
+    return verify(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, false, root_out, nullptr);
 }
 
 int zkhip_airset_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
                         const uint32_t* const* pvs, unsigned log_stack, const uint32_t* proof, size_t words, uint32_t* root_out,
                         uint32_t* pq_out) {
     if (!params || (n_prefix && !prefix) || !airs || !pvs || !proof) return ZKHIP_ERR_INVALID;
-    return as_verify(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, root_out, pq_out);
+    return verify(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, true, root_out, pq_out);
 }
 
 }  // extern "C"

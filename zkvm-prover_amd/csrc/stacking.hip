@@ -199,23 +199,6 @@ StackLayout stack_layout(const zkhip_whir_params* prm, const unsigned* lh, size_
     return L;
 }
 
-// device buffers of one call, freed (after the stream drains) on every exit
-struct StackBufs {
-    std::vector<void*> bufs;
-    zkhip_ctx* ctx;
-    explicit StackBufs(zkhip_ctx* c) : ctx(c) {}
-    uint32_t* get(size_t words) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(words, 4) * 4) != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        return (uint32_t*)p;
-    }
-    ~StackBufs() {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (void* p : bufs) (void)hipFree(p);
-    }
-};
-
 // the points and the columns' claims of an opening: checks every shape rule; eofs[p] = first entry of point p's eq table (used points)
 struct StackClaims {
     bool ok = false;
@@ -277,7 +260,7 @@ int stack_commit(zkhip_ctx* ctx, const zkhip_whir_params* prm, const uint32_t* c
     const size_t N = lay.n_stack << l;
     int rc = ZKHIP_OK;
     {
-        StackBufs B(ctx);
+        DevBufs B(ctx);
         uint32_t* d_src = B.get(2 * n_cols);
         if (!d_src || hipMalloc(&sc->d_mat, N * 4) != hipSuccess) rc = set_error(ctx, ZKHIP_ERR_NOMEM, "stack: commitment buffers");
         std::vector<const uint32_t*> src(n_cols);
@@ -323,7 +306,7 @@ int stack_open(zkhip_ctx* ctx, zkhip_stack_commitment* sc, DevTranscript* d_t, c
         hc[j] = StackCol{lay.off[j], lay.pos[j], sc->heights[j]};
         he[lay.pos[j]] = C.eofs[col_point[j]];
     }
-    StackBufs B(ctx);
+    DevBufs B(ctx);
     uint32_t *d_up = B.get(up.size()), *E = B.get(4 * C.e_total), *vpart = B.get(4 * (n_chunks + n_cols)), *partial = B.get(8 * (size_t)SC_NB);
     uint32_t *coef = B.get(4 * n_cols), *dP = B.get(head + 4 * (size_t)l + 4), *fA = B.get(2 * N), *wA = B.get(2 * N), *fB = B.get(N), *wB = B.get(N);
     if (!d_up || !E || !vpart || !partial || !coef || !dP || !fA || !wA || !fB || !wB) return set_error(ctx, ZKHIP_ERR_NOMEM, "stack: opening buffers");

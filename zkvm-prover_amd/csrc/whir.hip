@@ -335,27 +335,6 @@ void whir_destroy(zkhip_ctx* ctx, zkhip_whir_commitment* com) {
     delete com;
 }
 
-namespace {
-// device buffers of one opening, freed on every exit
-struct WhirOpenBufs {
-    std::vector<void*> bufs;
-    std::vector<zkhip_tree*> trees;
-    zkhip_ctx* ctx;
-    explicit WhirOpenBufs(zkhip_ctx* c) : ctx(c) {}
-    uint32_t* get(size_t words) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(words, 4) * 4) != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        return (uint32_t*)p;
-    }
-    ~WhirOpenBufs() {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (zkhip_tree* t : trees) zkhip_tree_destroy(ctx, t);
-        for (void* p : bufs) (void)hipFree(p);
-    }
-};
-}  // namespace
-
 int whir_open_device(zkhip_ctx* ctx, zkhip_whir_commitment* com, DevTranscript* d_t, const uint32_t* point, uint32_t* values_out,
                      uint32_t* proof_out, size_t cap) {
     const zkhip_whir_params* prm = &com->params;
@@ -369,7 +348,16 @@ int whir_open_device(zkhip_ctx* ctx, zkhip_whir_commitment* com, DevTranscript* 
     unsigned max_q = 0;
     for (unsigned i = 0; i < sh.R; i++) max_q = std::max(max_q, prm->num_queries[i]);
     const unsigned ln1 = m + b - 1;   // the largest later codeword
-    WhirOpenBufs B(ctx);
+    DevBufs B(ctx);
+    // the later codewords' trees: declared after B, so destroyed after the stream drains and before B frees the matrices under them
+    struct Trees {
+        zkhip_ctx* ctx;
+        std::vector<zkhip_tree*> list;
+        ~Trees() {
+            (void)hipStreamSynchronize(ctx->stream);
+            for (zkhip_tree* t : list) zkhip_tree_destroy(ctx, t);
+        }
+    } trees{ctx};
     uint32_t *fA = B.get(4 * n), *wA = B.get(4 * n), *fB = B.get(2 * n), *wB = B.get(2 * n), *cA = B.get(4 * n), *cB = B.get(4 * (n >> k));
     uint32_t *ntt = sh.R > 1 ? B.get(4 * ((size_t)1 << ln1)) : nullptr;
     uint32_t *mat[2] = {sh.R > 1 ? B.get(4 * ((size_t)1 << ln1)) : nullptr, sh.R > 2 ? B.get(4 * ((size_t)1 << (ln1 - 1))) : nullptr};
@@ -476,7 +464,7 @@ int whir_open_device(zkhip_ctx* ctx, zkhip_whir_commitment* com, DevTranscript* 
             }
             zkhip_matrix mx{mt, Nn >> k, ln - 1 - k, (size_t)4 << k};
             ZK_TRY(zkhip_merkle_commit(ctx, &mx, 1, &next, nullptr));
-            B.trees.push_back(next);
+            trees.list.push_back(next);
             ZK_HIP_CHECK(ctx, hipMemcpyAsync(dP + L.mid[i], zkhip_tree_root_device(next), 32, hipMemcpyDeviceToDevice, st));
             ZK_TRY(convert_repr(ctx, dP + L.mid[i], 8, false));
             ZK_TRY(transcript_observe(ctx, d_t, dP + L.mid[i], 8, true));

@@ -1,6 +1,6 @@
-// zerocheck_dev.hpp -- what the AIR zero-check (zerocheck.hip, docs/zerocheck.md) and the AIR-set proof (airset.hip, docs/airset.md)
-// share: the plan of one AIR, the sum-check kernels over the lowered constraint program, the rotation reduction, one AIR's device
-// prover (zc_prove_air) and the host evaluation of the constraints.
+// zerocheck_dev.hpp -- the per-AIR part of the AIR zero-check (docs/zerocheck.md) and the AIR-set proof (docs/airset.md), included
+// by airset.hip alone, which holds the host side of both: the plan of one AIR, the sum-check kernels over the lowered constraint
+// program, the rotation reduction, one AIR's device prover (zc_prove_air) and the host evaluation of a plan's nodes.
 //
 // The constraint kernels have a compile-time BUS form for the AIR-set proof: a second eq table (eq(rho_a, .)) and a second
 // coefficient set; an ASSERT whose number is at or above n_cons adds to a second combination, which the second eq factor multiplies.
@@ -304,12 +304,13 @@ struct ZcPlan {
     std::vector<char> reach;        // nodes the proven constraints reach
     // the AIR-set proof only (zc_plan with_bus): the roots of the bus part, per interaction its count node, then its field nodes
     std::vector<uint32_t> bus_roots;
+    std::vector<char> bus_reach;    // nodes the bus roots reach
     bool active() const { return D > 0; }
     size_t words() const { return 4 * (size_t)D * m + 4 * w + 4 * rot.size() + (rot.empty() ? 0 : 8 * (size_t)m + 4 * w); }
 };
 
 // with_bus: D = max(d_cons, d_bus) + 1 over the parts that exist, d_bus the largest degree of a count or field node
-bool zc_plan(const zkhip_air& a, ZcPlan* p, bool with_bus = false) {
+bool zc_plan(const zkhip_air& a, ZcPlan* p, bool with_bus) {
     if (!a.program || a.width < 1 || a.log_height < 1 || a.log_height > ZKHIP_WHIR_MAX_LOG_N) return false;
     if (parse_air(a.program, a.program_len, a.width, &p->prog, nullptr) != 0) return false;
     const AirProgram& g = p->prog;
@@ -368,30 +369,19 @@ bool zc_plan(const zkhip_air& a, ZcPlan* p, bool with_bus = false) {
             for (uint32_t i = 0; i < it.n_fields; i++) p->bus_roots.push_back(it.fields[i]), d_bus = std::max(d_bus, deg[it.fields[i]]);
         }
         p->D = std::max(p->D, d_bus + 1);
+        p->bus_reach.assign(g.n_nodes, 0);
+        for (uint32_t r : p->bus_roots) p->bus_reach[r] = 1;
+        for (uint32_t i = g.n_nodes; i-- > 0;) {
+            const uint32_t op = g.nodes[3 * i];
+            if (!p->bus_reach[i] || op < A_ADD || op > A_NEG) continue;
+            p->bus_reach[g.nodes[3 * i + 1]] = 1;
+            if (op != A_NEG) p->bus_reach[g.nodes[3 * i + 2]] = 1;
+        }
     }
     return p->D <= ZKHIP_ZEROCHECK_MAX_DEGREE;
 }
 
 // ---- the device prover ---------------------------------------------------------------------------------------------------------
-struct ZcBufs {
-    std::vector<void*> bufs;
-    zkhip_ctx* ctx;
-    explicit ZcBufs(zkhip_ctx* c) : ctx(c) {}
-    uint32_t* get(size_t words) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(words, 4) * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        bufs.push_back(p);
-        return (uint32_t*)p;
-    }
-    ~ZcBufs() {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (void* p : bufs) (void)hipFree(p);
-    }
-};
-
 template <unsigned D, bool BUS>
 void zc_launch_d(hipStream_t st, int which, unsigned grid, size_t lds, const ZcProg& pg, const ZcTabs& tb, const uint32_t* r, uint32_t* partial,
                  DevTranscript* d_t, uint32_t* proof, uint32_t* r_out) {
@@ -450,7 +440,7 @@ int zc_prove_air(zkhip_ctx* ctx, DevTranscript* d_t, const ZcPlan& pl, const uin
     std::copy(ca.consts.begin(), ca.consts.end(), hp), hp += ca.consts.size();
     for (uint32_t i = 0; i < pl.prog.n_pvs; i++) *hp++ = to_monty(pvs[i]);
     std::copy(pl.rot.begin(), pl.rot.end(), hp);
-    ZcBufs B(ctx);
+    DevBufs B(ctx);
     // challenges: [tau (4 m) | alpha (4) | r (4 m) | lambda (4)]
     uint32_t *d_up = B.get(up.size()), *ch = B.get(8 * (size_t)m + 8), *apow = B.get(4 * (size_t)std::max(n_cons, w + n_rot));
     uint32_t *E = B.get(4 * n), *partial = B.get(4 * (size_t)ZKHIP_ZEROCHECK_MAX_DEGREE * SC_NB);
@@ -594,12 +584,13 @@ Ext zc_rot_eval(const Ext* a, const Ext* b, unsigned m) {
     return acc;
 }
 
-// sum_k alpha^k C_k on (v, v', first, last, pvs)
-Ext zc_eval_host(const ZcPlan& pl, const Ext* v, const Ext* vn, const Ext& first, const Ext& last, const uint32_t* pvs, const Ext& alpha) {
+// the nodes marked in `reach` (pl.reach or pl.bus_reach) on (v, v', first, last, pvs); the others stay 0
+std::vector<Ext> zc_eval_host(const ZcPlan& pl, const std::vector<char>& reach, const Ext* v, const Ext* vn, const Ext& first, const Ext& last,
+                              const uint32_t* pvs) {
     const AirProgram& g = pl.prog;
     std::vector<Ext> val(g.n_nodes, ext_zero());
     for (uint32_t i = 0; i < g.n_nodes; i++) {
-        if (!pl.reach[i]) continue;
+        if (!reach[i]) continue;
         const uint32_t op = g.nodes[3 * i], x = g.nodes[3 * i + 1], y = g.nodes[3 * i + 2];
         switch (op) {
             case A_VAR:
@@ -633,9 +624,7 @@ Ext zc_eval_host(const ZcPlan& pl, const Ext* v, const Ext* vn, const Ext& first
                 val[i] = ext_neg(val[x]);
         }
     }
-    Ext acc = ext_zero(), ap = ext_one();
-    for (uint32_t c : pl.proven) acc = ext_add(acc, ext_mul(ap, val[c])), ap = ext_mul(ap, alpha);
-    return acc;
+    return val;
 }
 
 }  // namespace

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <atomic>
 #include <map>
 #include <string>
@@ -132,6 +133,26 @@ struct KernelScope {
     zkhip_ctx* ctx;
     KernelScope(zkhip_ctx* c, const char* name) : ctx(c) { profile_begin(ctx, name); }
     ~KernelScope() { profile_end(ctx); }
+};
+
+// device buffers of one call, freed (after the context's stream drains) on every exit
+struct DevBufs {
+    std::vector<void*> bufs;
+    zkhip_ctx* ctx;
+    explicit DevBufs(zkhip_ctx* c) : ctx(c) {}
+    uint32_t* get(size_t words) {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(words, 4) * 4) != hipSuccess) {
+            (void)hipGetLastError();   // or a later ZK_HIP_CHECK(hipGetLastError()) reports this stale out-of-memory error
+            return nullptr;
+        }
+        bufs.push_back(p);
+        return (uint32_t*)p;
+    }
+    ~DevBufs() {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void* p : bufs) (void)hipFree(p);
+    }
 };
 
 // ---- kernels / stages implemented across the .hip files --------------------------------------
