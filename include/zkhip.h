@@ -1130,7 +1130,8 @@ typedef struct {
     uint32_t quot_streams;
     /* body of the transform passes.  0 (the default): passes of the two-pass 2^22-point transform (2^11 rows x 8 columns, both digits eleven
      * bits: every pass of the flagship's LDEs) run k_ntt_pass4_ct_sq, whose shape is a compile-time constant and whose HBM reads are all
-     * issued before its first wait; every other pass runs the run-time-shaped k_ntt_pass4_ct.  1: k_ntt_pass4_ct for every shape (the body
+     * issued before its first wait; every other pass runs k_ntt_pass4_ct (one instantiation per tile shape) or, for the short passes of
+     * 2^12 and 2^13 points that no such shape covers, the run-time-shaped k_ntt_pass4.  1: k_ntt_pass4_ct for those passes too (the body
      * of rounds 1 - 6, kept for the A/B and for tests/test_gpu_ntt_pass_forms.py).  2: the radix-2 passes k_ntt_dif_pass and the
      * bit-reversal scaling of the LDE for EVERY size (the slow reference form of the same test; transforms of several matrices' columns as
      * one batch keep form 1) [ZKHIP_NTT_PASS_FORM] */

@@ -2,8 +2,10 @@
 
 * form 0 (the default): k_ntt_pass4_ct_sq -- shape and mode as compile-time constants, every HBM read of a tile issued before the first
   wait -- for the passes of the two-pass 2^22-point transform (plain, input twiddle
-  and bit-reversed scaled source: every pass of the flagship's LDEs); k_ntt_pass4_ct for every other shape;
-* form 1: k_ntt_pass4_ct everywhere, the body of rounds 1 - 6;
+  and bit-reversed scaled source: every pass of the flagship's LDEs); for every other pass k_ntt_pass4_ct, one instantiation per tile
+  shape, or the run-time-shaped k_ntt_pass4 where no instantiation fits (both passes of 2^12 points, the second pass of 2^13 points,
+  and its first pass at 1024 lanes);
+* form 1: k_ntt_pass4_ct for the passes of the 2^22-point transform too, the body of rounds 1 - 6;
 * form 2: the radix-2 passes k_ntt_dif_pass and the bit-reversal scaling, at every size.
 
 Every pass shape the dispatcher can choose is run: transforms of 2^12 .. 2^24 points (two and three passes, tiles of 2^7 .. 2^11 rows) under

@@ -181,9 +181,6 @@ struct Pass4Args {
     // src + col * src_col_stride (first pass of a transform) / dst + col * dst_col_stride (last pass)
     const uint32_t* const* src_cols;
     uint32_t* const* dst_cols;
-    // wave priority of the pass (s_setprio; experiment ZKHIP_NTT_PRIO=1..3): a pass beside another proof's row sponge issues its few VALU
-    // bursts ahead of the sponge's waves instead of taking turns with them
-    unsigned prio;
 };
 
 template <int Q>
@@ -229,14 +226,18 @@ __device__ __forceinline__ void lds_round(uint32_t* lv, const uint32_t* twl, uns
     }
 }
 
-// LOG_R / LOG_C != 0 fix the tile shape at compile time (address arithmetic folds, loops unroll);
-// <0,0> is the generic runtime-shaped variant.
-template <int LOG_R, int LOG_C>
+// The run-time-shaped pass: the tile shape comes from the arguments.  It serves the passes that no compile-time shape below covers
+// (see pass4_kernel_for: no table entry matches), which are the short ones of the two smallest four-step sizes:
+//  * 2^12 points, both passes: [2^6 x 16] tiles, 64 lanes;
+//  * 2^13 points, second pass: [2^6 x 16] tiles, 64 lanes;
+//  * 2^13 points, first pass at ntt_log_lanes = 10: 2^7 rows want 128 columns and the pass has only 2^6 -- [2^7 x 64] tiles, 512 lanes
+//    (at 9 / 8 lanes the [2^7 x 64] / [2^7 x 32] tile is a compile-time shape).
+// Every pass of 2^14 points and more has at least 2^7 rows and at least as many columns as its tile wants.
 __global__ __launch_bounds__(1024) void k_ntt_pass4(Pass4Args a) {
     extern __shared__ uint32_t sm[];
-    const unsigned log_r = LOG_R ? (unsigned)LOG_R : a.log_r;
+    const unsigned log_r = a.log_r;
     const unsigned R = 1u << log_r;
-    const unsigned log_c = LOG_C ? (unsigned)LOG_C : a.log_c, C = 1u << log_c, cmask = C - 1u, pitch = C + 1u;
+    const unsigned log_c = a.log_c, C = 1u << log_c, cmask = C - 1u, pitch = C + 1u;
     uint32_t* lv = sm;
     uint32_t* twl = sm + R * pitch;
     const unsigned tid = threadIdx.x, nt = blockDim.x;
@@ -332,8 +333,8 @@ __global__ __launch_bounds__(1024) void k_ntt_pass4(Pass4Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Compile-time shaped variant of the pass kernel for the two tile shapes every transform >= 2^20
-// uses ([2^11 x 8] and [2^10 x 16], 1024 lanes).  Same data flow as k_ntt_pass4 above; what changes
+// Compile-time shaped variant of the pass kernel (first written for the two tile shapes every transform >= 2^20
+// uses, [2^11 x 8] and [2^10 x 16] at 1024 lanes; P4_SHAPES lists its instantiations).  Same data flow as k_ntt_pass4 above; what changes
 // is the instruction count (1678 VALU instructions per wave before, 1106 now -- profiles/round01_pmc_valu.json --, of
 // which only ~900 are butterflies):
 //  * every LDS address is one per-lane base plus an immediate, every HBM address is a uniform
@@ -393,9 +394,7 @@ __device__ __forceinline__ void lds_rounds_ct(uint32_t* lv, const uint32_t* twl,
 #pragma unroll
             for (int k = 0; k < (1 << Q); k++) v[k] = base[(k << LOG_RQ) * pitch];
             load_unit_twiddles<Q, LOG_RQ, LOG_R - LOG_RCUR>(twl, j, w);
-#if !defined(NTT_ABL) || (NTT_ABL != 1 && NTT_ABL != 5)
             dif_unit_w<Q, LOG_RQ == 0>(v, w);
-#endif
 #pragma unroll
             for (int k = 0; k < (1 << Q); k++) base[(k << LOG_RQ) * pitch] = v[k];
         }
@@ -410,9 +409,6 @@ template <int LOG_R, int LOG_C, int LOG_T = 10>
 __global__ __launch_bounds__(1 << LOG_T) void k_ntt_pass4_ct(Pass4Args a) {
     static_assert(LOG_R >= 7 && LOG_R - 4 + LOG_C == LOG_T, "one radix-16 unit per lane in the first round");
     constexpr unsigned NT = 1u << LOG_T;
-    if (a.prio == 3) __builtin_amdgcn_s_setprio(3);
-    else if (a.prio == 2) __builtin_amdgcn_s_setprio(2);
-    else if (a.prio == 1) __builtin_amdgcn_s_setprio(1);
     extern __shared__ uint32_t sm[];
     constexpr unsigned R = 1u << LOG_R, C = 1u << LOG_C, pitch = C + 1u;
     constexpr int LOG_RQ = LOG_R - 4;
@@ -476,17 +472,9 @@ __global__ __launch_bounds__(1 << LOG_T) void k_ntt_pass4_ct(Pass4Args a) {
                                        (size_t)X * a.in_x_stride + F0;
             const uint32_t lane_off = (j << a.log_f) + c;
 #pragma unroll
-#if defined(NTT_ABL) && NTT_ABL == 2
-            for (int k = 0; k < 16; k++) v[k] = lane_off + k;
-#else
             for (int k = 0; k < 16; k++) v[k] = (tile_src + ((size_t)k << (LOG_RQ + a.log_f)))[lane_off];
-#endif
         }
-#if defined(NTT_ABL) && NTT_ABL == 5
-        if (false) {
-#else
         if (a.in_tw) {
-#endif
             const uint32_t mask = (a.log_tt >= 32) ? 0xffffffffu : ((1u << a.log_tt) - 1u);
             const uint32_t kc = bitrev32(F0 + c, a.log_prev);
             const uint32_t e0 = (kc * (j * a.tw_a + X * a.tw_bx)) & mask;
@@ -506,17 +494,13 @@ __global__ __launch_bounds__(1 << LOG_T) void k_ntt_pass4_ct(Pass4Args a) {
         }
         uint32_t w[15];
         load_unit_twiddles<4, LOG_RQ, 0>(twl, j, w);
-#if !defined(NTT_ABL) || (NTT_ABL != 1 && NTT_ABL != 5)
         dif_unit_w<4>(v, w);
-#endif
         uint32_t* base = lv + j * pitch + c;
 #pragma unroll
         for (int k = 0; k < 16; k++) base[(k << LOG_RQ) * pitch] = v[k];
     }
     zk_syncthreads();
-#if !defined(NTT_ABL) || (NTT_ABL != 4 && NTT_ABL != 5)
     lds_rounds_ct<LOG_R, LOG_C, LOG_RQ, NT>(lv, twl, tid);
-#endif
     // ---- write-out: each tile column is one contiguous run of R words; the column of every store is
     // a compile-time constant, so its HBM base is scalar and the LDS address an immediate ----
     const unsigned lo_mask = (1u << a.log_lo) - 1u;
@@ -528,11 +512,7 @@ __global__ __launch_bounds__(1 << LOG_T) void k_ntt_pass4_ct(Pass4Args a) {
             const unsigned c = (NT * i) >> LOG_R, p0 = (NT * i) & (R - 1u);
             const unsigned F = F0 + c;
             uint32_t* dcol = dst + (size_t)(F >> a.log_lo) * a.out_hi_stride + (size_t)(F & lo_mask) * a.out_lo_stride + p0;
-#if defined(NTT_ABL) && NTT_ABL == 3
-            if (lrow[p0 * pitch + c] == 0x12345678u) dcol[tid] = 1;
-#else
             dcol[tid] = lrow[p0 * pitch + c];
-#endif
         }
     } else {
         // short runs: one store instruction covers 1024 / R tile columns, the column is per lane
@@ -603,9 +583,6 @@ __global__ __launch_bounds__(1 << SH::LOG_T, 8) void k_ntt_pass4_ct_sq(Pass4Args
     constexpr int LOG_F = LOG_R, LOG_M = 2 * LOG_R, LOG_RQ = LOG_R - 4;
     constexpr unsigned NT = 1u << LOG_T, R = 1u << LOG_R, C = 1u << LOG_C, pitch = C + 1u;
     static_assert(LOG_C == 3 && LOG_RQ + LOG_C == LOG_T && LOG_R >= LOG_T && (R >> 1) % NT == 0 && LOG_F - LOG_C >= 7, "[2^11 x 8] tiles of 1024 lanes");
-    if (a.prio == 3) __builtin_amdgcn_s_setprio(3);
-    else if (a.prio == 2) __builtin_amdgcn_s_setprio(2);
-    else if (a.prio == 1) __builtin_amdgcn_s_setprio(1);
     extern __shared__ uint32_t sm[];
     uint32_t* lv = sm;
     uint32_t* twl = sm + R * pitch;
@@ -818,54 +795,79 @@ __global__ __launch_bounds__(1024, MIN_WAVES) void k_ntt_lde_fused(LdeFusedArgs 
     }
 }
 
-static constexpr unsigned P4_MAX_LOG_R = 11;
+// Stages per pass: 11 = two passes up to 2^22 points ([2^11 x 8] tiles of 70 KiB, two workgroups per CU).  At most three passes exist
+// (fourstep_split writes a[0..2]) and 3 x 11 covers the field's two-adicity of 27, so a smaller limit must never be set: one below 9 once
+// made 2^22-point transforms silently wrong (docs/kernels_2.md; a limit of 9 or 10 was measured there too and is slower).
+static constexpr unsigned MAX_LOG_R = 11;
 static constexpr unsigned P4_MIN_LOG_M = 12;
-// stages per pass: 11 = two passes up to 2^22 (128 KiB tiles, one workgroup per CU);
-// smaller values trade a third pass for small tiles and full occupancy.  Tunable for experiments.
-static unsigned p4_log_r_limit() {
-    static unsigned v = 0;
-    if (!v) {
-        const char* e = getenv("ZKHIP_NTT_MAX_LOG_R");
-        v = e ? (unsigned)atoi(e) : P4_MAX_LOG_R;
-        // at most three passes exist (fourstep_split writes a[0..2]): 3 * limit must cover the field's two-adicity (27).
-        // A smaller value used to be accepted and made 2^22 transforms silently wrong (4 "passes" of 7 stages, the 4th
-        // written past the array) -- found by tools/ntt_shape_sweep.sh.
-        if (v < 9 || v > P4_MAX_LOG_R) v = P4_MAX_LOG_R;
-    }
-    return v;
-}
 
-// src -> dst through tmp (and tmp2 for 3-pass sizes); dst may alias src.  Buffers hold `width`
-// columns of 2^log_sub transforms each, with the given column strides.
+// the coset scale tables of an LDE's forward transform (lde_scale_tables), for a first pass that reads bit-reversed coefficients
 struct BrSrc {
     const uint32_t *scale_col, *scale_row, *scale_rho;
 };
 // stage split of the four-step passes
 static unsigned fourstep_split(unsigned log_n, unsigned a[3]) {
-    const unsigned n_pass = std::max(2u, (log_n + p4_log_r_limit() - 1) / p4_log_r_limit());
+    const unsigned n_pass = std::max(2u, (log_n + MAX_LOG_R - 1) / MAX_LOG_R);
     a[0] = a[1] = a[2] = 0;
     for (unsigned p = 0; p < n_pass; p++) a[p] = log_n / n_pass + (p < log_n % n_pass ? 1 : 0);
     return n_pass;
 }
+// The passes' scratch (slot 4): `words` words for the passes to write their intermediate to, and as many again behind them for the
+// three-pass sizes (log_n > 2 * MAX_LOG_R), whose middle pass cannot write where it reads.
+static int pass_scratch(zkhip_ctx* ctx, unsigned log_n, size_t words, uint32_t** t1, uint32_t** t2) {
+    const bool three = log_n > 2 * MAX_LOG_R;
+    void* tmp;
+    ZK_TRY(get_scratch(ctx, 4, words * 4 * (three ? 2 : 1), &tmp));
+    *t1 = (uint32_t*)tmp;
+    *t2 = three ? *t1 + words : nullptr;
+    return ZKHIP_OK;
+}
 
+// Every compile-time tile shape of k_ntt_pass4_ct: 2^log_r rows x 2^log_c columns for a workgroup of 2^log_t lanes, one radix-16 unit per
+// lane (log_r - 4 + log_c == log_t).  The dispatcher launches from this table and sets the kernels' LDS attribute from it.
+typedef void (*Pass4Kernel)(Pass4Args);
+struct Pass4Shape {
+    unsigned log_r, log_c, log_t;
+    Pass4Kernel kernel;
+};
+#define ZK_P4_CT(R_, C_, T_) {R_, C_, T_, k_ntt_pass4_ct<R_, C_, T_>}
+static const Pass4Shape P4_SHAPES[] = {
+    ZK_P4_CT(11, 3, 10), ZK_P4_CT(10, 4, 10), ZK_P4_CT(9, 5, 10), ZK_P4_CT(8, 6, 10), ZK_P4_CT(7, 7, 10),  // 2^14 words, 70 KiB
+    ZK_P4_CT(10, 3, 9),  ZK_P4_CT(9, 4, 9),   ZK_P4_CT(8, 5, 9),  ZK_P4_CT(7, 6, 9),                       // 2^13 words, 37 KiB
+    ZK_P4_CT(10, 2, 8),  ZK_P4_CT(9, 3, 8),   ZK_P4_CT(8, 4, 8),  ZK_P4_CT(7, 5, 8),                       // 2^12 words, 18 KiB
+};
+#undef ZK_P4_CT
+// the shape-specialised form by pass mode (P4_PLAIN, P4_IN_TW, P4_BR_SRC)
+static const Pass4Kernel P4_SQ11[3] = {k_ntt_pass4_ct_sq<ShapeSq11, P4_PLAIN>, k_ntt_pass4_ct_sq<ShapeSq11, P4_IN_TW>,
+                                       k_ntt_pass4_ct_sq<ShapeSq11, P4_BR_SRC>};
+// The passes of the two-pass 2^22-point transform may run in their shape-specialised form (zkhip_config.ntt_pass_form = 0): everything
+// k_ntt_pass4_ct_sq<ShapeSq11, MODE> holds as a constant is checked here.
+static bool pass4_is_sq11(const Pass4Args& pa, unsigned n_pass, unsigned n_x, unsigned log_n) {
+    return n_pass == 2 && n_x == 1 && log_n == 22 && pa.log_r == 11 && pa.log_f == 11 && pa.log_c == 3 && pa.log_lo == 0 && pa.in_x_stride == 0 &&
+           pa.out_x_stride == 0 && pa.out_hi_stride == ((size_t)1 << 11) && !(pa.br_src && pa.in_tw) &&
+           (!pa.in_tw || (pa.log_prev == 11 && pa.log_tt == 22 && pa.tw_a == 1 && pa.tw_bx == 0));
+}
+// The kernel of a pass whose tile shape (pa.log_r, pa.log_c, log_t) is settled: the specialised form, else the table, else the
+// run-time-shaped kernel (k_ntt_pass4's header lists what reaches it).
+static Pass4Kernel pass4_kernel_for(const Pass4Args& pa, unsigned log_t, int pass_form, unsigned n_pass, unsigned n_x, unsigned log_n) {
+    if (pass_form == 0 && pass4_is_sq11(pa, n_pass, n_x, log_n)) return P4_SQ11[pa.br_src ? P4_BR_SRC : pa.in_tw ? P4_IN_TW : P4_PLAIN];
+    for (const Pass4Shape& sh : P4_SHAPES)
+        if (sh.log_r == pa.log_r && sh.log_c == pa.log_c && sh.log_t == log_t) return sh.kernel;
+    return k_ntt_pass4;
+}
+
+// src -> dst through tmp (and tmp2 for 3-pass sizes); dst may alias src.  Buffers hold `width`
+// columns of 2^log_sub transforms each, with the given column strides.
 static int ntt_dif_fourstep(zkhip_ctx* ctx, const uint32_t* src, size_t src_stride, uint32_t* dst, size_t dst_stride,
                             uint32_t* tmp, uint32_t* tmp2, size_t tmp_stride, unsigned log_n, size_t width,
                             unsigned log_sub, bool inverse, const BrSrc* brsrc = nullptr,
                             const uint32_t* const* src_cols = nullptr, uint32_t* const* dst_cols = nullptr) {
     static DeviceOnce attr_set;
     if (attr_set.need(ctx->device)) {
-        const int lds_max = ((17u << P4_MAX_LOG_R) + (1u << (P4_MAX_LOG_R - 1))) * 4;
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4<11, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4<10, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct<11, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct<10, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct<9, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct<8, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct<7, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct_sq<ShapeSq11, P4_PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct_sq<ShapeSq11, P4_IN_TW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4_ct_sq<ShapeSq11, P4_BR_SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        const int lds_max = ((17u << MAX_LOG_R) + (1u << (MAX_LOG_R - 1))) * 4;
+        for (const Pass4Shape& sh : P4_SHAPES) ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)sh.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        for (Pass4Kernel k : P4_SQ11) ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_ntt_pass4, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
         attr_set.mark(ctx->device);
     }
     unsigned a[3];
@@ -881,68 +883,25 @@ static int ntt_dif_fourstep(zkhip_ctx* ctx, const uint32_t* src, size_t src_stri
         pa.log_sub = log_sub;
         pa.log_m = log_n;
         const unsigned R = 1u << pa.log_r;
-        // 2^11-row tiles take 8 columns (70 KiB of LDS, two workgroups per CU so one loads while the
-        // other computes: measured 20 % faster than one 139 KiB / 16-column workgroup per CU);
-        // shorter tiles keep 16 columns (64-byte segments).  ZKHIP_NTT_LOG_C overrides.
-        static int log_c_env = -1;
-        if (log_c_env < 0) {
-            const char* e = getenv("ZKHIP_NTT_LOG_C");
-            log_c_env = e ? atoi(e) : 0;
-            if (log_c_env != 3 && log_c_env != 4) log_c_env = 0;
-        }
-        // tiles of 2^14 words (one radix-16 unit per lane): [2^11 x 8], [2^10 x 16], and for the short passes of
-        // three-pass sizes [2^9 x 32], [2^8 x 64], [2^7 x 128]
-        pa.log_c = log_c_env ? (unsigned)log_c_env : (pa.log_r >= 11 ? 3u : (pa.log_r >= 7 ? 14u - pa.log_r : 4u));
+        // tiles of 2^14 words (one radix-16 unit per lane): [2^11 x 8] (70 KiB of LDS, two workgroups per CU so one loads while the other
+        // computes: measured 20 % faster than one 139 KiB / 16-column workgroup per CU), [2^10 x 16], and for the short passes of
+        // three-pass sizes [2^9 x 32], [2^8 x 64], [2^7 x 128]; below 2^7 rows 16 columns (64-byte segments)
+        pa.log_c = pa.log_r >= 11 ? 3u : (pa.log_r >= 7 ? 14u - pa.log_r : 4u);
         // workgroups of 2^log_t lanes for the passes of at most 2^10 rows (zkhip_config.ntt_log_lanes: 10 = the 1024-lane tiles above; 9 / 8 =
         // tiles of 2^13 / 2^12 words, 37 / 18 KiB of LDS, four / eight workgroups per CU)
         unsigned log_t = 10;
-        if (!log_c_env && pa.log_r >= 7 && pa.log_r <= 10 && ctx->cfg.ntt_log_lanes >= 8 && ctx->cfg.ntt_log_lanes <= 9) {
+        if (pa.log_r >= 7 && pa.log_r <= 10 && ctx->cfg.ntt_log_lanes >= 8 && ctx->cfg.ntt_log_lanes <= 9) {
             const unsigned lc = ctx->cfg.ntt_log_lanes + 4 - pa.log_r;
             if (lc >= 2 && lc <= pa.log_f) log_t = ctx->cfg.ntt_log_lanes, pa.log_c = lc;
         }
         if (pa.log_c > pa.log_f) pa.log_c = pa.log_f;
         const unsigned C = 1u << pa.log_c;
+        // one lane per radix-16 unit: 2^log_t for a table shape; the run-time-shaped kernel takes any count
         const unsigned threads = std::min(1024u, std::max(64u, (R >> 4) * C));
         const size_t lds = ((size_t)R * (C + 1) + (R >> 1)) * 4;
         dim3 grid(n_x << (pa.log_f - pa.log_c), (unsigned)(width << log_sub));
         KernelScope ks(ctx, inverse ? "ntt_pass_inv" : "ntt_pass_fwd");
-        static const bool legacy = getenv("ZKHIP_NTT_LEGACY") != nullptr;  // A/B switch for experiments
-        static const unsigned prio_env = getenv("ZKHIP_NTT_PRIO") ? (unsigned)atoi(getenv("ZKHIP_NTT_PRIO")) : 0u;
-        pa.prio = prio_env;
-#define ZK_NTT_CT(R_, C_, T_) hipLaunchKernelGGL((k_ntt_pass4_ct<R_, C_, T_>), grid, dim3(1u << T_), lds, ctx->stream, pa)
-        if (log_t == 9 && pa.log_r == 10 && pa.log_c == 3) ZK_NTT_CT(10, 3, 9);
-        else if (log_t == 9 && pa.log_r == 9 && pa.log_c == 4) ZK_NTT_CT(9, 4, 9);
-        else if (log_t == 9 && pa.log_r == 8 && pa.log_c == 5) ZK_NTT_CT(8, 5, 9);
-        else if (log_t == 9 && pa.log_r == 7 && pa.log_c == 6) ZK_NTT_CT(7, 6, 9);
-        else if (log_t == 8 && pa.log_r == 10 && pa.log_c == 2) ZK_NTT_CT(10, 2, 8);
-        else if (log_t == 8 && pa.log_r == 9 && pa.log_c == 3) ZK_NTT_CT(9, 3, 8);
-        else if (log_t == 8 && pa.log_r == 8 && pa.log_c == 4) ZK_NTT_CT(8, 4, 8);
-        else if (log_t == 8 && pa.log_r == 7 && pa.log_c == 5) ZK_NTT_CT(7, 5, 8);
-#undef ZK_NTT_CT
-        // the passes of the two-pass 2^22-point transform in their shape-specialised form (zkhip_config.ntt_pass_form = 0): everything
-        // k_ntt_pass4_ct_sq holds as a constant is checked here
-        else if (ctx->cfg.ntt_pass_form == 0 && !legacy && n_pass == 2 && n_x == 1 && log_n == 22 && pa.log_r == 11 && pa.log_f == 11 && pa.log_c == 3 &&
-                 pa.log_lo == 0 && pa.in_x_stride == 0 && pa.out_x_stride == 0 && pa.out_hi_stride == ((size_t)1 << 11) && !(pa.br_src && pa.in_tw) &&
-                 (!pa.in_tw || (pa.log_prev == 11 && pa.log_tt == 22 && pa.tw_a == 1 && pa.tw_bx == 0))) {
-            if (pa.br_src) hipLaunchKernelGGL((k_ntt_pass4_ct_sq<ShapeSq11, P4_BR_SRC>), grid, dim3(1024), lds, ctx->stream, pa);
-            else if (pa.in_tw) hipLaunchKernelGGL((k_ntt_pass4_ct_sq<ShapeSq11, P4_IN_TW>), grid, dim3(1024), lds, ctx->stream, pa);
-            else hipLaunchKernelGGL((k_ntt_pass4_ct_sq<ShapeSq11, P4_PLAIN>), grid, dim3(1024), lds, ctx->stream, pa);
-        } else if (pa.log_r == 11 && pa.log_c == 3 && !legacy)
-            hipLaunchKernelGGL((k_ntt_pass4_ct<11, 3>), grid, dim3(threads), lds, ctx->stream, pa);
-        else if (pa.log_r == 10 && pa.log_c == 4 && !legacy)
-            hipLaunchKernelGGL((k_ntt_pass4_ct<10, 4>), grid, dim3(threads), lds, ctx->stream, pa);
-        else if (pa.log_r == 9 && pa.log_c == 5 && !legacy)
-            hipLaunchKernelGGL((k_ntt_pass4_ct<9, 5>), grid, dim3(threads), lds, ctx->stream, pa);
-        else if (pa.log_r == 8 && pa.log_c == 6 && !legacy)
-            hipLaunchKernelGGL((k_ntt_pass4_ct<8, 6>), grid, dim3(threads), lds, ctx->stream, pa);
-        else if (pa.log_r == 7 && pa.log_c == 7 && !legacy)
-            hipLaunchKernelGGL((k_ntt_pass4_ct<7, 7>), grid, dim3(threads), lds, ctx->stream, pa);
-        else if (pa.log_r == 11 && pa.log_c == 3)
-            hipLaunchKernelGGL((k_ntt_pass4<11, 3>), grid, dim3(threads), lds, ctx->stream, pa);
-        else if (pa.log_r == 10 && pa.log_c == 4)
-            hipLaunchKernelGGL((k_ntt_pass4<10, 4>), grid, dim3(threads), lds, ctx->stream, pa);
-        else
-            hipLaunchKernelGGL((k_ntt_pass4<0, 0>), grid, dim3(threads), lds, ctx->stream, pa);
+        hipLaunchKernelGGL(pass4_kernel_for(pa, log_t, ctx->cfg.ntt_pass_form, n_pass, n_x, log_n), grid, dim3(threads), lds, ctx->stream, pa);
         ZK_HIP_CHECK(ctx, hipGetLastError());
         return ZKHIP_OK;
     };
@@ -997,7 +956,6 @@ static int ntt_dif_fourstep(zkhip_ctx* ctx, const uint32_t* src, size_t src_stri
     return ZKHIP_OK;
 }
 
-static constexpr unsigned MAX_LOG_R = 11;      // stages per pass
 static constexpr unsigned MAX_LOG_TILE = 15;   // 2^15 words = 128 KiB of LDS
 static constexpr unsigned MAX_LOG_C = 7;
 
@@ -1007,11 +965,8 @@ int ntt_dif_inplace(zkhip_ctx* ctx, const uint32_t* src, size_t src_stride, uint
     ZK_TRY(ensure_twiddles(ctx, log_n));
     if (log_n >= P4_MIN_LOG_M && ctx->cfg.ntt_pass_form != 2) {
         const size_t per_col = (size_t)1 << (log_n + log_sub);
-        const bool three = log_n > 2 * p4_log_r_limit();
-        void* tmp;
-        ZK_TRY(get_scratch(ctx, 4, per_col * width * 4 * (three ? 2 : 1), &tmp));
-        uint32_t* t1 = (uint32_t*)tmp;
-        uint32_t* t2 = three ? t1 + per_col * width : nullptr;
+        uint32_t *t1, *t2;
+        ZK_TRY(pass_scratch(ctx, log_n, per_col * width, &t1, &t2));
         return ntt_dif_fourstep(ctx, src, src_stride, dst, dst_stride, t1, t2, per_col, log_n, width, log_sub, inverse);
     }
     if (log_n == 0) {
@@ -1373,6 +1328,25 @@ static int lde_fused(zkhip_ctx* ctx, const uint32_t* d_in, size_t in_stride, con
     return ZKHIP_OK;
 }
 
+// The tail both LDE entry points share: the forward four-step of every coset straight from the bit-reversed coefficients (`width` columns
+// of n words, contiguous).  The first pass reads each lane's 16 operands as one 64-byte chunk and applies shift_j^i / N as a geometric
+// sequence (the coset scale tables); the last writes to d_out, or to the columns of d_dst_cols when that is set.
+static int lde_forward_from_coeffs(zkhip_ctx* ctx, const uint32_t* coeffs, uint32_t* d_out, size_t out_stride, uint32_t* const* d_dst_cols,
+                                   unsigned log_n, unsigned added_bits, size_t width, uint32_t shift_monty) {
+    const size_t n = (size_t)1 << log_n, per_col = n << added_bits;
+    unsigned a[3];
+    fourstep_split(log_n, a);
+    const unsigned log_f = log_n - a[0], log_rq = a[0] - 4, n_co = 1u << added_bits;
+    uint32_t* d_col = nullptr;
+    ZK_TRY(lde_scale_tables(ctx, log_n, added_bits, shift_monty, log_f, log_rq, &d_col));
+    uint32_t* d_row = d_col + n_co * ((size_t)1 << log_f);
+    uint32_t* d_rho = d_row + n_co * ((size_t)1 << log_rq);
+    const BrSrc bs{d_col, d_row, d_rho};
+    uint32_t *t1, *t2;
+    ZK_TRY(pass_scratch(ctx, log_n, per_col * width, &t1, &t2));
+    return ntt_dif_fourstep(ctx, coeffs, n, d_out, out_stride, t1, t2, per_col, log_n, width, added_bits, false, &bs, nullptr, d_dst_cols);
+}
+
 int lde_batch(zkhip_ctx* ctx, const uint32_t* d_in, size_t in_stride, uint32_t* d_out, size_t out_stride,
               unsigned log_n, unsigned added_bits, size_t width, uint32_t shift_monty) {
     if (width == 0) return ZKHIP_OK;
@@ -1386,25 +1360,8 @@ int lde_batch(zkhip_ctx* ctx, const uint32_t* d_in, size_t in_stride, uint32_t* 
     ZK_TRY(get_scratch(ctx, 0, n * width * 4, &coeffs));
     ZK_TRY(ntt_dif_inplace(ctx, d_in, in_stride, (uint32_t*)coeffs, n, log_n, width, 0, true));
     if (log_n >= P4_MIN_LOG_M && ctx->cfg.ntt_pass_form != 2) {
-        // 2'. forward four-step straight from the bit-reversed coefficients: the first pass reads each
-        //     lane's 16 operands as one 64-byte chunk and applies shift_j^i / N as a geometric sequence
-        unsigned a[3];
-        fourstep_split(log_n, a);
-        const unsigned log_f = log_n - a[0], log_rq = a[0] - 4, n_co = 1u << added_bits;
-        const size_t n_col = (size_t)1 << log_f, n_row = (size_t)1 << log_rq;
-        uint32_t* d_col = nullptr;
-        ZK_TRY(lde_scale_tables(ctx, log_n, added_bits, shift_monty, log_f, log_rq, &d_col));
-        uint32_t* d_row = d_col + n_co * n_col;
-        uint32_t* d_rho = d_row + n_co * n_row;
-        BrSrc bs{d_col, d_row, d_rho};
-        const size_t per_col = n << added_bits;
-        const bool three = log_n > 2 * p4_log_r_limit();
-        void* tmp;
-        ZK_TRY(get_scratch(ctx, 4, per_col * width * 4 * (three ? 2 : 1), &tmp));
-        uint32_t* t1 = (uint32_t*)tmp;
-        uint32_t* t2 = three ? t1 + per_col * width : nullptr;
-        return ntt_dif_fourstep(ctx, (const uint32_t*)coeffs, n, d_out, out_stride, t1, t2, per_col, log_n, width, added_bits,
-                                false, &bs);
+        // 2'. forward four-step straight from the bit-reversed coefficients
+        return lde_forward_from_coeffs(ctx, (const uint32_t*)coeffs, d_out, out_stride, nullptr, log_n, added_bits, width, shift_monty);
     }
     // 2. per-coset power tables
     unsigned lb = (log_n + 1) / 2;
@@ -1453,31 +1410,13 @@ int lde_batch_cols(zkhip_ctx* ctx, const uint32_t* const* d_src_cols, uint32_t* 
     void* coeffs;
     ZK_TRY(get_scratch(ctx, 0, n * n_cols * 4, &coeffs));
     {
-        // inverse transform: columns come from the table, coefficients go to contiguous scratch
-        const bool three = log_n > 2 * p4_log_r_limit();
-        void* tmp;
-        ZK_TRY(get_scratch(ctx, 4, (n << added_bits) * n_cols * 4 * (three ? 2 : 1), &tmp));
-        uint32_t* t1 = (uint32_t*)tmp;
-        uint32_t* t2 = three ? t1 + n * n_cols : nullptr;
+        // inverse transform: columns come from the table, coefficients go to contiguous scratch (asked for at the size the forward
+        // transform will ask for, so that the scratch is not allocated twice)
+        uint32_t *t1, *t2;
+        ZK_TRY(pass_scratch(ctx, log_n, (n << added_bits) * n_cols, &t1, &t2));
         ZK_TRY(ntt_dif_fourstep(ctx, nullptr, 0, (uint32_t*)coeffs, n, t1, t2, n, log_n, n_cols, 0, true, nullptr, d_src_cols, nullptr));
     }
-    unsigned a[3];
-    fourstep_split(log_n, a);
-    const unsigned log_f = log_n - a[0], log_rq = a[0] - 4, n_co = 1u << added_bits;
-    const size_t n_col = (size_t)1 << log_f, n_row = (size_t)1 << log_rq;
-    uint32_t* d_col = nullptr;
-    ZK_TRY(lde_scale_tables(ctx, log_n, added_bits, shift_monty, log_f, log_rq, &d_col));
-    uint32_t* d_row = d_col + n_co * n_col;
-    uint32_t* d_rho = d_row + n_co * n_row;
-    BrSrc bs{d_col, d_row, d_rho};
-    const size_t per_col = n << added_bits;
-    const bool three = log_n > 2 * p4_log_r_limit();
-    void* tmp;
-    ZK_TRY(get_scratch(ctx, 4, per_col * n_cols * 4 * (three ? 2 : 1), &tmp));
-    uint32_t* t1 = (uint32_t*)tmp;
-    uint32_t* t2 = three ? t1 + per_col * n_cols : nullptr;
-    return ntt_dif_fourstep(ctx, (const uint32_t*)coeffs, n, nullptr, 0, t1, t2, per_col, log_n, n_cols, added_bits, false, &bs,
-                            nullptr, d_dst_cols);
+    return lde_forward_from_coeffs(ctx, (const uint32_t*)coeffs, nullptr, 0, d_dst_cols, log_n, added_bits, n_cols, shift_monty);
 }
 
 // ---------------------------------------------------------------------------------------------
