@@ -670,6 +670,38 @@ int zkhip_airset_verify(const zkhip_whir_params *params, const uint32_t *prefix,
                         const uint32_t *const *pvs, unsigned log_stack, const uint32_t *proof, size_t words, uint32_t *root_out,
                         uint32_t *pq_out);
 
+/* ---- the keyed form of both proofs (docs/airset.md, docs/zerocheck.md): AIR sets with preprocessed columns.  A key is ONE stacked
+ *      WHIR commitment, at log_stack_prep, of all preprocessed columns of the set (AIRs in caller order, columns in column order, an
+ *      AIR's columns at that AIR's height), made once; its root prep_root (8 canonical words) is the verifying-key entry.  Both sides
+ *      observe prep_root after the caller's prefix and before the main root; a PREP cell is proven like a main cell; the values v_p
+ *      (w_p) and v_p' (n_rot_p, the preprocessed columns read at rotation 1) follow v and v', the rotation reduction runs if
+ *      n_rot + n_rot_p > 0 and then u_p (w_p) follows u; after the main stacked opening comes one stacked opening of the key's
+ *      commitment, one point per AIR that has preprocessed columns.  with_bus = 0 is the zero-check, 1 the AIR-set proof.
+ *      Proof words: [root (8) | with_bus: GKR words for L | with_bus: 4 per AIR with interactions |
+ *      per active AIR: 4 D m + 4 (w + n_rot + w_p + n_rot_p) (+ 8 m + 4 (w + w_p) if n_rot + n_rot_p > 0) |
+ *      zkhip_stack_proof_words(main columns, log_stack) | zkhip_stack_proof_words(preprocessed columns, log_stack_prep)].
+ *      Refused (ZKHIP_ERR_INVALID; zkhip_airkey_proof_words returns 0): everything the unkeyed form refuses except PREP, a set in
+ *      which no AIR has a PREP section, preprocessed columns that zkhip_stack_width refuses at log_stack_prep; at key generation also
+ *      a PREP AIR whose prep_trace is NULL and a preprocessed word that is not canonical. ---- */
+typedef struct zkhip_airkey zkhip_airkey;
+/* Reads airs[a].prep_trace (HOST, canonical, column-major, as zkhip_keygen does) and copies the programs: nothing of `airs` need
+ * outlive the call.  The key keeps the columns on the device in Montgomery form together with the commitment; no prove call commits
+ * or uploads them again.  prep_root_out: HOST, 8 canonical words, may be NULL (synchronises). */
+int zkhip_airkey_create(zkhip_ctx *ctx, const zkhip_whir_params *params, const zkhip_air *airs, size_t n_airs, unsigned log_stack_prep,
+                        zkhip_airkey **key_out, uint32_t *prep_root_out);
+void zkhip_airkey_destroy(zkhip_ctx *ctx, zkhip_airkey *key);
+size_t zkhip_airkey_proof_words(const zkhip_whir_params *params, const zkhip_air *airs, size_t n_airs, unsigned log_stack,
+                                unsigned log_stack_prep, int with_bus);
+/* Device prover over the key's AIRs; d_traces, pvs, transcript, proof_out, cap and root_out as in zkhip_zerocheck_prove.  Workspace
+ * per call as for the unkeyed proof, plus (w_p + n_rot_p) folded tables per AIR. */
+int zkhip_airkey_prove(zkhip_ctx *ctx, zkhip_airkey *key, int with_bus, const uint32_t *const *d_traces, const uint32_t *const *pvs,
+                       unsigned log_stack, zkhip_transcript *transcript, uint32_t *proof_out, size_t cap, uint32_t *root_out);
+/* Host verifier, needs no device and never reads prep_trace: the key's opening is checked against prep_root.  root_out and pq_out
+ * (with_bus only) may be NULL. */
+int zkhip_airkey_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const zkhip_air *airs, size_t n_airs,
+                        const uint32_t *prep_root, unsigned log_stack_prep, const uint32_t *const *pvs, unsigned log_stack, int with_bus,
+                        const uint32_t *proof, size_t words, uint32_t *root_out, uint32_t *pq_out);
+
 /* Field offsets of a proof, in 32-bit words from its start (the layout is static for given parameters and AIR shapes:
  * DESIGN.md section 4).  The counterpart of `Proof::<SC>::decode_from_bytes` (crates/verifier/src/verifier.rs:62) for this
  * backend's proofs: commitments, opened values, FRI layers and query openings are read in place.  Needs no device. */

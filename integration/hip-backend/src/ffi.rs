@@ -87,6 +87,10 @@ pub struct zkhip_whir_commitment {
 pub struct zkhip_stack_commitment {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct zkhip_airkey {
+    _private: [u8; 0],
+}
 
 // docs/whir.md
 #[repr(C)]
@@ -447,6 +451,19 @@ extern "C" {
     pub fn zkhip_airset_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, airs: *const zkhip_air, n_airs: usize,
                                pvs: *const *const u32, log_stack: c_uint, proof: *const u32, words: usize, root_out: *mut u32,
                                pq_out: *mut u32) -> c_int;
+
+    // the keyed form of both proofs: AIR sets with preprocessed columns under a stacked commitment made at key generation
+    pub fn zkhip_airkey_create(ctx: *mut zkhip_ctx, params: *const zkhip_whir_params, airs: *const zkhip_air, n_airs: usize,
+                               log_stack_prep: c_uint, key_out: *mut *mut zkhip_airkey, prep_root_out: *mut u32) -> c_int;
+    pub fn zkhip_airkey_destroy(ctx: *mut zkhip_ctx, key: *mut zkhip_airkey);
+    pub fn zkhip_airkey_proof_words(params: *const zkhip_whir_params, airs: *const zkhip_air, n_airs: usize, log_stack: c_uint,
+                                    log_stack_prep: c_uint, with_bus: c_int) -> usize;
+    pub fn zkhip_airkey_prove(ctx: *mut zkhip_ctx, key: *mut zkhip_airkey, with_bus: c_int, d_traces: *const *const u32,
+                              pvs: *const *const u32, log_stack: c_uint, transcript: *mut zkhip_transcript, proof_out: *mut u32,
+                              cap: usize, root_out: *mut u32) -> c_int;
+    pub fn zkhip_airkey_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, airs: *const zkhip_air, n_airs: usize,
+                               prep_root: *const u32, log_stack_prep: c_uint, pvs: *const *const u32, log_stack: c_uint, with_bus: c_int,
+                               proof: *const u32, words: usize, root_out: *mut u32, pq_out: *mut u32) -> c_int;
 
     // the reference's stored-proof container (OpenVM-v1 Proof<SC>, bincode)
     pub fn zkhip_proof_decode_v1(bytes: *const u8, len: usize, kind: c_int, out: *mut zkhip_v1_summary) -> c_int;

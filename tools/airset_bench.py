@@ -3,11 +3,12 @@ zkhip_profile_*), wall time and proof words of zkhip_airset_prove, split into th
 commit plus opening (stack_*, whir_*), and beside it the fair comparison on the same key and the same library build: the two separate
 calls zkhip_zerocheck_prove plus zkhip_bus_gkr_prove (which prove less: their bus proof is not tied to the committed traces), and
 zkhip_prove.  Shapes: the lookup key of tools/gkr_bench.py (a sender of 2^20 rows, a table of 2^16) and the 42-chip ChipSet with a
-main-column range table in place of its preprocessed one.  Parameters (b, k, final_log) = (1, 4, 6), 80 queries and 16 bits of
+main-column range table in place of its preprocessed one, and `chipset42_keyed`: ChipSet().gen() as generated, with its preprocessed
+range table, proven through the key (Context.airkey; key generation is timed on its own, log_stack_prep = 4).  Parameters (b, k, final_log) = (1, 4, 6), 80 queries and 16 bits of
 grinding in every round; v1 parameters z.DEFAULT_PARAMS.  Every figure is the median of --reps runs after one warm-up.  Prints one
 JSON object.
 
-  python tools/airset_bench.py [--reps 3] [--shapes lookup20x16,chipset42] [--no-v1]"""
+  python tools/airset_bench.py [--reps 3] [--shapes lookup20x16,chipset42,chipset42_keyed] [--no-v1]"""
 import argparse
 import json
 import os
@@ -45,7 +46,9 @@ SHAPES = {
     # (AIRs, log_stack)
     "lookup20x16": (lambda: _lookup(20, 16), 20),
     "chipset42": (_chipset, 20),
+    "chipset42_keyed": (lambda: air.ChipSet().gen(), 20),
 }
+KEYED = {"chipset42_keyed": 4}   # shape -> log_stack_prep
 
 
 def _group(by_name):
@@ -65,7 +68,7 @@ def main():
     a = ap.parse_args()
     zk = z.Context(0)
     prm = z.WhirParams.make(1, 4, 6, 16, 80)
-    out = {"airset": [], "zerocheck": [], "bus_gkr": [], "v1": []}
+    out = {"airset": [], "zerocheck": [], "bus_gkr": [], "v1": [], "keyed": [], "keygen": []}
 
     def note(r):
         print(json.dumps({k: v for k, v in r.items() if k != "by_name"}), file=sys.stderr)
@@ -78,6 +81,32 @@ def main():
         d = [zk.upload(np.asarray(x["trace"], dtype=np.uint32).reshape(-1)) for x in airs]
         words = z.airset_proof_words(prm, vairs, l)
         common = dict(shape=name, n_airs=len(airs), log_stack=l, total_cells=sum(x["width"] << x["log_height"] for x in airs))
+        if name in KEYED:   # the set as generated, through the key; beside it zkhip_prove of the same set
+            lpr, proof = KEYED[name], {}
+            r = _profiled(zk, lambda: zk.airkey(prm, airs, lpr).close(), a.reps)
+            r.update(common, log_stack_prep=lpr)
+            out["keygen"].append(r)
+            note(r)
+            key = zk.airkey(prm, airs, lpr)
+
+            def keyed():
+                proof["p"] = key.prove(d, pvs, l, [1])[1]
+
+            r = _profiled(zk, keyed, a.reps)
+            z.airkey_verify(prm, [1], vairs, key.root, lpr, pvs, l, proof["p"])
+            r.update(common, log_stack_prep=lpr, proof_words=z.airkey_proof_words(prm, vairs, l, lpr), split=_group(r["by_name"]))
+            out["keyed"].append(r)
+            note(r)
+            key.close()
+            if not a.no_v1:
+                pk = z.ProvingKey(zk, z.DEFAULT_PARAMS, airs)
+                r = _profiled(zk, lambda: pk.prove(d, pvs), a.reps)
+                r.update(common, proof_words=pk.proof_size // 4)
+                out["v1"].append(r)
+                note(r)
+                pk.close()
+            del d
+            continue
         if not words:
             out["airset"].append(dict(common, refused=True))
             continue

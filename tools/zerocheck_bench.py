@@ -2,10 +2,12 @@
 zkhip_profile_*), wall time and proof words of zkhip_zerocheck_prove, split into commit (a zkhip_stack_commit of the same columns,
 measured on its own), zero-check (the zc_* kernels) and opening (the stack_* and whir_* kernels less the commit), beside zkhip_prove
 of the same key on the same library build, whose quotient evaluation and quotient commit are what the zero-check replaces.
+`chipset42_keyed` is ChipSet().gen() as generated, with its preprocessed range table, proven through the key (Context.airkey,
+with_bus = False, log_stack_prep = 4); key generation is timed on its own.
 Parameters (b, k, final_log) = (1, 4, 6), 80 queries and 16 bits of grinding in every round; v1 parameters (1, 0, 100, 16, 16).  Every
 figure is the median of --reps runs after one warm-up.  Prints one JSON object.
 
-  python tools/zerocheck_bench.py [--reps 3] [--shapes synth18,synth20,synth22,chipset42] [--no-v1]"""
+  python tools/zerocheck_bench.py [--reps 3] [--shapes synth18,synth20,synth22,chipset42,chipset42_keyed] [--no-v1]"""
 import argparse
 import json
 import os
@@ -38,7 +40,9 @@ SHAPES = {
     "synth20": (lambda: _synth(20), 23),
     "synth22": (lambda: _synth(22), 25),
     "chipset42": (_chipset, 20),
+    "chipset42_keyed": (lambda: air.ChipSet().gen(), 20),
 }
+KEYED = {"chipset42_keyed": 4}   # shape -> log_stack_prep
 
 
 def _group(by_name):
@@ -58,7 +62,7 @@ def main():
     a = ap.parse_args()
     zk = z.Context(0)
     prm = z.WhirParams.make(1, 4, 6, 16, 80)
-    out = {"zerocheck": [], "commit": [], "v1": []}
+    out = {"zerocheck": [], "commit": [], "v1": [], "keygen": []}
     for name in [s for s in a.shapes.split(",") if s]:
         airs_fn, l = SHAPES[name]
         airs = airs_fn()
@@ -66,18 +70,32 @@ def main():
         pvs = [x["pvs"] for x in airs]
         d = [zk.upload(np.asarray(x["trace"], dtype=np.uint32).reshape(-1)) for x in airs]
         cols = [t[c << x["log_height"]:(c + 1) << x["log_height"]] for t, x in zip(d, airs) for c in range(x["width"])]
-        words = z.zerocheck_proof_words(prm, vairs, l)
+        lpr = KEYED.get(name)
+        words = z.airkey_proof_words(prm, vairs, l, lpr, False) if lpr is not None else z.zerocheck_proof_words(prm, vairs, l)
         common = dict(shape=name, n_airs=len(airs), n_cols=len(cols), log_stack=l, total_cells=sum(x["width"] << x["log_height"] for x in airs))
         if not words:
             out["zerocheck"].append(dict(common, refused=True))
             continue
-        proof = {}
+        proof, key = {}, None
+        if lpr is not None:
+            r = _profiled(zk, lambda: zk.airkey(prm, airs, lpr).close(), a.reps)
+            r.update(common, log_stack_prep=lpr)
+            out["keygen"].append(r)
+            print(json.dumps({k: v for k, v in r.items() if k != "by_name"}), file=sys.stderr)
+            key = zk.airkey(prm, airs, lpr)
 
         def zerocheck():
-            proof["p"] = zk.zerocheck_prove(prm, vairs, d, pvs, l, [1])[1]
+            if key is not None:
+                proof["p"] = key.prove(d, pvs, l, [1], with_bus=False)[1]
+            else:
+                proof["p"] = zk.zerocheck_prove(prm, vairs, d, pvs, l, [1])[1]
 
         r = _profiled(zk, zerocheck, a.reps)
-        z.zerocheck_verify(prm, [1], vairs, pvs, l, proof["p"])
+        if key is not None:
+            z.airkey_verify(prm, [1], vairs, key.root, lpr, pvs, l, proof["p"], False)
+            key.close()
+        else:
+            z.zerocheck_verify(prm, [1], vairs, pvs, l, proof["p"])
         r.update(common, proof_words=words, split=_group(r["by_name"]))
         out["zerocheck"].append(r)
         print(json.dumps({k: v for k, v in r.items() if k != "by_name"}), file=sys.stderr)

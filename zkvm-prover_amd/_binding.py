@@ -334,6 +334,12 @@ def load_library():
                                          u32p]),
         "zkhip_airset_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, C.POINTER(_Air), sz, C.POINTER(u32p), C.c_uint, u32p, sz, u32p,
                                           u32p]),
+        "zkhip_airkey_create": (C.c_int, [vp, C.POINTER(WhirParams), C.POINTER(_Air), sz, C.c_uint, C.POINTER(vp), u32p]),
+        "zkhip_airkey_destroy": (None, [vp, vp]),
+        "zkhip_airkey_proof_words": (sz, [C.POINTER(WhirParams), C.POINTER(_Air), sz, C.c_uint, C.c_uint, C.c_int]),
+        "zkhip_airkey_prove": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(u32p), C.c_uint, vp, u32p, sz, u32p]),
+        "zkhip_airkey_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, C.POINTER(_Air), sz, u32p, C.c_uint, C.POINTER(u32p), C.c_uint, C.c_int,
+                                          u32p, sz, u32p, u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -1085,6 +1091,17 @@ class Context:
         self._check(rc)
         return root, proof[:words]
 
+    # ---- the keyed form of both: AIR sets with preprocessed columns (docs/airset.md, docs/zerocheck.md) -------------
+    def airkey(self, params, airs, log_stack_prep):
+        """The key of `airs` (dicts as for ProvingKey; an AIR with a PREP section carries `prep`, canonical, [prep_width, 2^log_height]):
+        every preprocessed column of the set in ONE stacked WHIR commitment at log_stack_prep, the columns resident on the device.
+        Returns the AirKey; its `root` (8 canonical words) is what a verifier holds."""
+        arr, keep = _air_structs(airs)
+        h = C.c_void_p()
+        root = np.zeros(8, dtype=np.uint32)
+        self._check(self.lib.zkhip_airkey_create(self.h, C.byref(params), arr, len(airs), log_stack_prep, C.byref(h), _u32p(root)))
+        return AirKey(self, h, params, airs, log_stack_prep, root)
+
     # ---- profiling -----------------------------------------------------------------------------
     def profile_enable(self, on=True):
         self._check(self.lib.zkhip_profile_enable(self.h, int(on)))
@@ -1369,6 +1386,43 @@ class StackCommitment:
             pass
 
 
+class AirKey:
+    """The key of an AIR set with preprocessed columns (zkhip_airkey): their stacked commitment and the columns on the device."""
+
+    def __init__(self, ctx, h, params, airs, log_stack_prep, root):
+        self.ctx, self.h, self.params, self.log_stack_prep, self.root = ctx, h, params, log_stack_prep, root
+        self.airs = [{k: v for k, v in a.items() if k not in ("prep", "prep_commit")} for a in airs]   # what a verifier needs
+
+    def prove(self, traces, pvs, log_stack, prefix, with_bus=True):
+        """The keyed AIR-set proof (with_bus) or zero-check of the key's AIRs on the device traces (as for Context.airset_prove) after a
+        fresh transcript observed `prefix`.  Returns (root (8 words), proof words), canonical numpy uint32; check with airkey_verify."""
+        ctx = self.ctx
+        words = airkey_proof_words(self.params, self.airs, log_stack, self.log_stack_prep, with_bus)
+        tr = Transcript(ctx)
+        pre = np.ascontiguousarray(prefix, dtype=np.uint32)
+        if pre.size:
+            tr.observe(pre)
+        tp = (C.c_void_p * len(traces))(*[t.data_ptr() for t in traces])
+        pa, keep = _pvs_array(pvs)
+        proof = np.zeros(max(words, 1), dtype=np.uint32)
+        root = np.zeros(8, dtype=np.uint32)
+        rc = ctx.lib.zkhip_airkey_prove(ctx.h, self.h, int(bool(with_bus)), tp, pa, log_stack, tr.h, _u32p(proof), proof.size, _u32p(root))
+        tr.close()
+        ctx._check(rc)
+        return root, proof[:words]
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.zkhip_airkey_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _uip(arr):
     return arr.ctypes.data_as(C.POINTER(C.c_uint))
 
@@ -1454,6 +1508,33 @@ def airset_verify(params, prefix, airs, pvs, log_stack, proof):
     (root of the trace commitment (8 canonical words), (P, Q) of the fraction sum (8 canonical words)); raises ZkhipError (its `code`
     is the library's status)."""
     return tuple(_air_verify("zkhip_airset", params, prefix, airs, pvs, log_stack, proof, 2))
+
+
+def airkey_proof_words(params, airs, log_stack, log_stack_prep, with_bus=True):
+    """words of a keyed proof of these AIR shapes (`prep` is not read); 0 for a refused shape"""
+    arr, keep = _air_structs([{k: v for k, v in a.items() if k != "prep"} for a in airs])
+    return int(load_library().zkhip_airkey_proof_words(C.byref(params), arr, len(airs), log_stack, log_stack_prep, int(bool(with_bus))))
+
+
+def airkey_verify(params, prefix, airs, prep_root, log_stack_prep, pvs, log_stack, proof, with_bus=True):
+    """Host verifier of a keyed proof (needs no GPU, never reads `prep`): a fresh challenger observes `prefix`, then prep_root, then the
+    proof is replayed and the key's opening checked against prep_root.  Returns the root of the trace commitment (with_bus: (root,
+    (P, Q))); raises ZkhipError (its `code` is the library's status)."""
+    lib = load_library()
+    pre, pw = _gkr_words(prefix, proof)
+    arr, keep = _air_structs([{k: v for k, v in a.items() if k != "prep"} for a in airs])
+    pa, keep2 = _pvs_array(pvs)
+    pr = np.ascontiguousarray(prep_root, dtype=np.uint32).reshape(-1)
+    if pr.size != 8:
+        raise ZkhipError("airkey_verify: prep_root holds 8 words")
+    root, pq = np.zeros(8, dtype=np.uint32), np.zeros(8, dtype=np.uint32)
+    rc = lib.zkhip_airkey_verify(C.byref(params), _u32p(pre), pre.size, arr, len(airs), _u32p(pr), log_stack_prep, pa, log_stack,
+                                 int(bool(with_bus)), _u32p(pw), pw.size, _u32p(root), _u32p(pq))
+    if rc != 0:
+        e = ZkhipError("zkhip_airkey_verify refused the proof (%d)" % rc)
+        e.code = rc
+        raise e
+    return (root, pq) if with_bus else root
 
 
 def whir_proof_words(params, m, n_cols):

@@ -13,9 +13,29 @@
 // result stays on the device), the blocks' eq factors and the roots' coefficients from rho, kappa and beta (k_as_coefs), the per-AIR
 // leaf claims in one pass over the leaf buffers (k_as_claims, k_as_claims_out); an AIR with interactions then runs
 // zc_prove_air<true>.  One prover frame, one host verifier (at the end of the file) and one shape serve both proofs.
+//
+// The keyed form of both (zkhip_airkey_*, with_bus = 0 / 1): the preprocessed columns of the set are ONE stacked WHIR commitment made at
+// key generation (zkhip_airkey: the columns resident in Montgomery form, the commitment, its root); both sides observe the root before
+// the main root; a PREP leaf is proven like a main cell (the kernels' PREP form reads the key's columns); the values v_p, v_p' and u_p
+// follow v, v' and u; a second stacked opening, of the key's commitment, follows the main one.  Keyed proof words:
+//   [root 8 | with_bus: GKR words for L | with_bus: 4 per AIR with interactions |
+//    per active AIR 4 D_a m + 4 (w + n_rot + w_p + n_rot_p) (+ 8 m + 4 (w + w_p) if n_rot + n_rot_p > 0) |
+//    zkhip_stack_proof_words(main columns, log_stack) | zkhip_stack_proof_words(preprocessed columns, log_stack_prep)]
 #include <map>
 
 #include "zerocheck_dev.hpp"
+
+// the key of the keyed proofs: made once by zkhip_airkey_create, read by every zkhip_airkey_prove
+struct zkhip_airkey {
+    zkhip_whir_params params{};
+    unsigned l_prep = 0;
+    std::vector<std::vector<uint32_t>> programs;   // copies: the caller's need not outlive the call
+    std::vector<zkhip_air> airs;                   // program -> programs[a]; prep_trace and prep_commit null
+    uint32_t* d_prep = nullptr;                    // every preprocessed column end to end, Montgomery, AIRs in caller order
+    std::vector<size_t> prep_at;                   // AIR -> its first word in d_prep
+    zkhip_stack_commitment* sc = nullptr;          // the stacked commitment of those columns at l_prep
+    uint32_t root[8] = {};
+};
 
 namespace zk {
 
@@ -28,6 +48,7 @@ struct AsBlock {
     const uint32_t* pvs;     // Montgomery
     const uint32_t* code;    // the interaction's operand program: roots = its fields, then its count
     const uint32_t* consts;
+    const uint32_t* prep;    // PREP: the AIR's preprocessed columns in the key, stride 2^m, Montgomery (null: none)
     uint64_t off, n;         // first leaf, leaves
     uint32_t n_ins, bus1, sign, n_fields, pad;
     uint32_t first_wg;       // its first workgroup in the flattened grid
@@ -55,6 +76,8 @@ __device__ __forceinline__ uint32_t as_block_of(const AsBlock* __restrict__ blk,
 
 // num = +-count and den = gamma + bus + 1 + sum_i beta^(i+1) f_i of one row of one block, straight into the sorted layout; the
 // padding's leaves are (0, 1).  The operand program is k_logup_denoms' form: ASSERT k < n_fields is field k, the last one the count.
+// PREP (the keyed proofs): an operand may be a cell of the key's columns.
+template <bool PREP>
 __global__ __launch_bounds__(AS_BS) void k_as_leaves(const AsBlock* __restrict__ blk, uint32_t n_blk, const uint32_t* __restrict__ lchal,
                                                      uint32_t* __restrict__ num, uint32_t* __restrict__ den) {
     extern __shared__ uint32_t as_slots[];   // [slot][lane]
@@ -72,6 +95,7 @@ __global__ __launch_bounds__(AS_BS) void k_as_leaves(const AsBlock* __restrict__
     uint32_t cnt = 0;
     auto fetch = [&](uint32_t w) -> uint32_t {
         const uint32_t idx = w & 0x07ffffffu;
+        if (PREP && (w >> 28) == K_PREP) return b.prep[(size_t)idx * b.n + r];
         switch (w >> 28) {
             case K_SLOT: return as_slots[idx * AS_BS + tid];
             case K_VAR: return b.trace[(size_t)idx * b.n + r];
@@ -177,16 +201,27 @@ struct Shape {
     std::vector<size_t> b_at;    // per AIR: its place among the AIRs with interactions, or -1
     unsigned L = 0;
     size_t n_bus = 0, gkr_words = 0;
+    // keyed only: the key's stacked columns (the preprocessed columns, AIRs in caller order), one point per AIR that has some
+    std::vector<unsigned> lh_p, col_point_p, dims_p;
+    std::vector<size_t> prep_airs;   // the AIRs with preprocessed columns
+    size_t main_words = 0;           // the main stacked opening's words (the key's opening follows it)
 };
 // false = refused.  Without with_bus the AIRs' interactions are ignored: their plans have no bus roots (and another D).
-bool shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus, Shape* S) {
+// l_prep >= 0: the keyed form at log_stack_prep = l_prep
+bool shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus, Shape* S, int l_prep = -1) {
+    const bool keyed = l_prep >= 0;
     if (!prm || !airs || n_airs < 1 || n_airs > ZKHIP_STACK_MAX_POINTS) return false;
     S->plans.resize(n_airs);
     std::vector<AirProgram> progs;
     size_t n_cols = 0;
     for (size_t a = 0; a < n_airs; a++) {
         ZcPlan& pl = S->plans[a];
-        if (!zc_plan(airs[a], &pl, with_bus)) return false;
+        if (!zc_plan(airs[a], &pl, with_bus, keyed)) return false;
+        if (pl.wp) {
+            S->dims_p.push_back(pl.m);
+            for (size_t c = 0; c < pl.wp; c++) S->lh_p.push_back(pl.m), S->col_point_p.push_back((unsigned)S->prep_airs.size());
+            S->prep_airs.push_back(a);
+        }
         n_cols += airs[a].width;
         if (n_cols > ZKHIP_STACK_MAX_COLS) return false;
         S->head += pl.active() ? pl.words() : 0;
@@ -211,7 +246,13 @@ bool shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, u
     }
     const size_t sw = zkhip_stack_proof_words(prm, S->lh.data(), S->lh.size(), l);
     if (!sw) return false;
-    S->total = S->head + sw;
+    S->main_words = sw, S->total = S->head + sw;
+    if (keyed) {
+        if (S->prep_airs.empty()) return false;   // no PREP anywhere: the unkeyed calls' case
+        const size_t sp = zkhip_stack_proof_words(prm, S->lh_p.data(), S->lh_p.size(), (unsigned)l_prep);
+        if (!sp) return false;
+        S->total += sp;
+    }
     return true;
 }
 
@@ -220,7 +261,7 @@ bool shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, u
 // the fraction-sum proof (its words to dP + 8), the leaf claims B_a (after them), and per AIR with interactions what its joint
 // sum-check needs (bus[a]).  Its buffers are B's: they live until the caller's per-AIR loop is done.
 int prove_bus(zkhip_ctx* ctx, const Shape& S, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces, const uint32_t* const* pvs,
-              DevTranscript* d_t, DevBufs& B, uint32_t* dP, std::vector<ZcBus>* bus) {
+              DevTranscript* d_t, DevBufs& B, uint32_t* dP, std::vector<ZcBus>* bus, const zkhip_airkey* key) {
     hipStream_t st = ctx->stream;
     const unsigned L = S.L;
     const size_t n_blk = S.blocks.size(), NL = (size_t)1 << L;
@@ -303,6 +344,7 @@ int prove_bus(zkhip_ctx* ctx, const Shape& S, const zkhip_air* airs, size_t n_ai
             const AsBlk& k = S.blocks[b];
             const Interaction& it = S.plans[k.a].prog.ints[k.j];
             d.trace = d_traces[k.a], d.pvs = d_up + o_pvs + pv_at[k.a];
+            d.prep = key && S.plans[k.a].wp ? key->d_prep + key->prep_at[k.a] : nullptr;
             d.code = d_up + 3 * low[b].code_at, d.consts = d_up + o_consts + low[b].const_at;
             d.off = k.off, d.n = (uint64_t)1 << k.m;
             d.n_ins = (uint32_t)low[b].n_ins, d.bus1 = to_monty(it.bus + 1), d.sign = it.sign, d.n_fields = it.n_fields;
@@ -327,8 +369,12 @@ int prove_bus(zkhip_ctx* ctx, const Shape& S, const zkhip_air* airs, size_t n_ai
     }
     {
         KernelScope ks(ctx, "as_leaves");
-        hipLaunchKernelGGL(k_as_leaves, dim3((unsigned)wg), dim3(AS_BS), (size_t)max_slots * AS_BS * 4, st, (const AsBlock*)d_blk, (uint32_t)(n_blk + 1),
-                           (const uint32_t*)lchal, d_num, d_den);
+        if (key)
+            hipLaunchKernelGGL(k_as_leaves<true>, dim3((unsigned)wg), dim3(AS_BS), (size_t)max_slots * AS_BS * 4, st, (const AsBlock*)d_blk,
+                               (uint32_t)(n_blk + 1), (const uint32_t*)lchal, d_num, d_den);
+        else
+            hipLaunchKernelGGL(k_as_leaves<false>, dim3((unsigned)wg), dim3(AS_BS), (size_t)max_slots * AS_BS * 4, st, (const AsBlock*)d_blk,
+                               (uint32_t)(n_blk + 1), (const uint32_t*)lchal, d_num, d_den);
     }
     ZK_HIP_CHECK(ctx, hipGetLastError());
     // 4. the fraction-sum proof; its words, rho and the claims stay on the device
@@ -366,12 +412,15 @@ int prove_bus(zkhip_ctx* ctx, const Shape& S, const zkhip_air* airs, size_t n_ai
     return ZKHIP_OK;
 }
 
-// either proof: with_bus, the AIR-set proof of docs/airset.md (its step numbers below); without, the zero-check of docs/zerocheck.md
+// either proof: with_bus, the AIR-set proof of docs/airset.md (its step numbers below); without, the zero-check of docs/zerocheck.md.
+// key: the keyed form (prm, airs and n_airs are the key's)
 int prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
-          const uint32_t* const* pvs, unsigned l, bool with_bus, DevTranscript* d_t, uint32_t* proof_out, size_t cap, uint32_t* root_out) {
-    const std::string who = with_bus ? "airset: " : "zerocheck: ";
+          const uint32_t* const* pvs, unsigned l, bool with_bus, DevTranscript* d_t, uint32_t* proof_out, size_t cap, uint32_t* root_out,
+          const zkhip_airkey* key = nullptr) {
+    const std::string who = key ? "airkey: " : with_bus ? "airset: " : "zerocheck: ";
     Shape S;
-    if (!shape(prm, airs, n_airs, l, with_bus, &S)) return set_error(ctx, ZKHIP_ERR_INVALID, who + "the shape does not fit the limits");
+    if (!shape(prm, airs, n_airs, l, with_bus, &S, key ? (int)key->l_prep : -1))
+        return set_error(ctx, ZKHIP_ERR_INVALID, who + "the shape does not fit the limits");
     if (cap < S.total) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, who + "proof buffer too small");
     size_t n_pv = 0, pt_words = 0;
     for (size_t a = 0; a < n_airs; a++) {
@@ -393,20 +442,26 @@ int prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, s
     ZK_TRY(stack_commit(ctx, prm, cols.data(), S.lh.data(), cols.size(), l, &com.sc, root));
     DevBufs B(ctx);
     // device: [the words before the opening | the points r'_a (Montgomery)], then the root and the public values to observe
-    uint32_t *dP = B.get(S.head + pt_words), *d_obs = B.get(8 + n_pv);
+    uint32_t *dP = B.get(S.head + pt_words), *d_obs = B.get((key ? 16 : 8) + n_pv);
     if (!dP || !d_obs) return set_error(ctx, ZKHIP_ERR_NOMEM, who + "proof staging");
-    std::vector<uint32_t> obs(root, root + 8);
+    std::vector<uint32_t> obs;
+    if (key) obs.assign(key->root, key->root + 8);   // the key's root is observed, not sent
+    obs.insert(obs.end(), root, root + 8);
     for (size_t a = 0; a < n_airs; a++) obs.insert(obs.end(), pvs[a], pvs[a] + airs[a].n_pvs);
     ZK_TRY(zkhip_h2d(ctx, d_obs, obs.data(), obs.size() * 4));
     ZK_TRY(transcript_observe(ctx, d_t, d_obs, (uint32_t)obs.size(), true));
     // 2. - 5. the bus part
     std::vector<ZcBus> bus(n_airs);   // E2 null: an AIR without interactions, or the zero-check
-    if (with_bus) ZK_TRY(prove_bus(ctx, S, airs, n_airs, d_traces, pvs, d_t, B, dP, &bus));
+    if (with_bus) ZK_TRY(prove_bus(ctx, S, airs, n_airs, d_traces, pvs, d_t, B, dP, &bus, key));
     // 6. - 8. per AIR
     size_t off = 8 + S.gkr_words + 4 * S.n_bus, poff = S.head;
     for (size_t a = 0; a < n_airs; a++) {
         const ZcPlan& pl = S.plans[a];
-        if (bus[a].E2) ZK_TRY(zc_prove_air<true>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff, bus[a]));
+        if (key && pl.wp) {   // the kernels' PREP form, on the key's resident columns
+            const uint32_t* prep = key->d_prep + key->prep_at[a];
+            if (bus[a].E2) ZK_TRY((zc_prove_air<true, true>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff, bus[a], prep)));
+            else ZK_TRY((zc_prove_air<false, true>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff, ZcBus{}, prep)));
+        } else if (bus[a].E2) ZK_TRY(zc_prove_air<true>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff, bus[a]));
         else ZK_TRY(zc_prove_air<false>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff));
         off += pl.active() ? pl.words() : 0;
         poff += 4 * (size_t)pl.m;
@@ -416,6 +471,14 @@ int prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, s
     ZK_TRY(zkhip_d2h(ctx, h.data(), dP, h.size() * 4));
     for (size_t i = S.head; i < h.size(); i++) h[i] = from_monty(h[i]);
     ZK_TRY(stack_open(ctx, com.sc, d_t, h.data() + S.head, S.dims.data(), n_airs, S.col_point.data(), nullptr, proof_out + S.head, cap - S.head));
+    if (key) {   // the key's commitment at the points of the AIRs that have preprocessed columns
+        std::vector<uint32_t> pts;
+        size_t at = S.head;
+        for (size_t a = 0; a < n_airs; at += 4 * (size_t)S.plans[a].m, a++)
+            if (S.plans[a].wp) pts.insert(pts.end(), h.begin() + at, h.begin() + at + 4 * (size_t)S.plans[a].m);
+        const size_t o = S.head + S.main_words;
+        ZK_TRY(stack_open(ctx, key->sc, d_t, pts.data(), S.dims_p.data(), S.dims_p.size(), S.col_point_p.data(), nullptr, proof_out + o, cap - o));
+    }
     memcpy(proof_out, root, 32);
     memcpy(proof_out + 8, h.data() + 8, (S.head - 8) * 4);
     if (root_out) memcpy(root_out, root, 32);
@@ -424,10 +487,14 @@ int prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, s
 
 // ---- the host verifier ---------------------------------------------------------------------------------------------------------
 // of either proof; pq_out: the fraction sum's (P, Q), with_bus only
+// prep_root: the keyed form, checked against the key's root at l_prep
 int verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs, const uint32_t* const* pvs,
-           unsigned l, const uint32_t* proof, size_t words, bool with_bus, uint32_t* root_out, uint32_t* pq_out) {
+           unsigned l, const uint32_t* proof, size_t words, bool with_bus, uint32_t* root_out, uint32_t* pq_out, const uint32_t* prep_root = nullptr,
+           unsigned l_prep = 0) {
     Shape S;
-    if (!shape(prm, airs, n_airs, l, with_bus, &S)) return ZKHIP_ERR_INVALID;
+    if (!shape(prm, airs, n_airs, l, with_bus, &S, prep_root ? (int)l_prep : -1)) return ZKHIP_ERR_INVALID;
+    for (size_t i = 0; prep_root && i < 8; i++)
+        if (prep_root[i] >= P) return ZKHIP_ERR_INVALID;
     for (size_t a = 0; a < n_airs; a++) {
         if (airs[a].n_pvs && !pvs[a]) return ZKHIP_ERR_INVALID;
         for (size_t i = 0; i < airs[a].n_pvs; i++)
@@ -440,6 +507,7 @@ int verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix
         if (proof[i] >= P) return ZKHIP_ERR_VERIFY;
     HostChallenger ch;
     ch.observe_canon(prefix, n_prefix);
+    if (prep_root) ch.observe_canon(prep_root, 8);
     ch.observe_canon(proof, 8);
     for (size_t a = 0; a < n_airs; a++) ch.observe_canon(pvs[a], airs[a].n_pvs);
     const Ext one = ext_one();
@@ -480,10 +548,11 @@ int verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix
     }
     std::vector<uint32_t> points;                            // r'_a, canonical, end to end
     std::vector<const uint32_t*> claimed(n_airs, nullptr);   // the w values the opening must show (null: none claimed)
+    std::vector<const uint32_t*> claimed_p(n_airs, nullptr); // keyed: the w_p values the key's opening must show
     for (size_t a = 0; a < n_airs; a++) {
         const ZcPlan& pl = S.plans[a];
         const unsigned m = pl.m, D = pl.D;
-        const size_t w = pl.w, n_rot = pl.rot.size();
+        const size_t w = pl.w, n_rot = pl.rot.size(), wp = pl.wp, n_rot_p = pl.rot_p.size(), n_val = w + n_rot + wp + n_rot_p;
         const bool has_cons = !pl.proven.empty(), has_bus = !pl.bus_roots.empty();   // the zero-check's plans have no bus roots
         std::vector<Ext> rp(m);
         if (!pl.active()) {
@@ -518,38 +587,40 @@ int verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix
                 claim = poly_at(s, D, r[i]);
             }
             // 7. the values
-            std::vector<Ext> v(w), vn(n_rot);
+            std::vector<Ext> v(w), vn(n_rot), vp(wp), vpn(n_rot_p);   // v, v', v_p, v_p'
             for (size_t j = 0; j < w; j++) v[j] = ext_from_canon(q + 4 * j);
             for (size_t t = 0; t < n_rot; t++) vn[t] = ext_from_canon(q + 4 * (w + t));
-            ch.observe_canon(q, 4 * (w + n_rot));
+            for (size_t j = 0; j < wp; j++) vp[j] = ext_from_canon(q + 4 * (w + n_rot + j));
+            for (size_t t = 0; t < n_rot_p; t++) vpn[t] = ext_from_canon(q + 4 * (w + n_rot + wp + t));
+            ch.observe_canon(q, 4 * n_val);
             const uint32_t* qv = q;
-            q += 4 * (w + n_rot);
+            q += 4 * n_val;
             Ext first = one, last = one;
             for (unsigned j = 0; j < m; j++) first = ext_mul(first, ext_sub(one, r[j])), last = ext_mul(last, r[j]);
             Ext rhs = ext_zero();
             if (has_cons) {   // eq(tau, r) sum_k alpha^k C_k
-                const std::vector<Ext> val = zc_eval_host(pl, pl.reach, v.data(), vn.data(), first, last, pvs[a]);
+                const std::vector<Ext> val = zc_eval_host(pl, pl.reach, v.data(), vn.data(), first, last, pvs[a], vp.data(), vpn.data());
                 Ext c = ext_zero(), ap = one;
                 for (uint32_t k : pl.proven) c = ext_add(c, ext_mul(ap, val[k])), ap = ext_mul(ap, alpha);
                 rhs = ext_mul(eq_eval(tau.data(), r.data(), m), c);
             }
             if (has_bus) {   // eq(rho_a, r) sum_j (cc_j count_j + sum_i cf_{j,i} f_{j,i}), coef in pl.bus_roots' order
                 // parse_air: interaction operands read the current row only, so neither v' nor first / last enters
-                const std::vector<Ext> val = zc_eval_host(pl, pl.bus_reach, v.data(), vn.data(), first, last, pvs[a]);
+                const std::vector<Ext> val = zc_eval_host(pl, pl.bus_reach, v.data(), vn.data(), first, last, pvs[a], vp.data(), vpn.data());
                 Ext c = ext_zero();
                 for (size_t k = 0; k < coef.size(); k++) c = ext_add(c, ext_mul(coef[k], val[pl.bus_roots[k]]));
                 rhs = ext_add(rhs, ext_mul(eq_eval(rho.data(), r.data(), m), c));
             }
             if (!ext_eq(rhs, claim)) return ZKHIP_ERR_VERIFY;
             // 8. the rotation reduction
-            if (n_rot == 0) {
-                rp = r, claimed[a] = qv;
+            if (!pl.reduces()) {
+                rp = r, claimed[a] = qv, claimed_p[a] = wp ? qv + 4 * (w + n_rot) : nullptr;
             } else {
                 const Ext lambda = ch.sample_ext();
-                std::vector<Ext> lp(w + n_rot);
+                std::vector<Ext> lp(n_val);   // over [v | v' | v_p | v_p']
                 Ext x = one;
                 claim = ext_zero();
-                for (size_t j = 0; j < w + n_rot; j++) lp[j] = x, claim = ext_add(claim, ext_mul(x, j < w ? v[j] : vn[j - w])), x = ext_mul(x, lambda);
+                for (size_t j = 0; j < n_val; j++) lp[j] = x, claim = ext_add(claim, ext_mul(x, ext_from_canon(qv + 4 * j))), x = ext_mul(x, lambda);
                 for (unsigned i = 0; i < m; i++, q += 8) {
                     const Ext s0 = ext_from_canon(q), s2 = ext_from_canon(q + 4);
                     ch.observe_canon(q, 8);
@@ -560,8 +631,11 @@ int verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix
                 Ext ua = ext_zero(), ub = ext_zero();
                 for (size_t j = 0; j < w; j++) ua = ext_add(ua, ext_mul(lp[j], ext_from_canon(q + 4 * j)));
                 for (size_t t = 0; t < n_rot; t++) ub = ext_add(ub, ext_mul(lp[w + t], ext_from_canon(q + 4 * pl.rot[t])));
-                ch.observe_canon(q, 4 * w);
-                claimed[a] = q, q += 4 * w;
+                const uint32_t* qp = q + 4 * w;   // u_p
+                for (size_t j = 0; j < wp; j++) ua = ext_add(ua, ext_mul(lp[w + n_rot + j], ext_from_canon(qp + 4 * j)));
+                for (size_t t = 0; t < n_rot_p; t++) ub = ext_add(ub, ext_mul(lp[w + n_rot + wp + t], ext_from_canon(qp + 4 * pl.rot_p[t])));
+                ch.observe_canon(q, 4 * (w + wp));
+                claimed[a] = q, claimed_p[a] = wp ? qp : nullptr, q += 4 * (w + wp);
                 const Ext want = ext_add(ext_mul(ua, eq_eval(r.data(), rp.data(), m)), ext_mul(ub, zc_rot_eval(r.data(), rp.data(), m)));
                 if (!ext_eq(want, claim)) return ZKHIP_ERR_VERIFY;
             }
@@ -574,18 +648,85 @@ int verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix
     }
     // 9. the stacked opening
     const uint32_t* op = proof + S.head;
-    ZK_TRY(stack_verify_host(ch, prm, proof, S.lh.data(), S.lh.size(), l, points.data(), S.dims.data(), n_airs, S.col_point.data(), op, words - S.head));
+    ZK_TRY(stack_verify_host(ch, prm, proof, S.lh.data(), S.lh.size(), l, points.data(), S.dims.data(), n_airs, S.col_point.data(), op, S.main_words));
     size_t col = 0;
     for (size_t a = 0; a < n_airs; col += airs[a].width, a++)
         if (claimed[a] && memcmp(claimed[a], op + 4 * col, 16 * airs[a].width) != 0) return ZKHIP_ERR_VERIFY;
+    if (prep_root) {   // the key's opening, against the verifier's own root
+        std::vector<uint32_t> pts;
+        size_t at = 0;
+        for (size_t a = 0; a < n_airs; at += 4 * (size_t)S.plans[a].m, a++)
+            if (S.plans[a].wp) pts.insert(pts.end(), points.begin() + at, points.begin() + at + 4 * (size_t)S.plans[a].m);
+        const uint32_t* op2 = op + S.main_words;
+        ZK_TRY(stack_verify_host(ch, prm, prep_root, S.lh_p.data(), S.lh_p.size(), l_prep, pts.data(), S.dims_p.data(), S.dims_p.size(),
+                                 S.col_point_p.data(), op2, words - S.head - S.main_words));
+        col = 0;
+        for (size_t a = 0; a < n_airs; col += S.plans[a].wp, a++)
+            if (claimed_p[a] && memcmp(claimed_p[a], op2 + 4 * col, 16 * S.plans[a].wp) != 0) return ZKHIP_ERR_VERIFY;
+    }
     if (root_out) memcpy(root_out, proof, 32);
     if (pq_out) memcpy(pq_out, proof + 8, 32);
     return ZKHIP_OK;
 }
 
-size_t proof_words(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus) {
+size_t proof_words(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus, int l_prep = -1) {
     Shape S;
-    return shape(prm, airs, n_airs, l, with_bus, &S) ? S.total : 0;
+    return shape(prm, airs, n_airs, l, with_bus, &S, l_prep) ? S.total : 0;
+}
+
+// ---- the key ---------------------------------------------------------------------------------------------------------------------
+void airkey_destroy(zkhip_ctx* ctx, zkhip_airkey* key) {
+    if (!key) return;
+    stack_destroy(ctx, key->sc);   // synchronises
+    if (key->d_prep) (void)hipFree(key->d_prep);
+    delete key;
+}
+
+// reads zkhip_air::prep_trace (host, canonical, column-major), as zkhip_keygen does; the columns stay on the device in Montgomery form
+int airkey_create(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l_prep, zkhip_airkey** out,
+                  uint32_t* root_out) {
+    if (n_airs < 1 || n_airs > ZKHIP_STACK_MAX_POINTS) return set_error(ctx, ZKHIP_ERR_INVALID, "airkey: AIR count");
+    zkhip_airkey* key = new zkhip_airkey();
+    struct Guard {
+        zkhip_ctx* ctx;
+        zkhip_airkey* key;
+        ~Guard() { airkey_destroy(ctx, key); }
+    } guard{ctx, key};
+    key->params = *prm, key->l_prep = l_prep;
+    key->programs.resize(n_airs), key->airs.resize(n_airs), key->prep_at.assign(n_airs, 0);
+    std::vector<unsigned> lh;
+    std::vector<uint32_t> host;   // Montgomery
+    for (size_t a = 0; a < n_airs; a++) {
+        ZcPlan pl;   // the zero-check's plan: a set the bus form alone refuses (D, no interaction) is refused by the prove call
+        if (!zc_plan(airs[a], &pl, false, true)) return set_error(ctx, ZKHIP_ERR_INVALID, "airkey: the shape does not fit the limits");
+        key->programs[a].assign(airs[a].program, airs[a].program + airs[a].program_len);
+        key->airs[a] = airs[a];
+        key->airs[a].program = key->programs[a].data(), key->airs[a].prep_trace = nullptr, key->airs[a].prep_commit = nullptr;
+        key->prep_at[a] = host.size();
+        if (!pl.wp) continue;
+        if (!airs[a].prep_trace) return set_error(ctx, ZKHIP_ERR_INVALID, "airkey: a PREP AIR without a preprocessed trace");
+        const size_t cnt = pl.wp << pl.m;
+        for (size_t i = 0; i < cnt; i++) {
+            if (airs[a].prep_trace[i] >= P) return set_error(ctx, ZKHIP_ERR_INVALID, "airkey: preprocessed word not canonical");
+            host.push_back(to_monty(airs[a].prep_trace[i]));
+        }
+        lh.insert(lh.end(), pl.wp, pl.m);
+    }
+    if (lh.empty()) return set_error(ctx, ZKHIP_ERR_INVALID, "airkey: no AIR has a PREP section: use the unkeyed calls");
+    if (!zkhip_stack_width(prm, lh.data(), lh.size(), l_prep)) return set_error(ctx, ZKHIP_ERR_INVALID, "airkey: the preprocessed columns do not fit log_stack_prep");
+    if (hipMalloc(&key->d_prep, host.size() * 4) != hipSuccess) return set_error(ctx, ZKHIP_ERR_NOMEM, "airkey: the preprocessed columns do not fit");
+    ZK_TRY(zkhip_h2d(ctx, key->d_prep, host.data(), host.size() * 4));
+    std::vector<const uint32_t*> cols;
+    for (size_t a = 0, j = 0; a < n_airs; a++) {
+        ZcPlan pl;
+        (void)zc_plan(key->airs[a], &pl, false, true);
+        for (size_t c = 0; c < pl.wp; c++, j++) cols.push_back(key->d_prep + key->prep_at[a] + (c << pl.m));
+    }
+    ZK_TRY(stack_commit(ctx, prm, cols.data(), lh.data(), cols.size(), l_prep, &key->sc, key->root));   // synchronises
+    if (root_out) memcpy(root_out, key->root, 32);
+    guard.key = nullptr;
+    *out = key;
+    return ZKHIP_OK;
 }
 }  // namespace
 
@@ -617,6 +758,40 @@ int zkhip_airset_prove(zkhip_ctx* ctx, const zkhip_whir_params* params, const zk
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !params || !airs || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
     return prove(ctx, params, airs, n_airs, d_traces, pvs, log_stack, true, transcript->d, proof_out, cap, root_out);
+}
+
+int zkhip_airkey_create(zkhip_ctx* ctx, const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, unsigned log_stack_prep,
+                        zkhip_airkey** key_out, uint32_t* prep_root_out) {
+    ZK_BIND_DEVICE(ctx);
+    if (!ctx || !params || !airs || !key_out) return ZKHIP_ERR_INVALID;
+    return airkey_create(ctx, params, airs, n_airs, log_stack_prep, key_out, prep_root_out);
+}
+
+void zkhip_airkey_destroy(zkhip_ctx* ctx, zkhip_airkey* key) {
+    ZK_BIND_DEVICE(ctx);
+    airkey_destroy(ctx, key);
+}
+
+size_t zkhip_airkey_proof_words(const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, unsigned log_stack, unsigned log_stack_prep,
+                                int with_bus) {
+    if (log_stack_prep > ZKHIP_WHIR_MAX_LOG_N) return 0;
+    return proof_words(params, airs, n_airs, log_stack, with_bus != 0, (int)log_stack_prep);
+}
+
+int zkhip_airkey_prove(zkhip_ctx* ctx, zkhip_airkey* key, int with_bus, const uint32_t* const* d_traces, const uint32_t* const* pvs,
+                       unsigned log_stack, zkhip_transcript* transcript, uint32_t* proof_out, size_t cap, uint32_t* root_out) {
+    ZK_BIND_DEVICE(ctx);
+    if (!ctx || !key || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
+    return prove(ctx, &key->params, key->airs.data(), key->airs.size(), d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out, cap,
+                 root_out, key);
+}
+
+int zkhip_airkey_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
+                        const uint32_t* prep_root, unsigned log_stack_prep, const uint32_t* const* pvs, unsigned log_stack, int with_bus,
+                        const uint32_t* proof, size_t words, uint32_t* root_out, uint32_t* pq_out) {
+    if (!params || (n_prefix && !prefix) || !airs || !prep_root || !pvs || !proof || log_stack_prep > ZKHIP_WHIR_MAX_LOG_N) return ZKHIP_ERR_INVALID;
+    return verify(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, root_out, with_bus ? pq_out : nullptr, prep_root,
+                  log_stack_prep);
 }
 
 int zkhip_zerocheck_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,

@@ -5,6 +5,10 @@
 // The constraint kernels have a compile-time BUS form for the AIR-set proof: a second eq table (eq(rho_a, .)) and a second
 // coefficient set; an ASSERT whose number is at or above n_cons adds to a second combination, which the second eq factor multiplies.
 // With BUS = false they are the zero-check's kernels as they were.
+//
+// The keyed proofs (zkhip_airkey_*) run a second compile-time form, PREP: kernels of their own (k_zc_round0_p, k_zc_pass_p,
+// k_zc_combine_p) over the same bodies, which also read the key's resident preprocessed columns (ZcPrep).  With PREP = false the
+// bodies are the unkeyed kernels' code: every preprocessed read sits behind the compile-time flag.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -31,6 +35,13 @@ struct ZcProg {
     unsigned n_cons;          // BUS: an ASSERT numbered n_cons or above goes to the second combination
 };
 
+// PREP: the preprocessed columns of one AIR as the key holds them (device)
+struct ZcPrep {
+    const uint32_t* cols;   // wp columns of 2^m Montgomery words
+    const uint32_t* rot;    // the columns read with rotation 1, increasing
+    unsigned wp, n_rot;
+};
+
 // x^k for k < n
 static __global__ __launch_bounds__(256) void k_zc_pows(const uint32_t* __restrict__ x, unsigned n, uint32_t* __restrict__ out) {
     const Ext a = sc_ld(x, 0);
@@ -55,9 +66,9 @@ __device__ __forceinline__ uint32_t zc_small(unsigned t) { return mmul(t, MONTY_
 // ---- round 0: the base-field trace in place ------------------------------------------------------------------------------------
 // Pair y holds rows 2y and 2y + 1; a next-row cell is the same column one row on (mod n).  At the integer point t a cell's value is
 // the base element f0 + t (f1 - f0), so the program runs in the base field; the alpha-combination and the eq factor are extension.
-template <unsigned D, bool BUS>
-__global__ __launch_bounds__(ZC_W) void k_zc_round0(ZcProg pg, const uint32_t* __restrict__ trace, unsigned m, const uint32_t* __restrict__ E,
-                                                    const uint32_t* __restrict__ E2, uint32_t* __restrict__ partial) {
+template <unsigned D, bool BUS, bool PREP>
+__device__ __forceinline__ void zc_round0_body(const ZcProg& pg, const uint32_t* __restrict__ trace, const uint32_t* __restrict__ prep, unsigned m,
+                                               const uint32_t* __restrict__ E, const uint32_t* __restrict__ E2, uint32_t* __restrict__ partial) {
     extern __shared__ uint32_t zc_slots[];   // [slot][lane]
     const unsigned lane = threadIdx.x;
     const size_t n = (size_t)1 << m, n_pairs = n >> 1;
@@ -75,6 +86,12 @@ __global__ __launch_bounds__(ZC_W) void k_zc_round0(ZcProg pg, const uint32_t* _
             const uint32_t tm = zc_small(p ? p + 1 : 0);
             auto operand = [&](uint32_t w) -> uint32_t {
                 const uint32_t pay = w & 0x0fffffffu;
+                if (PREP && (w >> 28) == K_PREP) {   // a cell of the key's columns: K_VAR's pair and next-row addressing
+                    const size_t base = (size_t)(pay & 0x07ffffffu) * n;
+                    const bool rot = (pay >> 27) & 1u;
+                    const uint32_t f0 = prep[base + (rot ? x1 : x0)], f1 = prep[base + (rot ? x2 : x1)];
+                    return madd(f0, mmul(tm, msub(f1, f0)));
+                }
                 switch (w >> 28) {
                     case K_SLOT:
                         return zc_slots[pay * ZC_W + lane];
@@ -116,10 +133,21 @@ __global__ __launch_bounds__(ZC_W) void k_zc_round0(ZcProg pg, const uint32_t* _
     }
     zc_wave_out(acc, partial);
 }
+template <unsigned D, bool BUS>
+__global__ __launch_bounds__(ZC_W) void k_zc_round0(ZcProg pg, const uint32_t* __restrict__ trace, unsigned m, const uint32_t* __restrict__ E,
+                                                    const uint32_t* __restrict__ E2, uint32_t* __restrict__ partial) {
+    zc_round0_body<D, BUS, false>(pg, trace, nullptr, m, E, E2, partial);
+}
+template <unsigned D, bool BUS>
+__global__ __launch_bounds__(ZC_W) void k_zc_round0_p(ZcProg pg, const uint32_t* __restrict__ trace, const uint32_t* __restrict__ prep, unsigned m,
+                                                      const uint32_t* __restrict__ E, const uint32_t* __restrict__ E2, uint32_t* __restrict__ partial) {
+    zc_round0_body<D, BUS, true>(pg, trace, prep, m, E, E2, partial);
+}
 
 // ---- rounds >= 1: fold with the previous challenge and evaluate, one pass --------------------------------------------------------
-// The tables of a pass: [w columns | n_rot next-row tables | first | last | eq (| BUS: the second eq)], table t's entry j at tab + 4 (t stride + j).  From
-// the base trace (the first fold) the next-row tables are the rotated columns; after it they are tables of their own.
+// The tables of a pass: [w columns | n_rot next-row tables (| PREP: w_p preprocessed columns | their n_rot_p next-row tables) | first |
+// last | eq (| BUS: the second eq)], table t's entry j at tab + 4 (t stride + j).  From the base trace (the first fold) the next-row
+// tables are the rotated columns; after it they are tables of their own.
 struct ZcTabs {
     const uint32_t* trace;   // FROM_BASE: the trace (2^m rows), eq(tau, .) and the rotated columns' numbers
     const uint32_t* E;
@@ -133,8 +161,8 @@ struct ZcTabs {
     size_t nd;
 };
 
-template <bool FROM_BASE>
-__device__ __forceinline__ Ext zc_fold_entry(const ZcTabs& tb, unsigned t, size_t e, const Ext& r) {
+template <bool FROM_BASE, bool PREP>
+__device__ __forceinline__ Ext zc_fold_entry(const ZcTabs& tb, const ZcPrep& pp, unsigned t, size_t e, const Ext& r) {
     if (FROM_BASE) {
         const size_t n = (size_t)1 << tb.m, i0 = 2 * e, i1 = i0 + 1;
         if (t < tb.w + tb.n_rot) {
@@ -145,7 +173,18 @@ __device__ __forceinline__ Ext zc_fold_entry(const ZcTabs& tb, unsigned t, size_
             v.c[0] = madd(v.c[0], a);
             return v;
         }
-        const unsigned s = t - tb.w - tb.n_rot;
+        unsigned s = t - tb.w - tb.n_rot;
+        if (PREP) {
+            if (s < pp.wp + pp.n_rot) {   // the key's columns, addressed as the trace's
+                const bool rot = s >= pp.wp;
+                const size_t base = (size_t)(rot ? pp.rot[s - pp.wp] : s) * n;
+                const uint32_t a = pp.cols[base + (rot ? i1 : i0)], b = pp.cols[base + (rot ? ((i1 + 1) & (n - 1)) : i1)];
+                Ext v = ext_mul_base(r, msub(b, a));
+                v.c[0] = madd(v.c[0], a);
+                return v;
+            }
+            s -= pp.wp + pp.n_rot;
+        }
         if (s == 2) return sc_fold(sc_ld(tb.E, i0), sc_ld(tb.E, i1), r);
         if (s == 3) return sc_fold(sc_ld(tb.E2, i0), sc_ld(tb.E2, i1), r);
         const Ext one = ext_one();
@@ -156,10 +195,11 @@ __device__ __forceinline__ Ext zc_fold_entry(const ZcTabs& tb, unsigned t, size_
 }
 
 // partial null: fold only (the last fold, nd = 1).  Every thread evaluates the pair whose two entries it has just written.
-template <unsigned D, bool FROM_BASE, bool BUS>
-__global__ __launch_bounds__(ZC_W) void k_zc_pass(ZcProg pg, ZcTabs tb, const uint32_t* __restrict__ r_ptr, uint32_t* __restrict__ partial) {
+template <unsigned D, bool FROM_BASE, bool BUS, bool PREP>
+__device__ __forceinline__ void zc_pass_body(const ZcProg& pg, const ZcTabs& tb, const ZcPrep& pp, const uint32_t* __restrict__ r_ptr,
+                                             uint32_t* __restrict__ partial) {
     extern __shared__ uint4 zc_xslots[];   // [slot][lane]
-    const unsigned lane = threadIdx.x, nt = tb.w + tb.n_rot + (BUS ? 4 : 3), t_first = tb.w + tb.n_rot;
+    const unsigned lane = threadIdx.x, t_first = tb.w + tb.n_rot + (PREP ? pp.wp + pp.n_rot : 0u), nt = t_first + (BUS ? 4 : 3);
     const Ext r = sc_ld(r_ptr, 0), one = ext_one();
     const size_t n_pairs = tb.nd > 1 ? tb.nd >> 1 : 1;
     Ext acc[D];
@@ -167,8 +207,8 @@ __global__ __launch_bounds__(ZC_W) void k_zc_pass(ZcProg pg, ZcTabs tb, const ui
     for (unsigned e = 0; e < D; e++) acc[e] = ext_zero();
     for (size_t y = (size_t)blockIdx.x * ZC_W + lane; y < n_pairs; y += (size_t)gridDim.x * ZC_W) {
         for (unsigned t = 0; t < nt; t++) {
-            sc_st(tb.dst, t * tb.dst_stride + 2 * y, zc_fold_entry<FROM_BASE>(tb, t, 2 * y, r));
-            if (2 * y + 1 < tb.nd) sc_st(tb.dst, t * tb.dst_stride + 2 * y + 1, zc_fold_entry<FROM_BASE>(tb, t, 2 * y + 1, r));
+            sc_st(tb.dst, t * tb.dst_stride + 2 * y, zc_fold_entry<FROM_BASE, PREP>(tb, pp, t, 2 * y, r));
+            if (2 * y + 1 < tb.nd) sc_st(tb.dst, t * tb.dst_stride + 2 * y + 1, zc_fold_entry<FROM_BASE, PREP>(tb, pp, t, 2 * y + 1, r));
         }
         if (!partial) continue;
         const Ext e0 = sc_ld(tb.dst, (t_first + 2) * tb.dst_stride + 2 * y), e1 = sc_ld(tb.dst, (t_first + 2) * tb.dst_stride + 2 * y + 1);
@@ -224,6 +264,15 @@ __global__ __launch_bounds__(ZC_W) void k_zc_pass(ZcProg pg, ZcTabs tb, const ui
     if (!partial) return;   // uniform across the grid
     zc_wave_out(acc, partial);
 }
+template <unsigned D, bool FROM_BASE, bool BUS>
+__global__ __launch_bounds__(ZC_W) void k_zc_pass(ZcProg pg, ZcTabs tb, const uint32_t* __restrict__ r_ptr, uint32_t* __restrict__ partial) {
+    zc_pass_body<D, FROM_BASE, BUS, false>(pg, tb, ZcPrep{}, r_ptr, partial);
+}
+// PREP: the extension passes' code names the preprocessed tables in K_VAR operands (zc_prove_air's remap), so only the table count differs
+template <unsigned D, bool FROM_BASE, bool BUS>
+__global__ __launch_bounds__(ZC_W) void k_zc_pass_p(ZcProg pg, ZcTabs tb, ZcPrep pp, const uint32_t* __restrict__ r_ptr, uint32_t* __restrict__ partial) {
+    zc_pass_body<D, FROM_BASE, BUS, true>(pg, tb, pp, r_ptr, partial);
+}
 
 // entry 0 of the first `cnt` tables, canonical, to out[4 t ..]
 static __global__ __launch_bounds__(256) void k_zc_emit(const uint32_t* __restrict__ tab, size_t stride, unsigned cnt, uint32_t* __restrict__ out) {
@@ -231,16 +280,33 @@ static __global__ __launch_bounds__(256) void k_zc_emit(const uint32_t* __restri
 }
 
 // ---- the rotation reduction ------------------------------------------------------------------------------------------------------
-// F_a = sum_j lambda^j col_j and F_b = sum_t lambda^(w + t) col_{j_t} (k_whir_combine's pattern, the powers from a table)
-static __global__ __launch_bounds__(256) void k_zc_combine(const uint32_t* __restrict__ trace, size_t n, unsigned w, const uint32_t* __restrict__ rot,
-                                                    unsigned n_rot, const uint32_t* __restrict__ lpow, uint32_t* __restrict__ fa,
-                                                    uint32_t* __restrict__ fb) {
+// F_a = sum_j lambda^j col_j and F_b = sum_t lambda^(w + t) col_{j_t} (k_whir_combine's pattern, the powers from a table); PREP: the
+// powers run on over [v_p | v_p'], F_a gains the preprocessed columns and F_b the rotated ones
+template <bool PREP>
+__device__ __forceinline__ void zc_combine_body(const uint32_t* __restrict__ trace, size_t n, unsigned w, const uint32_t* __restrict__ rot, unsigned n_rot,
+                                                const ZcPrep& pp, const uint32_t* __restrict__ lpow, uint32_t* __restrict__ fa,
+                                                uint32_t* __restrict__ fb) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         Ext a = ext_zero(), b = ext_zero();
         for (unsigned j = 0; j < w; j++) a = ext_add(a, ext_mul_base(sc_ld(lpow, j), trace[(size_t)j * n + i]));
         for (unsigned t = 0; t < n_rot; t++) b = ext_add(b, ext_mul_base(sc_ld(lpow, w + t), trace[(size_t)rot[t] * n + i]));
+        if (PREP) {
+            const unsigned o = w + n_rot;
+            for (unsigned j = 0; j < pp.wp; j++) a = ext_add(a, ext_mul_base(sc_ld(lpow, o + j), pp.cols[(size_t)j * n + i]));
+            for (unsigned t = 0; t < pp.n_rot; t++) b = ext_add(b, ext_mul_base(sc_ld(lpow, o + pp.wp + t), pp.cols[(size_t)pp.rot[t] * n + i]));
+        }
         sc_st(fa, i, a), sc_st(fb, i, b);
     }
+}
+static __global__ __launch_bounds__(256) void k_zc_combine(const uint32_t* __restrict__ trace, size_t n, unsigned w, const uint32_t* __restrict__ rot,
+                                                    unsigned n_rot, const uint32_t* __restrict__ lpow, uint32_t* __restrict__ fa,
+                                                    uint32_t* __restrict__ fb) {
+    zc_combine_body<false>(trace, n, w, rot, n_rot, ZcPrep{}, lpow, fa, fb);
+}
+static __global__ __launch_bounds__(256) void k_zc_combine_p(const uint32_t* __restrict__ trace, size_t n, unsigned w, const uint32_t* __restrict__ rot,
+                                                      unsigned n_rot, ZcPrep pp, const uint32_t* __restrict__ lpow, uint32_t* __restrict__ fa,
+                                                      uint32_t* __restrict__ fb) {
+    zc_combine_body<true>(trace, n, w, rot, n_rot, pp, lpow, fa, fb);
 }
 
 // its four tables before the second round's fold writes them out: F_a, eq(r, .), F_b, rot(r, .)[x] = eq(r, .)[(x - 1) mod n]
@@ -302,20 +368,26 @@ struct ZcPlan {
     std::vector<uint32_t> rot;      // the columns the proven constraints read with rotation 1, increasing
     std::vector<int> rot_of;        // column -> its place in rot, or -1
     std::vector<char> reach;        // nodes the proven constraints reach
+    // the keyed proofs only (zc_plan keyed): the preprocessed width, the preprocessed columns read with rotation 1, increasing
+    size_t wp = 0;
+    std::vector<uint32_t> rot_p;
+    std::vector<int> rot_p_of;
     // the AIR-set proof only (zc_plan with_bus): the roots of the bus part, per interaction its count node, then its field nodes
     std::vector<uint32_t> bus_roots;
     std::vector<char> bus_reach;    // nodes the bus roots reach
     bool active() const { return D > 0; }
-    size_t words() const { return 4 * (size_t)D * m + 4 * w + 4 * rot.size() + (rot.empty() ? 0 : 8 * (size_t)m + 4 * w); }
+    bool reduces() const { return !rot.empty() || !rot_p.empty(); }
+    size_t words() const { return 4 * (size_t)D * m + 4 * (w + rot.size() + wp + rot_p.size()) + (reduces() ? 8 * (size_t)m + 4 * (w + wp) : 0); }
 };
 
-// with_bus: D = max(d_cons, d_bus) + 1 over the parts that exist, d_bus the largest degree of a count or field node
-bool zc_plan(const zkhip_air& a, ZcPlan* p, bool with_bus) {
+// with_bus: D = max(d_cons, d_bus) + 1 over the parts that exist, d_bus the largest degree of a count or field node.
+// keyed: a PREP section is taken, its cells are proven like main cells (degree 1); without it PREP is refused
+bool zc_plan(const zkhip_air& a, ZcPlan* p, bool with_bus, bool keyed = false) {
     if (!a.program || a.width < 1 || a.log_height < 1 || a.log_height > ZKHIP_WHIR_MAX_LOG_N) return false;
     if (parse_air(a.program, a.program_len, a.width, &p->prog, nullptr) != 0) return false;
     const AirProgram& g = p->prog;
-    if (g.prep_width || g.n_pvs != a.n_pvs) return false;
-    p->m = a.log_height, p->w = a.width;
+    if ((g.prep_width && !keyed) || g.n_pvs != a.n_pvs) return false;
+    p->m = a.log_height, p->w = a.width, p->wp = g.prep_width;
     // multilinear degrees in the row index (is_transition = 1 - is_last counts 1); a node that reaches a LogUp-phase leaf is not proven
     std::vector<unsigned> deg(g.n_nodes, 0);
     std::vector<char> later(g.n_nodes, 0);
@@ -323,6 +395,7 @@ bool zc_plan(const zkhip_air& a, ZcPlan* p, bool with_bus) {
         const uint32_t op = g.nodes[3 * i], x = g.nodes[3 * i + 1], y = g.nodes[3 * i + 2];
         switch (op) {
             case A_VAR:
+            case A_PREP:
             case A_FIRST:
             case A_LAST:
             case A_TRANS:
@@ -341,7 +414,7 @@ bool zc_plan(const zkhip_air& a, ZcPlan* p, bool with_bus) {
             case A_NEG:
                 deg[i] = deg[x], later[i] = later[x];
                 break;
-            default:   // PERM, CHAL, EXPOSED (PREP: refused above)
+            default:   // PERM, CHAL, EXPOSED
                 later[i] = 1;
         }
     }
@@ -349,11 +422,12 @@ bool zc_plan(const zkhip_air& a, ZcPlan* p, bool with_bus) {
     p->reach.assign(g.n_nodes, 0);
     for (uint32_t k = 0; k < g.n_cons; k++)
         if (!later[g.cons[k]]) p->proven.push_back(g.cons[k]), p->reach[g.cons[k]] = 1, d = std::max(d, deg[g.cons[k]]);
-    p->rot_of.assign(p->w, -1);
+    p->rot_of.assign(p->w, -1), p->rot_p_of.assign(p->wp, -1);
     for (uint32_t i = g.n_nodes; i-- > 0;) {
         if (!p->reach[i]) continue;
         const uint32_t op = g.nodes[3 * i], x = g.nodes[3 * i + 1], y = g.nodes[3 * i + 2];
         if (op == A_VAR && y == 1) p->rot_of[x] = 0;
+        if (op == A_PREP && y == 1) p->rot_p_of[x] = 0;
         if (op >= A_ADD && op <= A_NEG) {
             p->reach[x] = 1;
             if (op != A_NEG) p->reach[y] = 1;
@@ -361,6 +435,8 @@ bool zc_plan(const zkhip_air& a, ZcPlan* p, bool with_bus) {
     }
     for (size_t c = 0; c < p->w; c++)
         if (p->rot_of[c] == 0) p->rot_of[c] = (int)p->rot.size(), p->rot.push_back((uint32_t)c);
+    for (size_t c = 0; c < p->wp; c++)
+        if (p->rot_p_of[c] == 0) p->rot_p_of[c] = (int)p->rot_p.size(), p->rot_p.push_back((uint32_t)c);
     p->D = p->proven.empty() ? 0 : d + 1;
     if (with_bus && !g.ints.empty()) {
         unsigned d_bus = 0;
@@ -382,22 +458,29 @@ bool zc_plan(const zkhip_air& a, ZcPlan* p, bool with_bus) {
 }
 
 // ---- the device prover ---------------------------------------------------------------------------------------------------------
-template <unsigned D, bool BUS>
-void zc_launch_d(hipStream_t st, int which, unsigned grid, size_t lds, const ZcProg& pg, const ZcTabs& tb, const uint32_t* r, uint32_t* partial,
-                 DevTranscript* d_t, uint32_t* proof, uint32_t* r_out) {
-    if (which == 0) hipLaunchKernelGGL((k_zc_round0<D, BUS>), dim3(grid), dim3(ZC_W), lds, st, pg, tb.trace, tb.m, tb.E, tb.E2, partial);
-    else if (which == 1) hipLaunchKernelGGL((k_zc_pass<D, true, BUS>), dim3(grid), dim3(ZC_W), lds, st, pg, tb, r, partial);
-    else if (which == 2) hipLaunchKernelGGL((k_zc_pass<D, false, BUS>), dim3(grid), dim3(ZC_W), lds, st, pg, tb, r, partial);
-    else hipLaunchKernelGGL(k_sc_round_tr<4 * D>, dim3(1), dim3(64), 0, st, d_t, (const uint32_t*)partial, grid, proof, r_out);
+template <unsigned D, bool BUS, bool PREP>
+void zc_launch_d(hipStream_t st, int which, unsigned grid, size_t lds, const ZcProg& pg, const ZcTabs& tb, const ZcPrep& pp, const uint32_t* r,
+                 uint32_t* partial, DevTranscript* d_t, uint32_t* proof, uint32_t* r_out) {
+    if (which == 3) {
+        hipLaunchKernelGGL(k_sc_round_tr<4 * D>, dim3(1), dim3(64), 0, st, d_t, (const uint32_t*)partial, grid, proof, r_out);
+    } else if (PREP) {
+        if (which == 0) hipLaunchKernelGGL((k_zc_round0_p<D, BUS>), dim3(grid), dim3(ZC_W), lds, st, pg, tb.trace, pp.cols, tb.m, tb.E, tb.E2, partial);
+        else if (which == 1) hipLaunchKernelGGL((k_zc_pass_p<D, true, BUS>), dim3(grid), dim3(ZC_W), lds, st, pg, tb, pp, r, partial);
+        else hipLaunchKernelGGL((k_zc_pass_p<D, false, BUS>), dim3(grid), dim3(ZC_W), lds, st, pg, tb, pp, r, partial);
+    } else {
+        if (which == 0) hipLaunchKernelGGL((k_zc_round0<D, BUS>), dim3(grid), dim3(ZC_W), lds, st, pg, tb.trace, tb.m, tb.E, tb.E2, partial);
+        else if (which == 1) hipLaunchKernelGGL((k_zc_pass<D, true, BUS>), dim3(grid), dim3(ZC_W), lds, st, pg, tb, r, partial);
+        else hipLaunchKernelGGL((k_zc_pass<D, false, BUS>), dim3(grid), dim3(ZC_W), lds, st, pg, tb, r, partial);
+    }
 }
 // which: 0 = round 0, 1 = pass from the base trace, 2 = pass on tables, 3 = the transcript step (grid = the pass's workgroups)
-template <bool BUS>
-void zc_launch(unsigned D, hipStream_t st, int which, unsigned grid, size_t lds, const ZcProg& pg, const ZcTabs& tb, const uint32_t* r,
+template <bool BUS, bool PREP>
+void zc_launch(unsigned D, hipStream_t st, int which, unsigned grid, size_t lds, const ZcProg& pg, const ZcTabs& tb, const ZcPrep& pp, const uint32_t* r,
                uint32_t* partial, DevTranscript* d_t = nullptr, uint32_t* proof = nullptr, uint32_t* r_out = nullptr) {
     switch (D) {
 #define ZC_CASE(d) \
     case d:        \
-        return zc_launch_d<d, BUS>(st, which, grid, lds, pg, tb, r, partial, d_t, proof, r_out);
+        return zc_launch_d<d, BUS, PREP>(st, which, grid, lds, pg, tb, pp, r, partial, d_t, proof, r_out);
         ZC_CASE(1) ZC_CASE(2) ZC_CASE(3) ZC_CASE(4) ZC_CASE(5) ZC_CASE(6) ZC_CASE(7) ZC_CASE(8)
 #undef ZC_CASE
     }
@@ -410,12 +493,16 @@ struct ZcBus {
 };
 
 // one AIR's part: the words at dP (device, canonical), its point r' at d_rp (4 m Montgomery words).  BUS: the joint sum-check of
-// docs/airset.md on the proven constraints and pl.bus_roots (tau and alpha are sampled only if there are proven constraints)
-template <bool BUS>
+// docs/airset.md on the proven constraints and pl.bus_roots (tau and alpha are sampled only if there are proven constraints).
+// PREP (the keyed proofs): `prep` holds the key's pl.wp preprocessed columns of this AIR, Montgomery, stride 2^m; their values follow
+// v and v', and u_p follows u
+template <bool BUS, bool PREP = false>
 int zc_prove_air(zkhip_ctx* ctx, DevTranscript* d_t, const ZcPlan& pl, const uint32_t* trace, const uint32_t* pvs, uint32_t* dP, uint32_t* d_rp,
-                 const ZcBus& bus = ZcBus{}) {
+                 const ZcBus& bus = ZcBus{}, const uint32_t* prep = nullptr) {
     hipStream_t st = ctx->stream;
-    const unsigned m = pl.m, D = pl.D, w = (unsigned)pl.w, n_rot = (unsigned)pl.rot.size(), nt = w + n_rot + (BUS ? 4 : 3), n_cons = (unsigned)pl.proven.size();
+    const unsigned m = pl.m, D = pl.D, w = (unsigned)pl.w, n_rot = (unsigned)pl.rot.size(), n_cons = (unsigned)pl.proven.size();
+    const unsigned wp = PREP ? (unsigned)pl.wp : 0, n_rot_p = PREP ? (unsigned)pl.rot_p.size() : 0, n_val = w + n_rot + wp + n_rot_p;
+    const unsigned nt = n_val + (BUS ? 4 : 3);
     const size_t n = (size_t)1 << m;
     if (!pl.active()) return transcript_sample(ctx, d_t, d_rp, nullptr, 4 * m);
     std::vector<uint32_t> roots = pl.proven;
@@ -426,7 +513,7 @@ int zc_prove_air(zkhip_ctx* ctx, DevTranscript* d_t, const ZcPlan& pl, const uin
     if (compile_air(pl.prog, &ca, &err, &roots) != 0 || ca.n_slots > ZC_MAX_SLOTS)
         return set_error(ctx, ZKHIP_ERR_INVALID, "zerocheck: " + (err.empty() ? "the AIR needs more than 64 live intermediates" : err));
     const size_t n_code = ca.code.size(), n_ins = n_code / 3;
-    std::vector<uint32_t> up(2 * n_code + ca.consts.size() + pl.prog.n_pvs + n_rot);
+    std::vector<uint32_t> up(2 * n_code + ca.consts.size() + pl.prog.n_pvs + n_rot + n_rot_p);
     std::copy(ca.code.begin(), ca.code.end(), up.begin());
     for (size_t i = 0; i < n_ins; i++) {
         uint32_t* x = up.data() + n_code + 3 * i;
@@ -434,15 +521,18 @@ int zc_prove_air(zkhip_ctx* ctx, DevTranscript* d_t, const ZcPlan& pl, const uin
         for (int k = 1; k < 3; k++) {
             const uint32_t o = ca.code[3 * i + k];
             x[k] = (o >> 28) != K_VAR ? o : (K_VAR << 28) | (((o >> 27) & 1u) ? w + (uint32_t)pl.rot_of[o & 0x07ffffffu] : (o & 0x07ffffffu));
+            if (PREP && (o >> 28) == K_PREP)   // the preprocessed tables follow the main ones
+                x[k] = (K_VAR << 28) | (w + n_rot + (((o >> 27) & 1u) ? wp + (uint32_t)pl.rot_p_of[o & 0x07ffffffu] : (o & 0x07ffffffu)));
         }
     }
     uint32_t* hp = up.data() + 2 * n_code;
     std::copy(ca.consts.begin(), ca.consts.end(), hp), hp += ca.consts.size();
     for (uint32_t i = 0; i < pl.prog.n_pvs; i++) *hp++ = to_monty(pvs[i]);
-    std::copy(pl.rot.begin(), pl.rot.end(), hp);
+    hp = std::copy(pl.rot.begin(), pl.rot.end(), hp);
+    if (PREP) std::copy(pl.rot_p.begin(), pl.rot_p.end(), hp);
     DevBufs B(ctx);
     // challenges: [tau (4 m) | alpha (4) | r (4 m) | lambda (4)]
-    uint32_t *d_up = B.get(up.size()), *ch = B.get(8 * (size_t)m + 8), *apow = B.get(4 * (size_t)std::max(n_cons, w + n_rot));
+    uint32_t *d_up = B.get(up.size()), *ch = B.get(8 * (size_t)m + 8), *apow = B.get(4 * (size_t)std::max(n_cons, n_val));
     uint32_t *E = B.get(4 * n), *partial = B.get(4 * (size_t)ZKHIP_ZEROCHECK_MAX_DEGREE * SC_NB);
     uint32_t *tA = B.get(4 * (size_t)nt * (n / 2)), *tB = B.get(4 * (size_t)nt * std::max<size_t>(n / 4, 1));
     if (!d_up || !ch || !apow || !E || !partial || !tA || !tB) return set_error(ctx, ZKHIP_ERR_NOMEM, "zerocheck: the folded tables do not fit");
@@ -462,7 +552,8 @@ int zc_prove_air(zkhip_ctx* ctx, DevTranscript* d_t, const ZcPlan& pl, const uin
     ZcProg pgx = pg;
     pgx.code = d_up + n_code;
     ZcTabs tb{};
-    tb.trace = trace, tb.E = n_cons ? E : bus.E2, tb.E2 = bus.E2, tb.rot = d_up + up.size() - n_rot, tb.m = m, tb.w = w, tb.n_rot = n_rot;
+    tb.trace = trace, tb.E = n_cons ? E : bus.E2, tb.E2 = bus.E2, tb.rot = d_up + up.size() - n_rot - n_rot_p, tb.m = m, tb.w = w, tb.n_rot = n_rot;
+    const ZcPrep pp{prep, d_up + up.size() - n_rot_p, wp, n_rot_p};
     const size_t sA = n / 2, sB = std::max<size_t>(n / 4, 1);
     uint32_t* cur = nullptr;   // the tables the last pass wrote
     size_t cur_stride = 0;
@@ -472,41 +563,41 @@ int zc_prove_air(zkhip_ctx* ctx, DevTranscript* d_t, const ZcPlan& pl, const uin
         if (i == 0) {
             grid = grid_w(n / 2);
             KernelScope ks(ctx, "zc_round0");
-            zc_launch<BUS>(D, st, 0, grid, (size_t)ca.n_slots * ZC_W * 4, pg, tb, nullptr, partial);
+            zc_launch<BUS, PREP>(D, st, 0, grid, (size_t)ca.n_slots * ZC_W * 4, pg, tb, pp, nullptr, partial);
         } else {
             tb.nd = n >> i;
             tb.src = cur, tb.src_stride = cur_stride;
             tb.dst = cur == tA ? tB : tA, tb.dst_stride = tb.dst == tA ? sA : sB;
             grid = grid_w(tb.nd > 1 ? tb.nd / 2 : 1);
             KernelScope ks(ctx, "zc_pass");
-            zc_launch<BUS>(D, st, i == 1 ? 1 : 2, grid, (size_t)ca.n_slots * ZC_W * 16, pgx, tb, rs + 4 * (i - 1), fold_only ? nullptr : partial);
+            zc_launch<BUS, PREP>(D, st, i == 1 ? 1 : 2, grid, (size_t)ca.n_slots * ZC_W * 16, pgx, tb, pp, rs + 4 * (i - 1), fold_only ? nullptr : partial);
             cur = tb.dst, cur_stride = tb.dst_stride;
         }
         if (!fold_only) {
             KernelScope ks(ctx, "zc_round_tr");
-            zc_launch<BUS>(D, st, 3, grid, 0, pg, tb, nullptr, partial, d_t, dP + 4 * (size_t)D * i, rs + 4 * i);
+            zc_launch<BUS, PREP>(D, st, 3, grid, 0, pg, tb, pp, nullptr, partial, d_t, dP + 4 * (size_t)D * i, rs + 4 * i);
         }
         ZK_HIP_CHECK(ctx, hipGetLastError());
     }
-    uint32_t* dV = dP + 4 * (size_t)D * m;   // v, v'
+    uint32_t* dV = dP + 4 * (size_t)D * m;   // v, v' (PREP: v_p, v_p')
     {
         KernelScope ks(ctx, "zc_emit");
-        hipLaunchKernelGGL(k_zc_emit, dim3(1), dim3(256), 0, st, (const uint32_t*)cur, cur_stride, w + n_rot, dV);
+        hipLaunchKernelGGL(k_zc_emit, dim3(1), dim3(256), 0, st, (const uint32_t*)cur, cur_stride, n_val, dV);
     }
     ZK_HIP_CHECK(ctx, hipGetLastError());
-    ZK_TRY(transcript_observe(ctx, d_t, dV, 4 * (w + n_rot), true));
-    if (n_rot == 0) {
+    ZK_TRY(transcript_observe(ctx, d_t, dV, 4 * n_val, true));
+    if (n_rot + n_rot_p == 0) {
         ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_rp, rs, 16 * (size_t)m, hipMemcpyDeviceToDevice, st));
         return ZKHIP_OK;
     }
     // the rotation reduction: a degree-2 sum-check on F_a eq(r, .) + F_b rot(r, .), the folded tables in tA (4 x n/2) and tB (4 x n/4)
     uint32_t *fa = B.get(4 * n), *fb = B.get(4 * n);
     if (!fa || !fb) return set_error(ctx, ZKHIP_ERR_NOMEM, "zerocheck: the reduction's tables do not fit");
-    uint32_t* dR = dV + 4 * (w + n_rot);   // the reduction's rounds, then u
+    uint32_t* dR = dV + 4 * n_val;   // the reduction's rounds, then u (PREP: u_p)
     ZK_TRY(transcript_sample(ctx, d_t, lambda, nullptr, 4));
     {
         KernelScope ks(ctx, "zc_pows");
-        hipLaunchKernelGGL(k_zc_pows, dim3(1), dim3(256), 0, st, (const uint32_t*)lambda, w + n_rot, apow);
+        hipLaunchKernelGGL(k_zc_pows, dim3(1), dim3(256), 0, st, (const uint32_t*)lambda, n_val, apow);
     }
     {
         KernelScope ks(ctx, "zc_eq");
@@ -514,7 +605,8 @@ int zc_prove_air(zkhip_ctx* ctx, DevTranscript* d_t, const ZcPlan& pl, const uin
     }
     {
         KernelScope ks(ctx, "zc_combine");
-        hipLaunchKernelGGL(k_zc_combine, dim3(grid_of(n)), dim3(256), 0, st, trace, n, w, tb.rot, n_rot, (const uint32_t*)apow, fa, fb);
+        if (PREP) hipLaunchKernelGGL(k_zc_combine_p, dim3(grid_of(n)), dim3(256), 0, st, trace, n, w, tb.rot, n_rot, pp, (const uint32_t*)apow, fa, fb);
+        else hipLaunchKernelGGL(k_zc_combine, dim3(grid_of(n)), dim3(256), 0, st, trace, n, w, tb.rot, n_rot, (const uint32_t*)apow, fa, fb);
     }
     ZK_HIP_CHECK(ctx, hipGetLastError());
     const ZcRotSrc src{fa, fb, E, n - 1};
@@ -566,9 +658,10 @@ int zc_prove_air(zkhip_ctx* ctx, DevTranscript* d_t, const ZcPlan& pl, const uin
     {
         KernelScope ks(ctx, "zc_dot");
         hipLaunchKernelGGL(k_zc_dot, dim3(w), dim3(256), 0, st, trace, n, (const uint32_t*)E, dU);
+        if (wp) hipLaunchKernelGGL(k_zc_dot, dim3(wp), dim3(256), 0, st, prep, n, (const uint32_t*)E, dU + 4 * w);   // u_p: the key's columns
     }
     ZK_HIP_CHECK(ctx, hipGetLastError());
-    return transcript_observe(ctx, d_t, dU, 4 * w, true);
+    return transcript_observe(ctx, d_t, dU, 4 * (w + wp), true);
 }
 
 // ---- the host verifier ---------------------------------------------------------------------------------------------------------
@@ -584,9 +677,10 @@ Ext zc_rot_eval(const Ext* a, const Ext* b, unsigned m) {
     return acc;
 }
 
-// the nodes marked in `reach` (pl.reach or pl.bus_reach) on (v, v', first, last, pvs); the others stay 0
+// the nodes marked in `reach` (pl.reach or pl.bus_reach) on (v, v', first, last, pvs); the others stay 0.  A keyed plan's PREP leaves
+// read vp and vpn (v_p, v_p')
 std::vector<Ext> zc_eval_host(const ZcPlan& pl, const std::vector<char>& reach, const Ext* v, const Ext* vn, const Ext& first, const Ext& last,
-                              const uint32_t* pvs) {
+                              const uint32_t* pvs, const Ext* vp = nullptr, const Ext* vpn = nullptr) {
     const AirProgram& g = pl.prog;
     std::vector<Ext> val(g.n_nodes, ext_zero());
     for (uint32_t i = 0; i < g.n_nodes; i++) {
@@ -595,6 +689,9 @@ std::vector<Ext> zc_eval_host(const ZcPlan& pl, const std::vector<char>& reach, 
         switch (op) {
             case A_VAR:
                 val[i] = y ? vn[pl.rot_of[x]] : v[x];
+                break;
+            case A_PREP:
+                val[i] = y ? vpn[pl.rot_p_of[x]] : vp[x];
                 break;
             case A_PUB:
                 val[i] = ext_from_base(to_monty(pvs[x]));
