@@ -670,6 +670,28 @@ int zkhip_airset_verify(const zkhip_whir_params *params, const uint32_t *prefix,
                         const uint32_t *const *pvs, unsigned log_stack, const uint32_t *proof, size_t words, uint32_t *root_out,
                         uint32_t *pq_out);
 
+/* ---- the batched AIR-set proof (docs/airbatch.md): the statement of zkhip_airset_prove (with_bus = 1) or of zkhip_zerocheck_prove
+ *      (with_bus = 0) over the same stacked commitment, with ONE constraint sum-check and ONE rotation reduction for the whole set.
+ *      The active AIRs' summands are batched by the powers of a challenge mu and the weights 2^(M - m_a) over the M-cube (M = the
+ *      largest log_height of an active AIR, D = the largest D_a), so every AIR's point is a prefix of the same r; the reduction
+ *      batches the reducing AIRs by one lambda over M' rounds and ends in r'.  The serial rounds are M + M', not the sums of the
+ *      heights, and the device prover's launches and host round trips do not grow with n_airs.  This repository's own transcript.
+ *      Proof words: [root (8) | with_bus: GKR words for L, then 4 per AIR with interactions | 4 D M | per active AIR 4 (w + n_rot) |
+ *      if an AIR reduces: 8 M', then 4 w per reducing AIR | stacked opening].
+ *      Refused (ZKHIP_ERR_INVALID; zkhip_airbatch_proof_words returns 0): with_bus = 1, what zkhip_airset_* refuses; with_bus = 0,
+ *      what zkhip_zerocheck_* refuses; PREP in both (there is no keyed batched form). ---- */
+size_t zkhip_airbatch_proof_words(const zkhip_whir_params *params, const zkhip_air *airs, size_t n_airs, unsigned log_stack, int with_bus);
+/* Device prover; arguments as zkhip_airset_prove, plus with_bus.  One upload carries every AIR's programs and the job tables; the
+ * workspace of all AIRs is laid out once per call and freed (ZKHIP_ERR_NOMEM before any launch of the sum-check if it does not fit). */
+int zkhip_airbatch_prove(zkhip_ctx *ctx, const zkhip_whir_params *params, const zkhip_air *airs, size_t n_airs,
+                         const uint32_t *const *d_traces, const uint32_t *const *pvs, unsigned log_stack, int with_bus,
+                         zkhip_transcript *transcript, uint32_t *proof_out, size_t cap, uint32_t *root_out);
+/* Host verifier, needs no device.  root_out (8 canonical words) may be NULL; pq_out ((P, Q), 8 canonical words, may be NULL) is
+ * written with with_bus only, where P = 0 and Q != 0 are required. */
+int zkhip_airbatch_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const zkhip_air *airs, size_t n_airs,
+                          const uint32_t *const *pvs, unsigned log_stack, int with_bus, const uint32_t *proof, size_t words,
+                          uint32_t *root_out, uint32_t *pq_out);
+
 /* ---- the keyed form of both proofs (docs/airset.md, docs/zerocheck.md): AIR sets with preprocessed columns.  A key is ONE stacked
  *      WHIR commitment, at log_stack_prep, of all preprocessed columns of the set (AIRs in caller order, columns in column order, an
  *      AIR's columns at that AIR's height), made once; its root prep_root (8 canonical words) is the verifying-key entry.  Both sides

@@ -443,6 +443,15 @@ extern "C" {
     pub fn zkhip_zerocheck_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, airs: *const zkhip_air, n_airs: usize,
                                   pvs: *const *const u32, log_stack: c_uint, proof: *const u32, words: usize, root_out: *mut u32) -> c_int;
 
+    // the batched AIR-set proof: one constraint sum-check and one rotation reduction for the whole set (docs/airbatch.md)
+    pub fn zkhip_airbatch_proof_words(params: *const zkhip_whir_params, airs: *const zkhip_air, n_airs: usize, log_stack: c_uint,
+                                      with_bus: c_int) -> usize;
+    pub fn zkhip_airbatch_prove(ctx: *mut zkhip_ctx, params: *const zkhip_whir_params, airs: *const zkhip_air, n_airs: usize,
+                                d_traces: *const *const u32, pvs: *const *const u32, log_stack: c_uint, with_bus: c_int,
+                                transcript: *mut zkhip_transcript, proof_out: *mut u32, cap: usize, root_out: *mut u32) -> c_int;
+    pub fn zkhip_airbatch_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, airs: *const zkhip_air, n_airs: usize,
+                                 pvs: *const *const u32, log_stack: c_uint, with_bus: c_int, proof: *const u32, words: usize,
+                                 root_out: *mut u32, pq_out: *mut u32) -> c_int;
     // constraints and bus balance of an AIR set over one stacked commitment (docs/airset.md)
     pub fn zkhip_airset_proof_words(params: *const zkhip_whir_params, airs: *const zkhip_air, n_airs: usize, log_stack: c_uint) -> usize;
     pub fn zkhip_airset_prove(ctx: *mut zkhip_ctx, params: *const zkhip_whir_params, airs: *const zkhip_air, n_airs: usize,

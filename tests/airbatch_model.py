@@ -1,0 +1,313 @@
+"""Independent Python model of the batched AIR-set proof (docs/airbatch.md): the statement of the AIR-set proof (with_bus) or of the
+zero-check (without) over one stacked WHIR commitment, with ONE constraint sum-check and ONE rotation reduction for the whole set;
+every AIR's point is a prefix of the same r (and r').  Built on tests/airset_model.py and tests/zerocheck_model.py (the plans, the
+leaves, the leaf claims, the constants) and below them the GKR, stacking and WHIR models.  It imports nothing from the product.
+
+Conventions as in zerocheck_model: extension elements are lists of 4 canonical ints, a table of 2^m entries is indexed by
+i = sum b_j 2^j, variables are bound lowest first, words on the wire are canonical."""
+import airset_model as am
+import gkr_model as gm
+import stacking_model as sm
+import whir_model as wm
+import zerocheck_model as zm
+from pymodel import P, ext_add, ext_mul
+
+ZERO, ONE = wm.ZERO, wm.ONE
+Refused = zm.Refused
+
+
+def _ints(p):
+    return getattr(p, "ints", [])
+
+
+def shape(params, airs, l, with_bus):
+    """(plans, heights of the stacked columns, col_point, blocks, L): airset_model's shape with the bus part, zerocheck_model's
+    without (its plans have no interactions and D = d_cons + 1); raises Refused"""
+    if with_bus:
+        return am.shape(params, airs, l)
+    plans, heights, col_point = zm.shape(params, airs, l)
+    return plans, heights, col_point, [], 0
+
+
+def dims(plans):
+    """(active AIRs, M, D, reducing AIRs, M')"""
+    act = [a for a, p in enumerate(plans) if p.D > 0]
+    red = [a for a in act if plans[a].rot]
+    return (act, max([plans[a].m for a in act], default=0), max([plans[a].D for a in act], default=0), red,
+            max([plans[a].m for a in red], default=0))
+
+
+def proof_words(params, airs, l, with_bus=True):
+    try:
+        plans, heights, _, _, L = shape(params, airs, l, with_bus)
+    except Refused:
+        return 0
+    act, M, D, red, M2 = dims(plans)
+    n = 8 + (gm.proof_words(L) + 4 * sum(1 for p in plans if _ints(p)) if with_bus else 0) + 4 * D * M
+    n += sum(4 * (plans[a].w + len(plans[a].rot)) for a in act)
+    if red:
+        n += 8 * M2 + sum(4 * plans[a].w for a in red)
+    return n + sm.proof_words(params, heights, l)
+
+
+def pow2(k):
+    return gm.ext_c(pow(2, k, P))
+
+
+def summand(plan, v, pvs, apow, coef):
+    """g_a on one value of every table of the AIR: [w columns | n_rot next-row | first | last | eq(tau_a, .) if it has proven
+    constraints | eq(rho_a, .) if it has interactions]"""
+    w, nr = plan.w, len(plan.rot)
+    e, acc = w + nr + 2, ZERO
+    if plan.proven:
+        acc = ext_mul(plan.combine(v[:w], v[w:w + nr], v[w + nr], v[w + nr + 1], pvs, apow), v[e])
+        e += 1
+    if _ints(plan):
+        acc = ext_add(acc, ext_mul(plan.bus_combine(v[:w], pvs, coef), v[e]))
+    return acc
+
+
+def tables(plan, trace, tau, rho):
+    """the tables `summand` reads, over the AIR's own m variables (tau, rho: the common points; their prefixes are used)"""
+    n = 1 << plan.m
+    cols = [[gm.ext_c(int(v)) for v in c] for c in trace]
+    tabs = cols + [cols[j][1:] + [cols[j][0]] for j in plan.rot] + [[ONE] + [ZERO] * (n - 1), [ZERO] * (n - 1) + [ONE]]
+    if plan.proven:
+        tabs.append(gm.eq_table(tau[:plan.m]))
+    if _ints(plan):
+        tabs.append(gm.eq_table(rho[:plan.m]))
+    return tabs
+
+
+def _bus(ch, plans, blocks, L, traces, pvs, words, leaf_hook):
+    """steps 2 - 5 of docs/airset.md: (rho, per-AIR coefficients, per-AIR claim c_a or None, info)"""
+    gamma, beta = gm.bus_challenges(ch)
+    num, den = am.leaves(plans, blocks, L, traces, pvs, gamma, beta)
+    if leaf_hook:
+        leaf_hook(num, den)
+    gw, rho, claims = gm.prove(ch, num, den)
+    words += gw
+    eb = am.block_eq(blocks, rho)
+    kappa = ch.sample_ext()
+    B = am.leaf_claims(plans, blocks, eb, rho, num, den, kappa)
+    wm._observe(ch, [x for e in B for x in e], words)
+    coef = am.bus_coefs(plans, blocks, eb, beta, kappa)
+    with_ints = [a for a, p in enumerate(plans) if p.ints]
+    c = {a: wm.ext_sub(B[i], am.const_of(plans[a], a, blocks, eb, gamma, kappa)) for i, a in enumerate(with_ints)}
+    return rho, coef, c, dict(rho=rho, claims=claims, B=B, num=num, den=den, L=L, blocks=blocks)
+
+
+def prove(ch, params, airs, traces, pvs, l, with_bus=True, weighted=True, leaf_hook=None):
+    """The proof, continuing `ch` (after the caller's prefix): (root, words, info).  weighted=False (tests only): a prover that
+    batches with mu^j alone, without the 2^(M - m_a) weights.  leaf_hook: as airset_model.prove's.  info: the challenges, every round
+    polynomial at 0..D, the claims."""
+    plans, heights, col_point, blocks, L = shape(params, airs, l, with_bus)
+    n_airs = len(plans)
+    scom = sm.Commitment(params, [[int(v) % P for v in c] for tr in traces for c in tr], heights, l)
+    words = []
+    wm._observe(ch, list(scom.root), words)
+    for pv in pvs:
+        ch.observe([int(x) for x in pv])
+    rho, coef, c, info = [], [None] * n_airs, {}, {}
+    if with_bus:
+        rho, coef, c, info = _bus(ch, plans, blocks, L, traces, pvs, words, leaf_hook)
+    act, M, D, red, M2 = dims(plans)
+    # 6. one batched sum-check
+    tau, alpha = [], ZERO
+    if any(plans[a].proven for a in act):
+        tau = [ch.sample_ext() for _ in range(M)]
+        alpha = ch.sample_ext()
+    mu = ch.sample_ext()
+    mup = sm._powers(mu, max(len(act), 1))
+    apow = {a: sm._powers(alpha, max(len(plans[a].proven), 1)) for a in act}
+    tabs = {a: tables(plans[a], traces[a], tau, rho) for a in act}
+    wgt = {a: ext_mul(mup[j], pow2(M - plans[a].m) if weighted else ONE) for j, a in enumerate(act)}
+    g_end = {}   # a used-up AIR's g_a(r_a)
+    claim = ZERO
+    for j, a in enumerate(act):
+        claim = ext_add(claim, ext_mul(wgt[a], c.get(a, ZERO)))
+    info.update(tau=tau, alpha=alpha, mu=mu, claim0=claim, rounds=[], c=c)
+    r = []
+    for i in range(M):
+        s = [ZERO] * (D + 1)
+        for j, a in enumerate(act):
+            pl = plans[a]
+            if pl.m > i:
+                for t in range(D + 1):
+                    sa = ZERO
+                    for y in range(len(tabs[a][0]) // 2):
+                        sa = ext_add(sa, summand(pl, [zm._at(tb[2 * y], tb[2 * y + 1], t) for tb in tabs[a]], pvs[a], apow[a], coef[a]))
+                    s[t] = ext_add(s[t], ext_mul(wgt[a], sa))
+            else:   # used up: the constant mu^j 2^(M - 1 - i) g_a(r_a)
+                k = ext_mul(ext_mul(mup[j], pow2(M - 1 - i) if weighted else ONE), g_end[a])
+                s = [ext_add(x, k) for x in s]
+        info["rounds"].append(s)
+        wm._observe(ch, [x for t in [0] + list(range(2, D + 1)) for x in s[t]], words)
+        ri = ch.sample_ext()
+        r.append(ri)
+        for a in act:
+            if plans[a].m > i:
+                tabs[a] = zm._fold_all(tabs[a], ri)
+                if plans[a].m == i + 1:
+                    g_end[a] = summand(plans[a], [tb[0] for tb in tabs[a]], pvs[a], apow[a], coef[a])
+    # 7. the values
+    vals = {a: [tabs[a][k][0] for k in range(plans[a].w + len(plans[a].rot))] for a in act}
+    wm._observe(ch, [x for a in act for e in vals[a] for x in e], words)
+    info.update(r=r, g_end=g_end, values=vals)
+    # 8. one batched rotation reduction
+    rp = []
+    if red:
+        lam = ch.sample_ext()
+        lp = sm._powers(lam, sum(len(vals[a]) for a in red))
+        rt, o = {}, 0
+        for a in red:
+            pl, n = plans[a], 1 << plans[a].m
+            cols = [[gm.ext_c(int(v)) for v in col] for col in traces[a]]
+            fa, fb = [ZERO] * n, [ZERO] * n
+            for k in range(pl.w):
+                fa = [ext_add(x, ext_mul(lp[o + k], y)) for x, y in zip(fa, cols[k])]
+            for t, k in enumerate(pl.rot):
+                fb = [ext_add(x, ext_mul(lp[o + pl.w + t], y)) for x, y in zip(fb, cols[k])]
+            e = gm.eq_table(r[:pl.m])
+            rt[a] = [fa, e, fb, [e[(x - 1) % n] for x in range(n)]]
+            o += len(vals[a])
+        end = {}
+        for i in range(M2):
+            s0, s2 = ZERO, ZERO
+            for a in red:
+                if plans[a].m > i:
+                    x0, x2 = wm._sumcheck_round(rt[a][0], rt[a][1])
+                    y0, y2 = wm._sumcheck_round(rt[a][2], rt[a][3])
+                    k = pow2(M2 - plans[a].m)
+                    s0, s2 = ext_add(s0, ext_mul(k, ext_add(x0, y0))), ext_add(s2, ext_mul(k, ext_add(x2, y2)))
+                else:
+                    k = ext_mul(pow2(M2 - 1 - i), end[a])
+                    s0, s2 = ext_add(s0, k), ext_add(s2, k)
+            wm._observe(ch, s0 + s2, words)
+            ri = ch.sample_ext()
+            rp.append(ri)
+            for a in red:
+                if plans[a].m > i:
+                    rt[a] = zm._fold_all(rt[a], ri)
+                    if plans[a].m == i + 1:
+                        end[a] = ext_add(ext_mul(rt[a][0][0], rt[a][1][0]), ext_mul(rt[a][2][0], rt[a][3][0]))
+        u = [gm.mle_eval([gm.ext_c(int(v)) for v in col], rp[:plans[a].m]) for a in red for col in traces[a]]
+        wm._observe(ch, [x for e in u for x in e], words)
+    # 9. the points
+    points = []
+    for a, pl in enumerate(plans):
+        points.append(rp[:pl.m] if a in red else r[:pl.m] if pl.D > 0 else [ch.sample_ext() for _ in range(pl.m)])
+    info.update(rp=rp, points=points)
+    _, op = sm.open_(scom, ch, points, col_point)
+    return list(scom.root), words + op, info
+
+
+def verify(ch, params, airs, pvs, l, words, with_bus=True):
+    """Replays a proof on `ch` (after the caller's prefix).  Returns (root, (P, Q) or None); raises wm.WhirReject or gm.GkrReject
+    (Refused for a refused shape)."""
+    plans, heights, col_point, blocks, L = shape(params, airs, l, with_bus)
+    words = [int(x) for x in words]
+    if len(words) != proof_words(params, airs, l, with_bus) or any(x < 0 or x >= P for x in words):
+        raise wm.WhirReject("shape")
+    rd = wm._Reader(words)
+    root = rd.take(8)
+    ch.observe(root)
+    for pv in pvs:
+        ch.observe([int(x) for x in pv])
+    n_airs = len(plans)
+    rho, coef, c, pq = [], [None] * n_airs, {}, None
+    if with_bus:
+        gamma, beta = gm.bus_challenges(ch)
+        rho, (pstar, qstar), pq = gm.verify(ch, rd.take(gm.proof_words(L)), L)
+        if pq[0] != ZERO or pq[1] == ZERO:
+            raise gm.GkrReject("unbalanced")
+        eb = am.block_eq(blocks, rho)
+        kappa = ch.sample_ext()
+        with_ints = [a for a, p in enumerate(plans) if p.ints]
+        B = {a: rd.ext() for a in with_ints}
+        ch.observe([x for a in with_ints for x in B[a]])
+        lhs = ext_mul(kappa, ONE)
+        for e in eb:
+            lhs = wm.ext_sub(lhs, ext_mul(kappa, e))
+        for a in with_ints:
+            lhs = ext_add(lhs, B[a])
+        if lhs != ext_add(pstar, ext_mul(kappa, qstar)):
+            raise wm.WhirReject("leaf claims")
+        coef = am.bus_coefs(plans, blocks, eb, beta, kappa)
+        c = {a: wm.ext_sub(B[a], am.const_of(plans[a], a, blocks, eb, gamma, kappa)) for a in with_ints}
+    act, M, D, red, M2 = dims(plans)
+    tau, alpha = [], ZERO
+    if any(plans[a].proven for a in act):
+        tau = [ch.sample_ext() for _ in range(M)]
+        alpha = ch.sample_ext()
+    mu = ch.sample_ext()
+    mup = sm._powers(mu, max(len(act), 1))
+    claim = ZERO
+    for j, a in enumerate(act):
+        claim = ext_add(claim, ext_mul(ext_mul(mup[j], pow2(M - plans[a].m)), c.get(a, ZERO)))
+    r = []
+    for _ in range(M):
+        s = [rd.ext() for _ in range(D)]
+        ch.observe([x for e in s for x in e])
+        ri = ch.sample_ext()
+        claim = zm.interp([s[0], wm.ext_sub(claim, s[0])] + s[1:], ri)
+        r.append(ri)
+    vals = {a: [rd.ext() for _ in range(plans[a].w + len(plans[a].rot))] for a in act}
+    ch.observe([x for a in act for e in vals[a] for x in e])
+    rhs = ZERO
+    for j, a in enumerate(act):
+        pl = plans[a]
+        ra = r[:pl.m]
+        v = vals[a] + [zm.first_eval(ra), zm.last_eval(ra)]
+        if pl.proven:
+            v.append(gm.eq_eval(tau[:pl.m], ra))
+        if _ints(pl):
+            v.append(gm.eq_eval(rho[:pl.m], ra))
+        rhs = ext_add(rhs, ext_mul(mup[j], summand(pl, v, pvs[a], sm._powers(alpha, max(len(pl.proven), 1)), coef[a])))
+    if rhs != claim:
+        raise wm.WhirReject("batched sum-check claim")
+    rp, u = [], {}
+    if red:
+        lp = sm._powers(ch.sample_ext(), sum(len(vals[a]) for a in red))
+        claim, o, at = ZERO, 0, {}
+        for a in red:
+            at[a], acc = o, ZERO
+            for x in vals[a]:
+                acc = ext_add(acc, ext_mul(lp[o], x))
+                o += 1
+            claim = ext_add(claim, ext_mul(pow2(M2 - plans[a].m), acc))
+        for _ in range(M2):
+            s0, s2 = rd.ext(), rd.ext()
+            ch.observe(s0 + s2)
+            ri = ch.sample_ext()
+            claim = wm._quad(s0, wm.ext_sub(claim, s0), s2, ri)
+            rp.append(ri)
+        for a in red:
+            u[a] = [rd.ext() for _ in range(plans[a].w)]
+        ch.observe([x for a in red for e in u[a] for x in e])
+        want = ZERO
+        for a in red:
+            pl, ua, ub = plans[a], ZERO, ZERO
+            for k in range(pl.w):
+                ua = ext_add(ua, ext_mul(lp[at[a] + k], u[a][k]))
+            for t, k in enumerate(pl.rot):
+                ub = ext_add(ub, ext_mul(lp[at[a] + pl.w + t], u[a][k]))
+            ra, rpa = r[:pl.m], rp[:pl.m]
+            want = ext_add(want, ext_add(ext_mul(ua, gm.eq_eval(ra, rpa)), ext_mul(ub, zm.rot_eval(ra, rpa))))
+        if want != claim:
+            raise wm.WhirReject("rotation claim")
+    points, claimed = [], []
+    for a, pl in enumerate(plans):
+        if a in red:
+            points.append(rp[:pl.m]), claimed.append(u[a])
+        elif pl.D > 0:
+            points.append(r[:pl.m]), claimed.append(vals[a][:pl.w])
+        else:
+            points.append([ch.sample_ext() for _ in range(pl.m)]), claimed.append(None)
+    opened = sm.verify(ch, params, root, heights, l, points, col_point, words[rd.pos:])
+    col = 0
+    for pl, cl in zip(plans, claimed):
+        if cl is not None and opened[col:col + pl.w] != cl:
+            raise wm.WhirReject("opened values")
+        col += pl.w
+    return root, pq

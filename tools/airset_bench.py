@@ -1,4 +1,4 @@
-"""The AIR-set proof on the device (docs/airset.md): launches, kernel time per kernel name (the library's kernel stats,
+"""The AIR-set proof on the device (docs/airset.md) and its batched form (docs/airbatch.md, an `airbatch` row per shape): launches, kernel time per kernel name (the library's kernel stats,
 zkhip_profile_*), wall time and proof words of zkhip_airset_prove, split into the bus part (as_* and gkr_*), the sum-checks (zc_*) and
 commit plus opening (stack_*, whir_*), and beside it the fair comparison on the same key and the same library build: the two separate
 calls zkhip_zerocheck_prove plus zkhip_bus_gkr_prove (which prove less: their bus proof is not tied to the committed traces), and
@@ -54,7 +54,7 @@ KEYED = {"chipset42_keyed": 4}   # shape -> log_stack_prep
 def _group(by_name):
     g = {k: {"launches": 0, "ms": 0.0} for k in ("bus", "sumchecks", "commit_and_opening")}
     for n, v in by_name.items():
-        k = "bus" if n.startswith(("as_", "gkr_")) else "sumchecks" if n.startswith("zc_") else "commit_and_opening"
+        k = "bus" if n.startswith(("as_", "gkr_")) else "sumchecks" if n.startswith(("zc_", "zb_")) else "commit_and_opening"
         g[k]["launches"] += v["launches"]
         g[k]["ms"] = round(g[k]["ms"] + v["ms"], 3)
     return g
@@ -68,7 +68,7 @@ def main():
     a = ap.parse_args()
     zk = z.Context(0)
     prm = z.WhirParams.make(1, 4, 6, 16, 80)
-    out = {"airset": [], "zerocheck": [], "bus_gkr": [], "v1": [], "keyed": [], "keygen": []}
+    out = {"airbatch": [], "airset": [], "zerocheck": [], "bus_gkr": [], "v1": [], "keyed": [], "keygen": []}
 
     def note(r):
         print(json.dumps({k: v for k, v in r.items() if k != "by_name"}), file=sys.stderr)
@@ -111,6 +111,16 @@ def main():
             out["airset"].append(dict(common, refused=True))
             continue
         proof = {}
+
+        def airbatch():   # the batched form of the same statement (docs/airbatch.md), same build, same run
+            proof["b"] = zk.airbatch_prove(prm, vairs, d, pvs, l, [1])[1]
+
+        r = _profiled(zk, airbatch, a.reps)
+        z.airbatch_verify(prm, [1], vairs, pvs, l, proof["b"])
+        r.update(common, proof_words=z.airbatch_proof_words(prm, vairs, l), split=_group(r["by_name"]),
+                 zb_launches={n: v["launches"] for n, v in r["by_name"].items() if n.startswith("zb_")})
+        out["airbatch"].append(r)
+        note(r)
 
         def airset():
             proof["p"] = zk.airset_prove(prm, vairs, d, pvs, l, [1])[1]

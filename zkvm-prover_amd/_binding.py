@@ -334,6 +334,11 @@ def load_library():
                                          u32p]),
         "zkhip_airset_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, C.POINTER(_Air), sz, C.POINTER(u32p), C.c_uint, u32p, sz, u32p,
                                           u32p]),
+        "zkhip_airbatch_proof_words": (sz, [C.POINTER(WhirParams), C.POINTER(_Air), sz, C.c_uint, C.c_int]),
+        "zkhip_airbatch_prove": (C.c_int, [vp, C.POINTER(WhirParams), C.POINTER(_Air), sz, C.POINTER(vp), C.POINTER(u32p), C.c_uint, C.c_int, vp,
+                                           u32p, sz, u32p]),
+        "zkhip_airbatch_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, C.POINTER(_Air), sz, C.POINTER(u32p), C.c_uint, C.c_int, u32p, sz,
+                                            u32p, u32p]),
         "zkhip_airkey_create": (C.c_int, [vp, C.POINTER(WhirParams), C.POINTER(_Air), sz, C.c_uint, C.POINTER(vp), u32p]),
         "zkhip_airkey_destroy": (None, [vp, vp]),
         "zkhip_airkey_proof_words": (sz, [C.POINTER(WhirParams), C.POINTER(_Air), sz, C.c_uint, C.c_uint, C.c_int]),
@@ -1091,6 +1096,27 @@ class Context:
         self._check(rc)
         return root, proof[:words]
 
+    # ---- the batched AIR-set proof (docs/airbatch.md) --------------------------------------------------------------
+    def airbatch_prove(self, params, airs, traces, pvs, log_stack, prefix, with_bus=True):
+        """The statement of airset_prove (with_bus) or zerocheck_prove (without) with one constraint sum-check and one rotation
+        reduction for the whole set (arguments as airset_prove) after a fresh transcript observed `prefix`.  Returns (root (8 words),
+        proof words), canonical numpy uint32; check with airbatch_verify."""
+        words = airbatch_proof_words(params, airs, log_stack, with_bus)
+        arr, keep = _air_structs(airs)
+        tr = Transcript(self)
+        pre = np.ascontiguousarray(prefix, dtype=np.uint32)
+        if pre.size:
+            tr.observe(pre)
+        tp = (C.c_void_p * len(traces))(*[t.data_ptr() for t in traces])
+        pa, keep2 = _pvs_array(pvs)
+        proof = np.zeros(max(words, 1), dtype=np.uint32)
+        root = np.zeros(8, dtype=np.uint32)
+        rc = self.lib.zkhip_airbatch_prove(self.h, C.byref(params), arr, len(airs), tp, pa, log_stack, int(bool(with_bus)), tr.h, _u32p(proof),
+                                           proof.size, _u32p(root))
+        tr.close()
+        self._check(rc)
+        return root, proof[:words]
+
     # ---- the keyed form of both: AIR sets with preprocessed columns (docs/airset.md, docs/zerocheck.md) -------------
     def airkey(self, params, airs, log_stack_prep):
         """The key of `airs` (dicts as for ProvingKey; an AIR with a PREP section carries `prep`, canonical, [prep_width, 2^log_height]):
@@ -1508,6 +1534,29 @@ def airset_verify(params, prefix, airs, pvs, log_stack, proof):
     (root of the trace commitment (8 canonical words), (P, Q) of the fraction sum (8 canonical words)); raises ZkhipError (its `code`
     is the library's status)."""
     return tuple(_air_verify("zkhip_airset", params, prefix, airs, pvs, log_stack, proof, 2))
+
+
+def airbatch_proof_words(params, airs, log_stack, with_bus=True):
+    """words of a batched AIR-set proof of these AIR shapes; 0 for a refused shape"""
+    arr, keep = _air_structs(airs)
+    return int(load_library().zkhip_airbatch_proof_words(C.byref(params), arr, len(airs), log_stack, int(bool(with_bus))))
+
+
+def airbatch_verify(params, prefix, airs, pvs, log_stack, proof, with_bus=True):
+    """Host verifier of a batched AIR-set proof (needs no GPU): a fresh challenger observes `prefix`, then the proof is replayed.
+    Returns the root of the trace commitment (with_bus: (root, (P, Q))); raises ZkhipError (its `code` is the library's status)."""
+    lib = load_library()
+    pre, pw = _gkr_words(prefix, proof)
+    arr, keep = _air_structs(airs)
+    pa, keep2 = _pvs_array(pvs)
+    root, pq = np.zeros(8, dtype=np.uint32), np.zeros(8, dtype=np.uint32)
+    rc = lib.zkhip_airbatch_verify(C.byref(params), _u32p(pre), pre.size, arr, len(airs), pa, log_stack, int(bool(with_bus)), _u32p(pw), pw.size,
+                                   _u32p(root), _u32p(pq))
+    if rc != 0:
+        e = ZkhipError("zkhip_airbatch_verify refused the proof (%d)" % rc)
+        e.code = rc
+        raise e
+    return (root, pq) if with_bus else root
 
 
 def airkey_proof_words(params, airs, log_stack, log_stack_prep, with_bus=True):

@@ -21,9 +21,13 @@
 //   [root 8 | with_bus: GKR words for L | with_bus: 4 per AIR with interactions |
 //    per active AIR 4 D_a m + 4 (w + n_rot + w_p + n_rot_p) (+ 8 m + 4 (w + w_p) if n_rot + n_rot_p > 0) |
 //    zkhip_stack_proof_words(main columns, log_stack) | zkhip_stack_proof_words(preprocessed columns, log_stack_prep)]
+//
+// The batched form of both (zkhip_airbatch_*, docs/airbatch.md, model tests/airbatch_model.py; kernels in airbatch_dev.hpp): the same
+// statements with ONE constraint sum-check and ONE rotation reduction for the whole set, every AIR's point a prefix of the same r (r');
+// shape(), prove_bus() and the stacked opening are shared, prove_batch() and verify_batch() below are its own.
 #include <map>
 
-#include "zerocheck_dev.hpp"
+#include "airbatch_dev.hpp"
 
 // the key of the keyed proofs: made once by zkhip_airkey_create, read by every zkhip_airkey_prove
 struct zkhip_airkey {
@@ -261,7 +265,8 @@ bool shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, u
 // the fraction-sum proof (its words to dP + 8), the leaf claims B_a (after them), and per AIR with interactions what its joint
 // sum-check needs (bus[a]).  Its buffers are B's: they live until the caller's per-AIR loop is done.
 int prove_bus(zkhip_ctx* ctx, const Shape& S, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces, const uint32_t* const* pvs,
-              DevTranscript* d_t, DevBufs& B, uint32_t* dP, std::vector<ZcBus>* bus, const zkhip_airkey* key) {
+              DevTranscript* d_t, DevBufs& B, uint32_t* dP, std::vector<ZcBus>* bus, const zkhip_airkey* key,
+              const uint32_t** chal_out = nullptr) {
     hipStream_t st = ctx->stream;
     const unsigned L = S.L;
     const size_t n_blk = S.blocks.size(), NL = (size_t)1 << L;
@@ -326,6 +331,7 @@ int prove_bus(zkhip_ctx* ctx, const Shape& S, const zkhip_air* airs, size_t n_ai
     AsClaim* d_cl = (AsClaim*)B.get(S.n_bus * sizeof(AsClaim) / 4);
     if (!d_up || !ch || !lchal || !rho || !eb || !coef || !d_num || !d_den || !partial || !d_blk || !d_pos || !d_roots || !d_cl)
         return set_error(ctx, ZKHIP_ERR_NOMEM, "airset: the leaves do not fit");
+    if (chal_out) *chal_out = ch;   // the batched proof's round kernel reads gamma and kappa
     // one eq(rho[0..m), .) table per distinct height of an AIR with interactions
     std::map<unsigned, uint32_t*> eq_of;
     for (const AsBlk& k : S.blocks)
@@ -674,6 +680,497 @@ size_t proof_words(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n
     return shape(prm, airs, n_airs, l, with_bus, &S, l_prep) ? S.total : 0;
 }
 
+// ---- the batched proof (docs/airbatch.md) ---------------------------------------------------------------------------------------
+// The statement of either proof above with ONE constraint sum-check and ONE rotation reduction for the set: every AIR's point is a
+// prefix of the same r (r').  Steps 0 - 5 (plan, commit, the bus part) are the code above; the step numbers below are the document's.
+struct BatchShape {
+    Shape S;
+    std::vector<size_t> act, red;   // the active AIRs, the reducing ones among them, caller order
+    unsigned M = 0, D = 0, M2 = 0;  // the largest height and degree of an active AIR, the largest height of a reducing one
+    bool any_cons = false;
+    size_t o_rounds = 0, o_vals = 0, o_red = 0, o_u = 0, head = 0, total = 0;   // words; head: before the stacked opening
+};
+bool batch_shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus, BatchShape* T) {
+    if (!shape(prm, airs, n_airs, l, with_bus, &T->S)) return false;
+    size_t vals = 0, us = 0;
+    for (size_t a = 0; a < n_airs; a++) {
+        const ZcPlan& pl = T->S.plans[a];
+        if (!pl.active()) continue;
+        T->act.push_back(a);
+        T->M = std::max(T->M, pl.m), T->D = std::max(T->D, pl.D), T->any_cons |= !pl.proven.empty();
+        vals += 4 * (pl.w + pl.rot.size());
+        if (pl.reduces()) T->red.push_back(a), T->M2 = std::max(T->M2, pl.m), us += 4 * pl.w;
+    }
+    T->o_rounds = 8 + (with_bus ? T->S.gkr_words + 4 * T->S.n_bus : 0);
+    T->o_vals = T->o_rounds + 4 * (size_t)T->D * T->M;
+    T->o_red = T->o_vals + vals;
+    T->o_u = T->o_red + (T->red.empty() ? 0 : 8 * (size_t)T->M2);
+    T->head = T->o_u + us;
+    T->total = T->head + T->S.main_words;
+    return true;
+}
+
+// the device prover: one upload, one workspace, launches that do not grow with the number of AIRs
+int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
+                const uint32_t* const* pvs, unsigned l, bool with_bus, DevTranscript* d_t, uint32_t* proof_out, size_t cap, uint32_t* root_out) {
+    const std::string who = "airbatch: ";
+    hipStream_t st = ctx->stream;
+    BatchShape T;
+    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T)) return set_error(ctx, ZKHIP_ERR_INVALID, who + "the shape does not fit the limits");
+    const Shape& S = T.S;
+    if (cap < T.total) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, who + "proof buffer too small");
+    size_t n_pv = 0, inact_words = 0;
+    for (size_t a = 0; a < n_airs; a++) {
+        if (!d_traces[a] || (airs[a].n_pvs && !pvs[a])) return set_error(ctx, ZKHIP_ERR_INVALID, who + "null trace or public values");
+        for (size_t i = 0; i < airs[a].n_pvs; i++)
+            if (pvs[a][i] >= P) return set_error(ctx, ZKHIP_ERR_INVALID, who + "public value not canonical");
+        n_pv += airs[a].n_pvs;
+        if (!S.plans[a].active()) inact_words += 4 * (size_t)S.plans[a].m;
+    }
+    const unsigned M = T.M, D = T.D, M2 = T.M2;
+    const size_t n_jobs = T.act.size(), n_red = T.red.size();
+    // the jobs: a (D, BUS) class is a run of the table, tallest first; the lowered programs
+    std::vector<size_t> order(T.act);
+    auto cls = [&](size_t a) { return 2 * S.plans[a].D + (with_bus && !S.plans[a].prog.ints.empty() ? 1u : 0u); };
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return cls(x) != cls(y) ? cls(x) < cls(y) : S.plans[x].m > S.plans[y].m; });
+    std::vector<CompiledAir> ca(n_jobs);
+    size_t n_cons_max = 1, up_words = 0, tab_words = 0, n_cst = 0, n_ucols = 0, red_vals = 0;
+    auto pad4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    for (size_t k = 0; k < n_jobs; k++) {
+        const ZcPlan& pl = S.plans[order[k]];
+        std::vector<uint32_t> roots = pl.proven;
+        if (with_bus) roots.insert(roots.end(), pl.bus_roots.begin(), pl.bus_roots.end());
+        std::string err;
+        if (compile_air(pl.prog, &ca[k], &err, &roots) != 0 || ca[k].n_slots > ZC_MAX_SLOTS)
+            return set_error(ctx, ZKHIP_ERR_INVALID, who + (err.empty() ? "an AIR needs more than 64 live intermediates" : err));
+        n_cons_max = std::max(n_cons_max, pl.proven.size());
+        up_words += pad4(2 * ca[k].code.size() + ca[k].consts.size() + pl.prog.n_pvs + pl.rot.size());
+        const size_t n = (size_t)1 << pl.m, nt = pl.w + pl.rot.size() + (with_bus && !pl.prog.ints.empty() ? 4 : 3);
+        tab_words += 4 * (size_t)pl.D * SC_NB + 4 * nt * (n / 2) + 4 * nt * std::max<size_t>(n / 4, 1);
+        if (pl.reduces()) tab_words += 8 * n + 8 * SC_NB, n_ucols += pl.w, red_vals += pl.w + pl.rot.size();
+        if (with_bus) n_cst += pl.prog.ints.size();
+    }
+    std::map<unsigned, size_t> eq_at;   // height of an AIR with proven constraints -> its eq table (words from d_ws)
+    // the workspace, laid out once: [upload | challenges | powers | weights, claims, states | eq tables | per job: partial, tA, tB (, F_a, F_b, partial)]
+    const size_t o_lagx = up_words, o_lagw = o_lagx + pad4(ZB_PTS * ZB_PTS * ZB_PTS), o_structs = o_lagw + pad4(ZB_PTS);
+    const size_t job_w = pad4(n_jobs * sizeof(ZbJob) / 4 + 1), cst_w = pad4(n_cst * sizeof(ZbCst) / 4 + 1), rot_w = pad4(n_red * sizeof(ZbRot) / 4 + 1),
+                 col_w = pad4(n_ucols * sizeof(ZbCol) / 4 + 1);
+    const size_t o_job = o_structs, o_cst = o_job + job_w, o_rot = o_cst + cst_w, o_col = o_rot + rot_w, up_total = o_col + col_w;
+    const size_t o_chal = up_total, o_apow = o_chal + 4 * (size_t)M + 12, o_lpow = o_apow + 4 * n_cons_max, o_wgt = o_lpow + 4 * std::max<size_t>(red_vals, 1),
+                 o_claim = o_wgt + 4 * std::max<size_t>(n_jobs, 1), o_state = o_claim + 4 * std::max<size_t>(n_jobs, 1);
+    size_t o_end = o_state + 4 * std::max<size_t>(n_red, 1);
+    for (size_t a : T.act)
+        if (!S.plans[a].proven.empty() && !eq_at.count(S.plans[a].m)) eq_at[S.plans[a].m] = o_end, o_end += 4 * ((size_t)1 << S.plans[a].m);
+    const size_t o_tabs = o_end, ws_words = o_tabs + tab_words;
+    // 1. commit: every main column, AIRs in caller order
+    std::vector<const uint32_t*> cols;
+    for (size_t a = 0; a < n_airs; a++)
+        for (size_t c = 0; c < airs[a].width; c++) cols.push_back(d_traces[a] + (c << airs[a].log_height));
+    struct Com {
+        zkhip_ctx* ctx;
+        zkhip_stack_commitment* sc = nullptr;
+        ~Com() { stack_destroy(ctx, sc); }
+    } com{ctx};
+    uint32_t root[8];
+    ZK_TRY(stack_commit(ctx, prm, cols.data(), S.lh.data(), cols.size(), l, &com.sc, root));
+    DevBufs B(ctx);
+    // device: [the words before the opening | r (4 M) | r' (4 M') | the inactive AIRs' points], all read back at once
+    const size_t o_r = T.head, o_rp = o_r + 4 * (size_t)M, o_inact = o_rp + 4 * (size_t)M2, back_words = o_inact + inact_words;
+    uint32_t *dP = B.get(back_words), *d_obs = B.get(8 + n_pv), *d_ws = B.get(ws_words);
+    if (!dP || !d_obs || !d_ws) return set_error(ctx, ZKHIP_ERR_NOMEM, who + "the workspace does not fit");
+    std::vector<uint32_t> obs(root, root + 8);
+    for (size_t a = 0; a < n_airs; a++) obs.insert(obs.end(), pvs[a], pvs[a] + airs[a].n_pvs);
+    ZK_TRY(zkhip_h2d(ctx, d_obs, obs.data(), obs.size() * 4));
+    ZK_TRY(transcript_observe(ctx, d_t, d_obs, (uint32_t)obs.size(), true));
+    // 2. - 5. the bus part
+    std::vector<ZcBus> bus(n_airs);
+    const uint32_t* chal = nullptr;
+    if (with_bus) ZK_TRY(prove_bus(ctx, S, airs, n_airs, d_traces, pvs, d_t, B, dP, &bus, nullptr, &chal));
+    // the one upload: programs, constants, public values, rotation lists, the interpolation weights, the job tables
+    std::vector<uint32_t> up(up_total, 0);
+    std::vector<ZbJob> jobs(n_jobs);
+    std::vector<ZbCst> cst;
+    std::vector<ZbRot> rots(n_red);
+    std::vector<ZbCol> ucols;
+    std::vector<size_t> val_at(n_airs, 0), u_at(n_airs, 0), lam_at(n_airs, 0), job_of(n_airs, 0);
+    {
+        size_t v = 0, u = 0, o = 0;
+        for (size_t a : T.act) {
+            const ZcPlan& pl = S.plans[a];
+            val_at[a] = v, v += 4 * (pl.w + pl.rot.size());
+            if (pl.reduces()) u_at[a] = u, u += 4 * pl.w, lam_at[a] = o, o += pl.w + pl.rot.size();
+        }
+    }
+    uint32_t *tau = d_ws + o_chal, *alpha = tau + 4 * M, *mu = alpha + 4, *lambda = mu + 4;
+    uint32_t *d_r = dP + o_r, *d_rp = dP + o_rp;
+    struct Cls {
+        size_t lo, n;
+        unsigned D, slots;
+        bool bus;
+    };
+    std::vector<Cls> classes;
+    {
+        size_t at = 0, tabs = o_tabs;
+        uint64_t wg = 0;
+        for (size_t k = 0; k < n_jobs; k++) {
+            const size_t a = order[k];
+            const ZcPlan& pl = S.plans[a];
+            const bool has_bus = with_bus && !pl.prog.ints.empty();
+            const unsigned w = (unsigned)pl.w, n_rot = (unsigned)pl.rot.size();
+            if (classes.empty() || cls(order[classes.back().lo]) != cls(a)) classes.push_back({k, 0, pl.D, 1, has_bus}), wg = 0;
+            classes.back().n++, classes.back().slots = std::max(classes.back().slots, ca[k].n_slots);
+            const size_t n_code = ca[k].code.size(), n_ins = n_code / 3;
+            uint32_t* h = up.data() + at;
+            std::copy(ca[k].code.begin(), ca[k].code.end(), h);
+            for (size_t i = 0; i < n_ins; i++) {   // the extension passes' copy names tables in its VAR operands (zc_prove_air's remap)
+                uint32_t* x = h + n_code + 3 * i;
+                x[0] = ca[k].code[3 * i];
+                for (int q = 1; q < 3; q++) {
+                    const uint32_t o = ca[k].code[3 * i + q];
+                    x[q] = (o >> 28) != K_VAR ? o : (K_VAR << 28) | (((o >> 27) & 1u) ? w + (uint32_t)pl.rot_of[o & 0x07ffffffu] : (o & 0x07ffffffu));
+                }
+            }
+            uint32_t* hp = h + 2 * n_code;
+            hp = std::copy(ca[k].consts.begin(), ca[k].consts.end(), hp);
+            for (uint32_t i = 0; i < pl.prog.n_pvs; i++) *hp++ = to_monty(pvs[a][i]);
+            std::copy(pl.rot.begin(), pl.rot.end(), hp);
+            const uint32_t* d = d_ws + at;
+            const size_t n = (size_t)1 << pl.m, nt = w + n_rot + (has_bus ? 4 : 3);
+            ZbJob& jb = jobs[k];
+            jb = ZbJob{};
+            jb.pg = ZcProg{d, (unsigned)n_ins, d + 2 * n_code, d + 2 * n_code + ca[k].consts.size(), d_ws + o_apow, bus[a].coef, (unsigned)pl.proven.size()};
+            jb.xcode = d + n_code, jb.trace = d_traces[a], jb.rot = d + 2 * n_code + ca[k].consts.size() + pl.prog.n_pvs;
+            jb.E2 = bus[a].E2, jb.E = pl.proven.empty() ? bus[a].E2 : d_ws + eq_at[pl.m];
+            jb.partial = d_ws + tabs, tabs += 4 * (size_t)pl.D * SC_NB;
+            jb.tA = d_ws + tabs, tabs += 4 * nt * (n / 2);
+            jb.tB = d_ws + tabs, tabs += 4 * nt * std::max<size_t>(n / 4, 1);
+            jb.m = pl.m, jb.w = w, jb.n_rot = n_rot, jb.D = pl.D;
+            jb.j = (uint32_t)(std::find(T.act.begin(), T.act.end(), a) - T.act.begin());
+            jb.first_wg = (uint32_t)wg, jb.n_wg = grid_w(n / 2), wg += jb.n_wg;
+            jb.val_at = (uint32_t)val_at[a];
+            if (has_bus) {
+                jb.cst_at = (uint32_t)cst.size(), jb.cst_n = (uint32_t)pl.prog.ints.size(), jb.b_at = (uint32_t)S.b_at[a];
+                uint32_t root_at = 0;   // pl.bus_roots: per interaction its count, then its fields
+                for (const Interaction& it : pl.prog.ints) cst.push_back({root_at, to_monty(it.bus + 1), it.sign}), root_at += 1 + it.n_fields;
+            }
+            job_of[a] = k;
+            at += pad4(2 * n_code + ca[k].consts.size() + pl.prog.n_pvs + n_rot);
+            if (pl.reduces()) {   // its reduction buffers follow its tables
+                ZbRot& rj = rots[std::find(T.red.begin(), T.red.end(), a) - T.red.begin()];
+                rj = ZbRot{};
+                rj.trace = d_traces[a], rj.rot = jb.rot, rj.lpow = d_ws + o_lpow + 4 * lam_at[a], rj.E = d_ws + eq_at[pl.m];
+                rj.fa = d_ws + tabs, rj.fb = rj.fa + 4 * n, tabs += 8 * n;
+                rj.partial = d_ws + tabs, tabs += 8 * SC_NB;
+                rj.tA = jb.tA, rj.tB = jb.tB, rj.m = pl.m, rj.w = w, rj.n_rot = n_rot;
+                rj.wgt = mpow(to_monty(2), M2 - pl.m), rj.u_at = (uint32_t)u_at[a];
+            }
+        }
+        for (size_t a : T.red)
+            for (size_t c = 0; c < S.plans[a].w; c++)
+                ucols.push_back({d_traces[a] + (c << S.plans[a].m), d_ws + eq_at[S.plans[a].m], S.plans[a].m, (uint32_t)(u_at[a] + 4 * c)});
+        // s(t), t > d, from s(0..d); and 1 / prod_{i != t} (t - i) over 0..D
+        auto small = [](unsigned x) { return to_monty(x); };
+        for (unsigned d = 1; d < ZB_PTS; d++)
+            for (unsigned t = d + 1; t < ZB_PTS; t++)
+                for (unsigned j = 0; j <= d; j++) {
+                    uint32_t num = MONTY_ONE, den = MONTY_ONE;
+                    for (unsigned i = 0; i <= d; i++)
+                        if (i != j) num = mmul(num, msub(small(t), small(i))), den = mmul(den, msub(small(j), small(i)));
+                    up[o_lagx + (d * ZB_PTS + t) * ZB_PTS + j] = mmul(num, minv(den));
+                }
+        for (unsigned t = 0; t <= D; t++) {
+            uint32_t den = MONTY_ONE;
+            for (unsigned i = 0; i <= D; i++)
+                if (i != t) den = mmul(den, msub(small(t), small(i)));
+            up[o_lagw + t] = minv(den);
+        }
+        if (n_jobs) memcpy(up.data() + o_job, jobs.data(), n_jobs * sizeof(ZbJob));
+        if (!cst.empty()) memcpy(up.data() + o_cst, cst.data(), cst.size() * sizeof(ZbCst));
+        if (n_red) memcpy(up.data() + o_rot, rots.data(), n_red * sizeof(ZbRot));
+        if (!ucols.empty()) memcpy(up.data() + o_col, ucols.data(), ucols.size() * sizeof(ZbCol));
+    }
+    ZK_TRY(zkhip_h2d(ctx, d_ws, up.data(), up.size() * 4));
+    const ZbJob* d_jobs = (const ZbJob*)(d_ws + o_job);
+    const ZbRot* d_rots = (const ZbRot*)(d_ws + o_rot);
+    // 6. the batched sum-check: tau and alpha (if some AIR has proven constraints), then mu
+    if (T.any_cons) ZK_TRY(transcript_sample(ctx, d_t, tau, nullptr, 4 * M + 8));
+    else ZK_TRY(transcript_sample(ctx, d_t, mu, nullptr, 4));
+    for (auto& e : eq_at) {
+        KernelScope ks(ctx, "zb_eq");
+        whir_eq_launch(st, d_ws + e.second, e.first, tau);
+    }
+    if (T.any_cons) {
+        KernelScope ks(ctx, "zb_pows");
+        hipLaunchKernelGGL(k_zc_pows, dim3(1), dim3(256), 0, st, (const uint32_t*)alpha, (unsigned)n_cons_max, d_ws + o_apow);
+    }
+    ZK_HIP_CHECK(ctx, hipGetLastError());
+    ZbTr ztr{};
+    ztr.mu = mu, ztr.lagx = d_ws + o_lagx, ztr.lagw = d_ws + o_lagw, ztr.cst = (const ZbCst*)(d_ws + o_cst), ztr.chal = chal;
+    ztr.dB = dP + 8 + S.gkr_words, ztr.wgt = d_ws + o_wgt, ztr.claim = d_ws + o_claim, ztr.proof = dP + T.o_rounds, ztr.r = d_r;
+    for (unsigned i = 0; i <= M; i++) {   // round i; i = M: the tallest AIRs' last fold only
+        for (const Cls& c : classes) {
+            size_t alive = 0;   // the class's jobs are sorted tallest first: the ones with m >= i are a prefix
+            while (alive < c.n && jobs[c.lo + alive].m >= i) alive++;
+            if (!alive) continue;
+            const ZbJob& last = jobs[c.lo + alive - 1];
+            KernelScope ks(ctx, i ? "zb_pass" : "zb_round0");
+            zb_launch(c.D, c.bus, st, last.first_wg + last.n_wg, (size_t)c.slots * ZC_W * (i ? 16 : 4), d_jobs + c.lo, (uint32_t)alive, i,
+                      i ? d_r + 4 * (i - 1) : nullptr);
+        }
+        if (i < M) {
+            KernelScope ks(ctx, "zb_round_tr");
+            hipLaunchKernelGGL(k_zb_round_tr, dim3(1), dim3(ZB_TR), 0, st, d_t, d_jobs, (unsigned)n_jobs, i, M, D, ztr);
+        }
+        ZK_HIP_CHECK(ctx, hipGetLastError());
+    }
+    // 7. the values of every active AIR at its prefix of r
+    if (n_jobs) {
+        {
+            KernelScope ks(ctx, "zb_emit");
+            hipLaunchKernelGGL(k_zb_emit, dim3((unsigned)n_jobs), dim3(64), 0, st, d_jobs, dP + T.o_vals);
+        }
+        ZK_HIP_CHECK(ctx, hipGetLastError());
+        ZK_TRY(transcript_observe(ctx, d_t, dP + T.o_vals, (uint32_t)(T.o_red - T.o_vals), true));
+    }
+    // 8. the batched rotation reduction
+    if (n_red) {
+        std::map<unsigned, size_t> heights;   // the reducing AIRs' distinct heights
+        unsigned m_min = M2;
+        for (size_t a : T.red) heights[S.plans[a].m] = eq_at[S.plans[a].m], m_min = std::min(m_min, S.plans[a].m);
+        ZK_TRY(transcript_sample(ctx, d_t, lambda, nullptr, 4));
+        {
+            KernelScope ks(ctx, "zb_pows");
+            hipLaunchKernelGGL(k_zc_pows, dim3(1), dim3(256), 0, st, (const uint32_t*)lambda, (unsigned)red_vals, d_ws + o_lpow);
+        }
+        for (auto& e : heights) {
+            KernelScope ks(ctx, "zb_eq");
+            whir_eq_launch(st, d_ws + e.second, e.first, d_r);
+        }
+        {
+            KernelScope ks(ctx, "zb_combine");
+            hipLaunchKernelGGL(k_zb_combine, dim3(grid_of((size_t)1 << M2), (unsigned)n_red), dim3(256), 0, st, d_rots);
+        }
+        ZK_HIP_CHECK(ctx, hipGetLastError());
+        const ZbRotTr rtr{d_ws + o_state, dP + T.o_red, d_rp};
+        for (unsigned t = 0; t < M2; t++) {
+            {
+                KernelScope ks(ctx, "zb_rot_pass");
+                hipLaunchKernelGGL(k_zb_rot_pass, dim3(grid_of(((size_t)1 << (M2 - t)) >> 1), (unsigned)n_red), dim3(256), 0, st, d_rots, t,
+                                   t ? (const uint32_t*)(d_rp + 4 * (t - 1)) : nullptr);
+            }
+            {
+                KernelScope ks(ctx, "zb_round_tr");
+                hipLaunchKernelGGL(k_zb_rot_tr, dim3(1), dim3(ZB_TR), 0, st, d_t, d_rots, (unsigned)n_red, t, rtr);
+            }
+            ZK_HIP_CHECK(ctx, hipGetLastError());
+        }
+        for (auto& e : heights) {
+            KernelScope ks(ctx, "zb_eq");
+            whir_eq_launch(st, d_ws + e.second, e.first, d_rp);
+        }
+        {
+            KernelScope ks(ctx, "zb_dot");
+            hipLaunchKernelGGL(k_zb_dot, dim3((unsigned)n_ucols), dim3(256), 0, st, (const ZbCol*)(d_ws + o_col), dP + T.o_u);
+        }
+        ZK_HIP_CHECK(ctx, hipGetLastError());
+        ZK_TRY(transcript_observe(ctx, d_t, dP + T.o_u, (uint32_t)(T.head - T.o_u), true));
+    }
+    // 9. the points: an inactive AIR samples its own, all of them in one launch
+    if (inact_words) ZK_TRY(transcript_sample(ctx, d_t, dP + o_inact, nullptr, (uint32_t)inact_words));
+    std::vector<uint32_t> h(back_words);
+    ZK_TRY(zkhip_d2h(ctx, h.data(), dP, h.size() * 4));
+    for (size_t i = T.head; i < h.size(); i++) h[i] = from_monty(h[i]);
+    std::vector<uint32_t> points;
+    size_t in_at = o_inact;
+    for (size_t a = 0; a < n_airs; a++) {
+        const ZcPlan& pl = S.plans[a];
+        const size_t from = !pl.active() ? in_at : pl.reduces() ? o_rp : o_r;
+        points.insert(points.end(), h.begin() + from, h.begin() + from + 4 * (size_t)pl.m);
+        if (!pl.active()) in_at += 4 * (size_t)pl.m;
+    }
+    // 10. the one stacked opening
+    ZK_TRY(stack_open(ctx, com.sc, d_t, points.data(), S.dims.data(), n_airs, S.col_point.data(), nullptr, proof_out + T.head, cap - T.head));
+    memcpy(proof_out, root, 32);
+    memcpy(proof_out + 8, h.data() + 8, (T.head - 8) * 4);
+    if (root_out) memcpy(root_out, root, 32);
+    return ZKHIP_OK;
+}
+
+// the host verifier of the batched proof; pq_out: with_bus only
+int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs, const uint32_t* const* pvs,
+                 unsigned l, const uint32_t* proof, size_t words, bool with_bus, uint32_t* root_out, uint32_t* pq_out) {
+    BatchShape T;
+    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T)) return ZKHIP_ERR_INVALID;
+    const Shape& S = T.S;
+    for (size_t a = 0; a < n_airs; a++) {
+        if (airs[a].n_pvs && !pvs[a]) return ZKHIP_ERR_INVALID;
+        for (size_t i = 0; i < airs[a].n_pvs; i++)
+            if (pvs[a][i] >= P) return ZKHIP_ERR_INVALID;
+    }
+    for (size_t i = 0; i < n_prefix; i++)
+        if (prefix[i] >= P) return ZKHIP_ERR_INVALID;
+    if (words != T.total) return ZKHIP_ERR_VERIFY;
+    for (size_t i = 0; i < T.head; i++)
+        if (proof[i] >= P) return ZKHIP_ERR_VERIFY;
+    HostChallenger ch;
+    ch.observe_canon(prefix, n_prefix);
+    ch.observe_canon(proof, 8);
+    for (size_t a = 0; a < n_airs; a++) ch.observe_canon(pvs[a], airs[a].n_pvs);
+    const Ext one = ext_one();
+    const size_t n_blk = S.blocks.size();
+    const uint32_t* qB = nullptr;
+    Ext gamma = ext_zero(), kappa = ext_zero();
+    std::vector<Ext> rho(S.L), eb(n_blk), bpow(LOGUP_MAX_FIELDS + 1, one);
+    std::vector<std::vector<size_t>> blk_of(n_airs);
+    if (with_bus) {   // steps 2 - 5, as in verify()
+        gamma = ch.sample_ext();
+        const Ext beta = ch.sample_ext();
+        std::vector<uint32_t> pt(4 * (size_t)S.L);
+        uint32_t cl8[8];
+        Ext pq[2];
+        ZK_TRY(gkr_verify_host(ch, proof + 8, S.gkr_words, S.L, pt.data(), cl8, pq));
+        if (!ext_eq(pq[0], ext_zero()) || ext_eq(pq[1], ext_zero())) return ZKHIP_ERR_VERIFY;
+        for (unsigned j = 0; j < S.L; j++) rho[j] = ext_from_canon(pt.data() + 4 * j);
+        const Ext pstar = ext_from_canon(cl8), qstar = ext_from_canon(cl8 + 4);
+        Ext pad = one;
+        for (size_t b = 0; b < n_blk; b++) {
+            const AsBlk& k = S.blocks[b];
+            Ext e = one;
+            for (unsigned t = 0; k.m + t < S.L; t++) e = ext_mul(e, ((k.off >> k.m) >> t) & 1u ? rho[k.m + t] : ext_sub(one, rho[k.m + t]));
+            eb[b] = e, pad = ext_sub(pad, e);
+        }
+        kappa = ch.sample_ext();
+        qB = proof + 8 + S.gkr_words;
+        Ext lhs = ext_mul(kappa, pad);
+        for (size_t i = 0; i < S.n_bus; i++) lhs = ext_add(lhs, ext_from_canon(qB + 4 * i));
+        ch.observe_canon(qB, 4 * S.n_bus);
+        if (!ext_eq(lhs, ext_add(pstar, ext_mul(kappa, qstar)))) return ZKHIP_ERR_VERIFY;
+        for (unsigned i = 1; i <= LOGUP_MAX_FIELDS; i++) bpow[i] = ext_mul(bpow[i - 1], beta);
+        for (size_t a = 0; a < n_airs; a++) blk_of[a].resize(S.plans[a].prog.ints.size());
+        for (size_t b = 0; b < n_blk; b++) blk_of[S.blocks[b].a][S.blocks[b].j] = b;
+    }
+    // 6. the batched sum-check
+    const unsigned M = T.M, D = T.D, M2 = T.M2;
+    std::vector<Ext> tau(M), r(M), rp(M2);
+    Ext alpha = ext_zero();
+    if (T.any_cons) {
+        for (unsigned j = 0; j < M; j++) tau[j] = ch.sample_ext();
+        alpha = ch.sample_ext();
+    }
+    const Ext mu = ch.sample_ext();
+    const Ext two = ext_from_base(to_monty(2));
+    std::vector<std::vector<Ext>> coef(n_airs);   // per AIR with interactions: the coefficients of pl.bus_roots
+    Ext claim = ext_zero(), mup = one;
+    for (size_t a : T.act) {
+        const ZcPlan& pl = S.plans[a];
+        if (!pl.bus_roots.empty()) {
+            Ext cst = ext_zero();   // sum_j e_{a,j} (gamma + bus_j + 1)
+            for (size_t j = 0; j < blk_of[a].size(); j++) {
+                const Interaction& it = pl.prog.ints[j];
+                const Ext e = eb[blk_of[a][j]], ke = ext_mul(kappa, e);
+                Ext g1 = gamma;
+                g1.c[0] = madd(g1.c[0], to_monty(it.bus + 1));
+                cst = ext_add(cst, ext_mul(e, g1));
+                coef[a].push_back(it.sign ? ext_neg(e) : e);
+                for (uint32_t i = 0; i < it.n_fields; i++) coef[a].push_back(ext_mul(ke, bpow[i + 1]));
+            }
+            const Ext c = ext_sub(ext_from_canon(qB + 4 * S.b_at[a]), ext_mul(kappa, cst));
+            claim = ext_add(claim, ext_mul(ext_mul(mup, ext_pow(two, M - pl.m)), c));   // mu^j 2^(M - m_a) c_a
+        }
+        mup = ext_mul(mup, mu);
+    }
+    const uint32_t* q = proof + T.o_rounds;
+    for (unsigned i = 0; i < M; i++, q += 4 * D) {
+        Ext s[ZKHIP_ZEROCHECK_MAX_DEGREE + 1];
+        s[0] = ext_from_canon(q), s[1] = ext_sub(claim, s[0]);
+        for (unsigned e = 1; e < D; e++) s[e + 1] = ext_from_canon(q + 4 * e);
+        ch.observe_canon(q, 4 * D);
+        r[i] = ch.sample_ext();
+        claim = poly_at(s, D, r[i]);
+    }
+    // 7. the values: sum_j mu^j [eq(tau_a, r_a) sum_k alpha^k C_k + eq(rho_a, r_a) (the bus part)] = the last claim
+    ch.observe_canon(q, T.o_red - T.o_vals);
+    std::vector<const uint32_t*> vals(n_airs, nullptr), claimed(n_airs, nullptr);
+    Ext rhs = ext_zero();
+    mup = one;
+    for (size_t a : T.act) {
+        const ZcPlan& pl = S.plans[a];
+        const unsigned m = pl.m;
+        const size_t w = pl.w, n_rot = pl.rot.size();
+        std::vector<Ext> v(w), vn(n_rot);
+        for (size_t j = 0; j < w; j++) v[j] = ext_from_canon(q + 4 * j);
+        for (size_t t = 0; t < n_rot; t++) vn[t] = ext_from_canon(q + 4 * (w + t));
+        vals[a] = q, q += 4 * (w + n_rot);
+        Ext first = one, last = one, g = ext_zero();
+        for (unsigned j = 0; j < m; j++) first = ext_mul(first, ext_sub(one, r[j])), last = ext_mul(last, r[j]);
+        if (!pl.proven.empty()) {
+            const std::vector<Ext> val = zc_eval_host(pl, pl.reach, v.data(), vn.data(), first, last, pvs[a]);
+            Ext c = ext_zero(), ap = one;
+            for (uint32_t k : pl.proven) c = ext_add(c, ext_mul(ap, val[k])), ap = ext_mul(ap, alpha);
+            g = ext_mul(eq_eval(tau.data(), r.data(), m), c);
+        }
+        if (!pl.bus_roots.empty()) {
+            const std::vector<Ext> val = zc_eval_host(pl, pl.bus_reach, v.data(), vn.data(), first, last, pvs[a]);
+            Ext c = ext_zero();
+            for (size_t k = 0; k < coef[a].size(); k++) c = ext_add(c, ext_mul(coef[a][k], val[pl.bus_roots[k]]));
+            g = ext_add(g, ext_mul(eq_eval(rho.data(), r.data(), m), c));
+        }
+        rhs = ext_add(rhs, ext_mul(mup, g));
+        mup = ext_mul(mup, mu);
+    }
+    if (!ext_eq(rhs, claim)) return ZKHIP_ERR_VERIFY;
+    // 8. the batched rotation reduction
+    if (!T.red.empty()) {
+        const Ext lambda = ch.sample_ext();
+        std::vector<std::vector<Ext>> lp(n_airs);   // lambda^(o_a + k) over the AIR's [v | v']
+        Ext x = one;
+        claim = ext_zero();
+        for (size_t a : T.red) {
+            const ZcPlan& pl = S.plans[a];
+            Ext acc = ext_zero();
+            for (size_t k = 0; k < pl.w + pl.rot.size(); k++) lp[a].push_back(x), acc = ext_add(acc, ext_mul(x, ext_from_canon(vals[a] + 4 * k))), x = ext_mul(x, lambda);
+            claim = ext_add(claim, ext_mul(ext_pow(two, M2 - pl.m), acc));
+        }
+        for (unsigned i = 0; i < M2; i++, q += 8) {
+            const Ext s0 = ext_from_canon(q), s2 = ext_from_canon(q + 4);
+            ch.observe_canon(q, 8);
+            rp[i] = ch.sample_ext();
+            const Ext sv[3] = {s0, ext_sub(claim, s0), s2};
+            claim = poly_at(sv, 2, rp[i]);
+        }
+        ch.observe_canon(q, T.head - T.o_u);
+        Ext want = ext_zero();
+        for (size_t a : T.red) {
+            const ZcPlan& pl = S.plans[a];
+            Ext ua = ext_zero(), ub = ext_zero();
+            for (size_t j = 0; j < pl.w; j++) ua = ext_add(ua, ext_mul(lp[a][j], ext_from_canon(q + 4 * j)));
+            for (size_t t = 0; t < pl.rot.size(); t++) ub = ext_add(ub, ext_mul(lp[a][pl.w + t], ext_from_canon(q + 4 * pl.rot[t])));
+            claimed[a] = q, q += 4 * pl.w;
+            want = ext_add(want, ext_add(ext_mul(ua, eq_eval(r.data(), rp.data(), pl.m)), ext_mul(ub, zc_rot_eval(r.data(), rp.data(), pl.m))));
+        }
+        if (!ext_eq(want, claim)) return ZKHIP_ERR_VERIFY;
+    }
+    // 9. the points, 10. the stacked opening
+    std::vector<uint32_t> points;
+    for (size_t a = 0; a < n_airs; a++) {
+        const ZcPlan& pl = S.plans[a];
+        if (pl.active() && !pl.reduces()) claimed[a] = vals[a];
+        for (unsigned j = 0; j < pl.m; j++) {
+            uint32_t c4[4];
+            ext_to_canon(c4, !pl.active() ? ch.sample_ext() : pl.reduces() ? rp[j] : r[j]);
+            points.insert(points.end(), c4, c4 + 4);
+        }
+    }
+    const uint32_t* op = proof + T.head;
+    ZK_TRY(stack_verify_host(ch, prm, proof, S.lh.data(), S.lh.size(), l, points.data(), S.dims.data(), n_airs, S.col_point.data(), op, S.main_words));
+    size_t col = 0;
+    for (size_t a = 0; a < n_airs; col += airs[a].width, a++)
+        if (claimed[a] && memcmp(claimed[a], op + 4 * col, 16 * airs[a].width) != 0) return ZKHIP_ERR_VERIFY;
+    if (root_out) memcpy(root_out, proof, 32);
+    if (pq_out && with_bus) memcpy(pq_out, proof + 8, 32);
+    return ZKHIP_OK;
+}
+
 // ---- the key ---------------------------------------------------------------------------------------------------------------------
 void airkey_destroy(zkhip_ctx* ctx, zkhip_airkey* key) {
     if (!key) return;
@@ -805,6 +1302,26 @@ int zkhip_airset_verify(const zkhip_whir_params* params, const uint32_t* prefix,
                         uint32_t* pq_out) {
     if (!params || (n_prefix && !prefix) || !airs || !pvs || !proof) return ZKHIP_ERR_INVALID;
     return verify(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, true, root_out, pq_out);
+}
+
+size_t zkhip_airbatch_proof_words(const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, unsigned log_stack, int with_bus) {
+    BatchShape T;
+    return batch_shape(params, airs, n_airs, log_stack, with_bus != 0, &T) ? T.total : 0;
+}
+
+int zkhip_airbatch_prove(zkhip_ctx* ctx, const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
+                         const uint32_t* const* pvs, unsigned log_stack, int with_bus, zkhip_transcript* transcript, uint32_t* proof_out, size_t cap,
+                         uint32_t* root_out) {
+    ZK_BIND_DEVICE(ctx);
+    if (!ctx || !params || !airs || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
+    return prove_batch(ctx, params, airs, n_airs, d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out, cap, root_out);
+}
+
+int zkhip_airbatch_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
+                          const uint32_t* const* pvs, unsigned log_stack, int with_bus, const uint32_t* proof, size_t words, uint32_t* root_out,
+                          uint32_t* pq_out) {
+    if (!params || (n_prefix && !prefix) || !airs || !pvs || !proof) return ZKHIP_ERR_INVALID;
+    return verify_batch(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, root_out, pq_out);
 }
 
 }  // extern "C"

@@ -48,15 +48,15 @@ static __global__ __launch_bounds__(256) void k_zc_pows(const uint32_t* __restri
     for (unsigned k = threadIdx.x; k < n; k += 256) sc_st(out, k, ext_pow(a, k));
 }
 
-// one wave's sums of the round polynomial: word 4 e + q at partial[(4 e + q) SC_NB + blockIdx.x]
+// one wave's sums of the round polynomial: word 4 e + q at partial[(4 e + q) SC_NB + wg]
 template <unsigned D>
-__device__ __forceinline__ void zc_wave_out(const Ext (&acc)[D], uint32_t* partial) {
+__device__ __forceinline__ void zc_wave_out(const Ext (&acc)[D], uint32_t* partial, unsigned wg) {
 #pragma unroll
     for (unsigned e = 0; e < D; e++)
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const uint32_t x = sc_wave_sum(acc[e].c[q]);
-            if (threadIdx.x == 0) partial[(size_t)(4 * e + q) * SC_NB + blockIdx.x] = x;
+            if (threadIdx.x == 0) partial[(size_t)(4 * e + q) * SC_NB + wg] = x;
         }
 }
 
@@ -66,16 +66,18 @@ __device__ __forceinline__ uint32_t zc_small(unsigned t) { return mmul(t, MONTY_
 // ---- round 0: the base-field trace in place ------------------------------------------------------------------------------------
 // Pair y holds rows 2y and 2y + 1; a next-row cell is the same column one row on (mod n).  At the integer point t a cell's value is
 // the base element f0 + t (f1 - f0), so the program runs in the base field; the alpha-combination and the eq factor are extension.
+// The workgroup is number wg of the n_wg that share the pairs (the single-AIR kernels: the grid; the batched ones: its job's range).
 template <unsigned D, bool BUS, bool PREP>
 __device__ __forceinline__ void zc_round0_body(const ZcProg& pg, const uint32_t* __restrict__ trace, const uint32_t* __restrict__ prep, unsigned m,
-                                               const uint32_t* __restrict__ E, const uint32_t* __restrict__ E2, uint32_t* __restrict__ partial) {
+                                               const uint32_t* __restrict__ E, const uint32_t* __restrict__ E2, uint32_t* __restrict__ partial,
+                                               unsigned wg, unsigned n_wg) {
     extern __shared__ uint32_t zc_slots[];   // [slot][lane]
     const unsigned lane = threadIdx.x;
     const size_t n = (size_t)1 << m, n_pairs = n >> 1;
     Ext acc[D];
 #pragma unroll
     for (unsigned e = 0; e < D; e++) acc[e] = ext_zero();
-    for (size_t y = (size_t)blockIdx.x * ZC_W + lane; y < n_pairs; y += (size_t)gridDim.x * ZC_W) {
+    for (size_t y = (size_t)wg * ZC_W + lane; y < n_pairs; y += (size_t)n_wg * ZC_W) {
         const size_t x0 = 2 * y, x1 = x0 + 1, x2 = (x0 + 2) & (n - 1);
         const Ext e0 = sc_ld(E, x0), e1 = sc_ld(E, x1), de = ext_sub(e1, e0);
         Ext et = e0;
@@ -131,17 +133,17 @@ __device__ __forceinline__ void zc_round0_body(const ZcProg& pg, const uint32_t*
             }
         }
     }
-    zc_wave_out(acc, partial);
+    zc_wave_out(acc, partial, wg);
 }
 template <unsigned D, bool BUS>
 __global__ __launch_bounds__(ZC_W) void k_zc_round0(ZcProg pg, const uint32_t* __restrict__ trace, unsigned m, const uint32_t* __restrict__ E,
                                                     const uint32_t* __restrict__ E2, uint32_t* __restrict__ partial) {
-    zc_round0_body<D, BUS, false>(pg, trace, nullptr, m, E, E2, partial);
+    zc_round0_body<D, BUS, false>(pg, trace, nullptr, m, E, E2, partial, blockIdx.x, gridDim.x);
 }
 template <unsigned D, bool BUS>
 __global__ __launch_bounds__(ZC_W) void k_zc_round0_p(ZcProg pg, const uint32_t* __restrict__ trace, const uint32_t* __restrict__ prep, unsigned m,
                                                       const uint32_t* __restrict__ E, const uint32_t* __restrict__ E2, uint32_t* __restrict__ partial) {
-    zc_round0_body<D, BUS, true>(pg, trace, prep, m, E, E2, partial);
+    zc_round0_body<D, BUS, true>(pg, trace, prep, m, E, E2, partial, blockIdx.x, gridDim.x);
 }
 
 // ---- rounds >= 1: fold with the previous challenge and evaluate, one pass --------------------------------------------------------
@@ -197,7 +199,7 @@ __device__ __forceinline__ Ext zc_fold_entry(const ZcTabs& tb, const ZcPrep& pp,
 // partial null: fold only (the last fold, nd = 1).  Every thread evaluates the pair whose two entries it has just written.
 template <unsigned D, bool FROM_BASE, bool BUS, bool PREP>
 __device__ __forceinline__ void zc_pass_body(const ZcProg& pg, const ZcTabs& tb, const ZcPrep& pp, const uint32_t* __restrict__ r_ptr,
-                                             uint32_t* __restrict__ partial) {
+                                             uint32_t* __restrict__ partial, unsigned wg, unsigned n_wg) {
     extern __shared__ uint4 zc_xslots[];   // [slot][lane]
     const unsigned lane = threadIdx.x, t_first = tb.w + tb.n_rot + (PREP ? pp.wp + pp.n_rot : 0u), nt = t_first + (BUS ? 4 : 3);
     const Ext r = sc_ld(r_ptr, 0), one = ext_one();
@@ -205,7 +207,7 @@ __device__ __forceinline__ void zc_pass_body(const ZcProg& pg, const ZcTabs& tb,
     Ext acc[D];
 #pragma unroll
     for (unsigned e = 0; e < D; e++) acc[e] = ext_zero();
-    for (size_t y = (size_t)blockIdx.x * ZC_W + lane; y < n_pairs; y += (size_t)gridDim.x * ZC_W) {
+    for (size_t y = (size_t)wg * ZC_W + lane; y < n_pairs; y += (size_t)n_wg * ZC_W) {
         for (unsigned t = 0; t < nt; t++) {
             sc_st(tb.dst, t * tb.dst_stride + 2 * y, zc_fold_entry<FROM_BASE, PREP>(tb, pp, t, 2 * y, r));
             if (2 * y + 1 < tb.nd) sc_st(tb.dst, t * tb.dst_stride + 2 * y + 1, zc_fold_entry<FROM_BASE, PREP>(tb, pp, t, 2 * y + 1, r));
@@ -261,17 +263,17 @@ __device__ __forceinline__ void zc_pass_body(const ZcProg& pg, const ZcTabs& tb,
             }
         }
     }
-    if (!partial) return;   // uniform across the grid
-    zc_wave_out(acc, partial);
+    if (!partial) return;   // uniform across the workgroup's share
+    zc_wave_out(acc, partial, wg);
 }
 template <unsigned D, bool FROM_BASE, bool BUS>
 __global__ __launch_bounds__(ZC_W) void k_zc_pass(ZcProg pg, ZcTabs tb, const uint32_t* __restrict__ r_ptr, uint32_t* __restrict__ partial) {
-    zc_pass_body<D, FROM_BASE, BUS, false>(pg, tb, ZcPrep{}, r_ptr, partial);
+    zc_pass_body<D, FROM_BASE, BUS, false>(pg, tb, ZcPrep{}, r_ptr, partial, blockIdx.x, gridDim.x);
 }
 // PREP: the extension passes' code names the preprocessed tables in K_VAR operands (zc_prove_air's remap), so only the table count differs
 template <unsigned D, bool FROM_BASE, bool BUS>
 __global__ __launch_bounds__(ZC_W) void k_zc_pass_p(ZcProg pg, ZcTabs tb, ZcPrep pp, const uint32_t* __restrict__ r_ptr, uint32_t* __restrict__ partial) {
-    zc_pass_body<D, FROM_BASE, BUS, true>(pg, tb, pp, r_ptr, partial);
+    zc_pass_body<D, FROM_BASE, BUS, true>(pg, tb, pp, r_ptr, partial, blockIdx.x, gridDim.x);
 }
 
 // entry 0 of the first `cnt` tables, canonical, to out[4 t ..]
