@@ -679,7 +679,7 @@ int zkhip_airset_verify(const zkhip_whir_params *params, const uint32_t *prefix,
  *      Proof words: [root (8) | with_bus: GKR words for L, then 4 per AIR with interactions | 4 D M | per active AIR 4 (w + n_rot) |
  *      if an AIR reduces: 8 M', then 4 w per reducing AIR | stacked opening].
  *      Refused (ZKHIP_ERR_INVALID; zkhip_airbatch_proof_words returns 0): with_bus = 1, what zkhip_airset_* refuses; with_bus = 0,
- *      what zkhip_zerocheck_* refuses; PREP in both (there is no keyed batched form). ---- */
+ *      what zkhip_zerocheck_* refuses; PREP in both (its case is zkhip_airkey_batch_*). ---- */
 size_t zkhip_airbatch_proof_words(const zkhip_whir_params *params, const zkhip_air *airs, size_t n_airs, unsigned log_stack, int with_bus);
 /* Device prover; arguments as zkhip_airset_prove, plus with_bus.  One upload carries every AIR's programs and the job tables; the
  * workspace of all AIRs is laid out once per call and freed (ZKHIP_ERR_NOMEM before any launch of the sum-check if it does not fit). */
@@ -723,6 +723,28 @@ int zkhip_airkey_prove(zkhip_ctx *ctx, zkhip_airkey *key, int with_bus, const ui
 int zkhip_airkey_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const zkhip_air *airs, size_t n_airs,
                         const uint32_t *prep_root, unsigned log_stack_prep, const uint32_t *const *pvs, unsigned log_stack, int with_bus,
                         const uint32_t *proof, size_t words, uint32_t *root_out, uint32_t *pq_out);
+
+/* ---- the keyed batched form (docs/airbatch.md, "The keyed batched form"): the statement of zkhip_airkey_prove with ONE constraint
+ *      sum-check and ONE rotation reduction for the whole set, under the same key (key generation does not change: one key serves
+ *      zkhip_airkey_prove and zkhip_airkey_batch_prove).  The transcript head is the keyed form's (prep_root observed, not sent), the
+ *      sum-check and the reduction are zkhip_airbatch_prove's over the keyed plans; an AIR reduces if n_rot + n_rot_p > 0; after the
+ *      main stacked opening comes one stacked opening of the key's commitment, one point per AIR that has preprocessed columns.
+ *      Proof words: [root (8) | with_bus: GKR words for L, then 4 per AIR with interactions | 4 D M |
+ *      per active AIR 4 (w + n_rot + w_p + n_rot_p) | if an AIR reduces: 8 M', then 4 (w + w_p) per reducing AIR |
+ *      zkhip_stack_proof_words(main columns, log_stack) | zkhip_stack_proof_words(preprocessed columns, log_stack_prep)].
+ *      Refused (ZKHIP_ERR_INVALID; zkhip_airkey_batch_proof_words returns 0): what zkhip_airkey_* refuses with the same with_bus (a
+ *      set without any PREP section included: zkhip_airbatch_*'s case), more than 64 AIRs.  Argument forms are those of
+ *      zkhip_airkey_proof_words / zkhip_airkey_prove / zkhip_airkey_verify. ---- */
+size_t zkhip_airkey_batch_proof_words(const zkhip_whir_params *params, const zkhip_air *airs, size_t n_airs, unsigned log_stack,
+                                      unsigned log_stack_prep, int with_bus);
+/* Device prover.  Workspace: zkhip_airbatch_prove's with (w + n_rot + w_p + n_rot_p + 3 or 4) folded tables per job, laid out once
+ * (ZKHIP_ERR_NOMEM before any launch of the sum-check if it does not fit). */
+int zkhip_airkey_batch_prove(zkhip_ctx *ctx, zkhip_airkey *key, int with_bus, const uint32_t *const *d_traces, const uint32_t *const *pvs,
+                             unsigned log_stack, zkhip_transcript *transcript, uint32_t *proof_out, size_t cap, uint32_t *root_out);
+/* Host verifier, needs no device and never reads prep_trace. */
+int zkhip_airkey_batch_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const zkhip_air *airs, size_t n_airs,
+                              const uint32_t *prep_root, unsigned log_stack_prep, const uint32_t *const *pvs, unsigned log_stack,
+                              int with_bus, const uint32_t *proof, size_t words, uint32_t *root_out, uint32_t *pq_out);
 
 /* Field offsets of a proof, in 32-bit words from its start (the layout is static for given parameters and AIR shapes:
  * DESIGN.md section 4).  The counterpart of `Proof::<SC>::decode_from_bytes` (crates/verifier/src/verifier.rs:62) for this

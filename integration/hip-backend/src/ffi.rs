@@ -473,6 +473,16 @@ extern "C" {
     pub fn zkhip_airkey_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, airs: *const zkhip_air, n_airs: usize,
                                prep_root: *const u32, log_stack_prep: c_uint, pvs: *const *const u32, log_stack: c_uint, with_bus: c_int,
                                proof: *const u32, words: usize, root_out: *mut u32, pq_out: *mut u32) -> c_int;
+    // the keyed batched form: zkhip_airkey_prove's statement with one sum-check and one reduction for the set (docs/airbatch.md)
+    pub fn zkhip_airkey_batch_proof_words(params: *const zkhip_whir_params, airs: *const zkhip_air, n_airs: usize, log_stack: c_uint,
+                                          log_stack_prep: c_uint, with_bus: c_int) -> usize;
+    pub fn zkhip_airkey_batch_prove(ctx: *mut zkhip_ctx, key: *mut zkhip_airkey, with_bus: c_int, d_traces: *const *const u32,
+                                    pvs: *const *const u32, log_stack: c_uint, transcript: *mut zkhip_transcript, proof_out: *mut u32,
+                                    cap: usize, root_out: *mut u32) -> c_int;
+    pub fn zkhip_airkey_batch_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, airs: *const zkhip_air,
+                                     n_airs: usize, prep_root: *const u32, log_stack_prep: c_uint, pvs: *const *const u32,
+                                     log_stack: c_uint, with_bus: c_int, proof: *const u32, words: usize, root_out: *mut u32,
+                                     pq_out: *mut u32) -> c_int;
 
     // the reference's stored-proof container (OpenVM-v1 Proof<SC>, bincode)
     pub fn zkhip_proof_decode_v1(bytes: *const u8, len: usize, kind: c_int, out: *mut zkhip_v1_summary) -> c_int;

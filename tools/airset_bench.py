@@ -4,7 +4,8 @@ commit plus opening (stack_*, whir_*), and beside it the fair comparison on the 
 calls zkhip_zerocheck_prove plus zkhip_bus_gkr_prove (which prove less: their bus proof is not tied to the committed traces), and
 zkhip_prove.  Shapes: the lookup key of tools/gkr_bench.py (a sender of 2^20 rows, a table of 2^16) and the 42-chip ChipSet with a
 main-column range table in place of its preprocessed one, and `chipset42_keyed`: ChipSet().gen() as generated, with its preprocessed
-range table, proven through the key (Context.airkey; key generation is timed on its own, log_stack_prep = 4).  Parameters (b, k, final_log) = (1, 4, 6), 80 queries and 16 bits of
+range table, proven through the key (Context.airkey; key generation is timed on its own, log_stack_prep = 4): a `keyed` row
+(AirKey.prove) and, from the same key in the same run, a `keyed_batch` row (AirKey.prove_batch).  Parameters (b, k, final_log) = (1, 4, 6), 80 queries and 16 bits of
 grinding in every round; v1 parameters z.DEFAULT_PARAMS.  Every figure is the median of --reps runs after one warm-up.  Prints one
 JSON object.
 
@@ -68,7 +69,7 @@ def main():
     a = ap.parse_args()
     zk = z.Context(0)
     prm = z.WhirParams.make(1, 4, 6, 16, 80)
-    out = {"airbatch": [], "airset": [], "zerocheck": [], "bus_gkr": [], "v1": [], "keyed": [], "keygen": []}
+    out = {"airbatch": [], "airset": [], "zerocheck": [], "bus_gkr": [], "v1": [], "keyed": [], "keyed_batch": [], "keygen": []}
 
     def note(r):
         print(json.dumps({k: v for k, v in r.items() if k != "by_name"}), file=sys.stderr)
@@ -96,6 +97,16 @@ def main():
             z.airkey_verify(prm, [1], vairs, key.root, lpr, pvs, l, proof["p"])
             r.update(common, log_stack_prep=lpr, proof_words=z.airkey_proof_words(prm, vairs, l, lpr), split=_group(r["by_name"]))
             out["keyed"].append(r)
+            note(r)
+
+            def keyed_batch():   # the batched form of the same statement under the same key (docs/airbatch.md), same build, same run
+                proof["b"] = key.prove_batch(d, pvs, l, [1])[1]
+
+            r = _profiled(zk, keyed_batch, a.reps)
+            z.airkey_batch_verify(prm, [1], vairs, key.root, lpr, pvs, l, proof["b"])
+            r.update(common, log_stack_prep=lpr, proof_words=z.airkey_batch_proof_words(prm, vairs, l, lpr), split=_group(r["by_name"]),
+                     zb_launches={n: v["launches"] for n, v in r["by_name"].items() if n.startswith("zb_")})
+            out["keyed_batch"].append(r)
             note(r)
             key.close()
             if not a.no_v1:

@@ -343,6 +343,10 @@ def load_library():
         "zkhip_airkey_destroy": (None, [vp, vp]),
         "zkhip_airkey_proof_words": (sz, [C.POINTER(WhirParams), C.POINTER(_Air), sz, C.c_uint, C.c_uint, C.c_int]),
         "zkhip_airkey_prove": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(u32p), C.c_uint, vp, u32p, sz, u32p]),
+        "zkhip_airkey_batch_proof_words": (sz, [C.POINTER(WhirParams), C.POINTER(_Air), sz, C.c_uint, C.c_uint, C.c_int]),
+        "zkhip_airkey_batch_prove": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(u32p), C.c_uint, vp, u32p, sz, u32p]),
+        "zkhip_airkey_batch_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, C.POINTER(_Air), sz, u32p, C.c_uint, C.POINTER(u32p), C.c_uint, C.c_int,
+                                                u32p, sz, u32p, u32p]),
         "zkhip_airkey_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, C.POINTER(_Air), sz, u32p, C.c_uint, C.POINTER(u32p), C.c_uint, C.c_int,
                                           u32p, sz, u32p, u32p]),
     }
@@ -1422,8 +1426,17 @@ class AirKey:
     def prove(self, traces, pvs, log_stack, prefix, with_bus=True):
         """The keyed AIR-set proof (with_bus) or zero-check of the key's AIRs on the device traces (as for Context.airset_prove) after a
         fresh transcript observed `prefix`.  Returns (root (8 words), proof words), canonical numpy uint32; check with airkey_verify."""
+        return self._prove(False, traces, pvs, log_stack, prefix, with_bus)
+
+    def prove_batch(self, traces, pvs, log_stack, prefix, with_bus=True):
+        """The same statement in the batched form (docs/airbatch.md, "The keyed batched form"): one constraint sum-check and one rotation
+        reduction for the whole set, then the main opening and the key's.  Arguments and result as for prove; check with
+        airkey_batch_verify."""
+        return self._prove(True, traces, pvs, log_stack, prefix, with_bus)
+
+    def _prove(self, batch, traces, pvs, log_stack, prefix, with_bus):
         ctx = self.ctx
-        words = airkey_proof_words(self.params, self.airs, log_stack, self.log_stack_prep, with_bus)
+        words = (airkey_batch_proof_words if batch else airkey_proof_words)(self.params, self.airs, log_stack, self.log_stack_prep, with_bus)
         tr = Transcript(ctx)
         pre = np.ascontiguousarray(prefix, dtype=np.uint32)
         if pre.size:
@@ -1432,7 +1445,8 @@ class AirKey:
         pa, keep = _pvs_array(pvs)
         proof = np.zeros(max(words, 1), dtype=np.uint32)
         root = np.zeros(8, dtype=np.uint32)
-        rc = ctx.lib.zkhip_airkey_prove(ctx.h, self.h, int(bool(with_bus)), tp, pa, log_stack, tr.h, _u32p(proof), proof.size, _u32p(root))
+        fn = ctx.lib.zkhip_airkey_batch_prove if batch else ctx.lib.zkhip_airkey_prove
+        rc = fn(ctx.h, self.h, int(bool(with_bus)), tp, pa, log_stack, tr.h, _u32p(proof), proof.size, _u32p(root))
         tr.close()
         ctx._check(rc)
         return root, proof[:words]
@@ -1565,10 +1579,25 @@ def airkey_proof_words(params, airs, log_stack, log_stack_prep, with_bus=True):
     return int(load_library().zkhip_airkey_proof_words(C.byref(params), arr, len(airs), log_stack, log_stack_prep, int(bool(with_bus))))
 
 
+def airkey_batch_proof_words(params, airs, log_stack, log_stack_prep, with_bus=True):
+    """words of a keyed batched proof of these AIR shapes (`prep` is not read); 0 for a refused shape"""
+    arr, keep = _air_structs([{k: v for k, v in a.items() if k != "prep"} for a in airs])
+    return int(load_library().zkhip_airkey_batch_proof_words(C.byref(params), arr, len(airs), log_stack, log_stack_prep, int(bool(with_bus))))
+
+
+def airkey_batch_verify(params, prefix, airs, prep_root, log_stack_prep, pvs, log_stack, proof, with_bus=True):
+    """Host verifier of a keyed batched proof (AirKey.prove_batch); arguments, result and errors as for airkey_verify."""
+    return _airkey_verify("zkhip_airkey_batch_verify", params, prefix, airs, prep_root, log_stack_prep, pvs, log_stack, proof, with_bus)
+
+
 def airkey_verify(params, prefix, airs, prep_root, log_stack_prep, pvs, log_stack, proof, with_bus=True):
     """Host verifier of a keyed proof (needs no GPU, never reads `prep`): a fresh challenger observes `prefix`, then prep_root, then the
     proof is replayed and the key's opening checked against prep_root.  Returns the root of the trace commitment (with_bus: (root,
     (P, Q))); raises ZkhipError (its `code` is the library's status)."""
+    return _airkey_verify("zkhip_airkey_verify", params, prefix, airs, prep_root, log_stack_prep, pvs, log_stack, proof, with_bus)
+
+
+def _airkey_verify(_fn, params, prefix, airs, prep_root, log_stack_prep, pvs, log_stack, proof, with_bus):
     lib = load_library()
     pre, pw = _gkr_words(prefix, proof)
     arr, keep = _air_structs([{k: v for k, v in a.items() if k != "prep"} for a in airs])
@@ -1577,10 +1606,10 @@ def airkey_verify(params, prefix, airs, prep_root, log_stack_prep, pvs, log_stac
     if pr.size != 8:
         raise ZkhipError("airkey_verify: prep_root holds 8 words")
     root, pq = np.zeros(8, dtype=np.uint32), np.zeros(8, dtype=np.uint32)
-    rc = lib.zkhip_airkey_verify(C.byref(params), _u32p(pre), pre.size, arr, len(airs), _u32p(pr), log_stack_prep, pa, log_stack,
-                                 int(bool(with_bus)), _u32p(pw), pw.size, _u32p(root), _u32p(pq))
+    rc = getattr(lib, _fn)(C.byref(params), _u32p(pre), pre.size, arr, len(airs), _u32p(pr), log_stack_prep, pa, log_stack,
+                           int(bool(with_bus)), _u32p(pw), pw.size, _u32p(root), _u32p(pq))
     if rc != 0:
-        e = ZkhipError("zkhip_airkey_verify refused the proof (%d)" % rc)
+        e = ZkhipError("%s refused the proof (%d)" % (_fn, rc))
         e.code = rc
         raise e
     return (root, pq) if with_bus else root

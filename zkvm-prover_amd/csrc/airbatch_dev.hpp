@@ -3,11 +3,14 @@
 // the launches nor the host round trips grow with the number of AIRs.
 //
 // The constraint rounds run the zero-check's bodies (zerocheck_dev.hpp) per job: a workgroup, still one wave, finds its job by a
-// binary search over the jobs' first workgroups (as_block_of's pattern); D_a and BUS stay compile-time, so a round is one launch
-// per (D_a, BUS) class over that class's run of the job table.  One workgroup per round (k_zb_round_tr) adds the jobs' partial sums
+// binary search over the jobs' first workgroups (as_block_of's pattern); D_a, BUS and (the keyed form) PREP stay compile-time, so a
+// round is one launch per (D_a, BUS, PREP) class over that class's run of the job table.  One workgroup per round (k_zb_round_tr) adds the jobs' partial sums
 // up, extends every s_a from 0..D_a to 0..D, weights, writes the round, runs the transcript step and keeps every AIR's running claim.
+// The job entry (ZbJob) is in airbatch_job.hpp; the per-class constraint kernels (k_zb_round0, k_zb_pass and their PREP forms) are a
+// translation unit of their own, airbatch_pass.hip, reached through zb_launch: they are most of this proof's device code, and the
+// build compiles the two units side by side.
 #pragma once
-#include "zerocheck_dev.hpp"
+#include "airbatch_job.hpp"
 
 namespace zk {
 
@@ -15,64 +18,10 @@ constexpr unsigned ZB_TR = 1024;                               // threads of the
 constexpr unsigned ZB_MAX_JOBS = ZKHIP_STACK_MAX_POINTS;       // one job per active AIR
 constexpr unsigned ZB_PTS = ZKHIP_ZEROCHECK_MAX_DEGREE + 1;    // points 0..D of a round polynomial
 
-// one active AIR in the batched constraint sum-check.  The jobs of a (D, BUS) class are consecutive, tallest first; first_wg counts
-// from the class's first job.
-struct ZbJob {
-    ZcProg pg;               // the base round's program; apow is the set's alpha powers
-    const uint32_t* xcode;   // the extension passes' copy (tables in place of cells)
-    const uint32_t* trace;
-    const uint32_t* E;       // eq(tau[0..m), .); an AIR without proven constraints: E2
-    const uint32_t* E2;      // BUS: eq(rho[0..m), .)
-    const uint32_t* rot;
-    uint32_t* tA;            // ping-pong tables: nt tables of 2^(m-1) entries, and of max(2^(m-2), 1)
-    uint32_t* tB;
-    uint32_t* partial;       // 4 D SC_NB words
-    uint32_t m, w, n_rot, D;
-    uint32_t j;              // its number among the active AIRs, caller order: the weight is mu^j 2^(M - m)
-    uint32_t first_wg, n_wg;
-    uint32_t val_at;         // its v, v' in the proof's value section (words)
-    uint32_t cst_at, cst_n;  // BUS: its interactions in the constant table
-    uint32_t b_at;           // BUS: its leaf claim's number
-};
-
-// the job of a workgroup: the last one whose first_wg is <= wg
-__device__ __forceinline__ uint32_t zb_job_of(const ZbJob* __restrict__ jobs, uint32_t n, uint32_t wg) {
-    uint32_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].first_wg <= wg) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // workgroups of a job that hold pairs in round i (i < m): the single-AIR grid_w, within the job's range
 __device__ __forceinline__ uint32_t zb_wgs(uint32_t m, uint32_t i, uint32_t n_wg) {
     const uint64_t pairs = (uint64_t)1 << (m - i - 1), need = (pairs + ZC_W - 1) / ZC_W;
     return (uint32_t)(need < n_wg ? need : n_wg);
-}
-
-// round 0 of every job of one class
-template <unsigned D, bool BUS>
-__global__ __launch_bounds__(ZC_W) void k_zb_round0(const ZbJob* __restrict__ jobs, uint32_t n) {
-    const ZbJob jb = jobs[zb_job_of(jobs, n, blockIdx.x)];
-    zc_round0_body<D, BUS, false>(jb.pg, jb.trace, nullptr, jb.m, jb.E, jb.E2, jb.partial, blockIdx.x - jb.first_wg, jb.n_wg);
-}
-
-// round i >= 1 of every job of one class that is still alive: fold with r_{i-1} and evaluate; a job with m = i runs its last fold only
-template <unsigned D, bool FROM_BASE, bool BUS>
-__global__ __launch_bounds__(ZC_W) void k_zb_pass(const ZbJob* __restrict__ jobs, uint32_t n, uint32_t i, const uint32_t* __restrict__ r_ptr) {
-    const ZbJob jb = jobs[zb_job_of(jobs, n, blockIdx.x)];
-    if (jb.m < i) return;
-    const size_t sA = (size_t)1 << (jb.m - 1), sB = jb.m >= 2 ? (size_t)1 << (jb.m - 2) : 1;
-    ZcTabs tb{};
-    tb.trace = jb.trace, tb.E = jb.E, tb.E2 = jb.E2, tb.rot = jb.rot, tb.m = jb.m, tb.w = jb.w, tb.n_rot = jb.n_rot;
-    tb.nd = (size_t)1 << (jb.m - i);
-    if (i & 1u) tb.src = jb.tB, tb.src_stride = sB, tb.dst = jb.tA, tb.dst_stride = sA;
-    else tb.src = jb.tA, tb.src_stride = sA, tb.dst = jb.tB, tb.dst_stride = sB;
-    ZcProg pg = jb.pg;
-    pg.code = jb.xcode;
-    zc_pass_body<D, FROM_BASE, BUS, false>(pg, tb, ZcPrep{}, r_ptr, jb.m == i ? nullptr : jb.partial, blockIdx.x - jb.first_wg, jb.n_wg);
 }
 
 // one interaction of a BUS job: its denominators' constant part leaves through the claim
@@ -221,12 +170,12 @@ __global__ __launch_bounds__(ZB_TR) void k_zb_round_tr(DevTranscript* tr, const 
     }
 }
 
-// v, v' of every job: entry 0 of the tables its last fold wrote, canonical, to out + val_at
+// v, v' (v_p, v_p') of every job: entry 0 of the tables its last fold wrote, canonical, to out + val_at
 __global__ __launch_bounds__(64) void k_zb_emit(const ZbJob* __restrict__ jobs, uint32_t* __restrict__ out) {
     const ZbJob& jb = jobs[blockIdx.x];
     const uint32_t* tab = (jb.m & 1u) ? jb.tA : jb.tB;
     const size_t stride = (jb.m & 1u) ? (size_t)1 << (jb.m - 1) : (jb.m >= 2 ? (size_t)1 << (jb.m - 2) : 1);
-    for (unsigned i = threadIdx.x; i < 4 * (jb.w + jb.n_rot); i += 64) out[jb.val_at + i] = from_monty(tab[4 * (size_t)(i >> 2) * stride + (i & 3u)]);
+    for (unsigned i = threadIdx.x; i < 4 * (jb.w + jb.n_rot + jb.pp.wp + jb.pp.n_rot); i += 64) out[jb.val_at + i] = from_monty(tab[4 * (size_t)(i >> 2) * stride + (i & 3u)]);
 }
 
 // ---- the batched rotation reduction ----------------------------------------------------------------------------------------------
@@ -244,12 +193,19 @@ struct ZbRot {
     uint32_t m, w, n_rot;
     uint32_t wgt;            // 2^(M' - m), Montgomery
     uint32_t u_at;           // its u in the proof's u section (words)
+    ZcPrep pp;               // the keyed form: the job's
 };
 
 // F_a and F_b of every reducing AIR: blockIdx.y is the AIR
 __global__ __launch_bounds__(256) void k_zb_combine(const ZbRot* __restrict__ jobs) {
     const ZbRot jb = jobs[blockIdx.y];
     zc_combine_body<false>(jb.trace, (size_t)1 << jb.m, jb.w, jb.rot, jb.n_rot, ZcPrep{}, jb.lpow, jb.fa, jb.fb);
+}
+
+// the keyed form: lambda's powers run on over [v_p | v_p'], F_a gains the key's columns and F_b the rotated ones
+__global__ __launch_bounds__(256) void k_zb_combine_p(const ZbRot* __restrict__ jobs) {
+    const ZbRot jb = jobs[blockIdx.y];
+    zc_combine_body<true>(jb.trace, (size_t)1 << jb.m, jb.w, jb.rot, jb.n_rot, jb.pp, jb.lpow, jb.fa, jb.fb);
 }
 
 // Round t of the reduction for every AIR with m >= t (blockIdx.y): from round 1 on the four tables are folded with r'_{t-1} first (from
@@ -350,24 +306,5 @@ __global__ __launch_bounds__(256) void k_zb_dot(const ZbCol* __restrict__ cols, 
     zk_syncthreads();
     if (threadIdx.x < 4) out[c.out_at + threadIdx.x] = from_monty(s[threadIdx.x]);
 }
-
-namespace {
-template <unsigned D, bool BUS>
-void zb_launch_d(hipStream_t st, unsigned grid, size_t lds, const ZbJob* jobs, uint32_t n, unsigned i, const uint32_t* r) {
-    if (i == 0) hipLaunchKernelGGL((k_zb_round0<D, BUS>), dim3(grid), dim3(ZC_W), lds, st, jobs, n);
-    else if (i == 1) hipLaunchKernelGGL((k_zb_pass<D, true, BUS>), dim3(grid), dim3(ZC_W), lds, st, jobs, n, i, r);
-    else hipLaunchKernelGGL((k_zb_pass<D, false, BUS>), dim3(grid), dim3(ZC_W), lds, st, jobs, n, i, r);
-}
-// round i of the class (D, bus) over its n jobs
-void zb_launch(unsigned D, bool bus, hipStream_t st, unsigned grid, size_t lds, const ZbJob* jobs, uint32_t n, unsigned i, const uint32_t* r) {
-    switch (D) {
-#define ZB_CASE(d) \
-    case d:        \
-        return bus ? zb_launch_d<d, true>(st, grid, lds, jobs, n, i, r) : zb_launch_d<d, false>(st, grid, lds, jobs, n, i, r);
-        ZB_CASE(1) ZB_CASE(2) ZB_CASE(3) ZB_CASE(4) ZB_CASE(5) ZB_CASE(6) ZB_CASE(7) ZB_CASE(8)
-#undef ZB_CASE
-    }
-}
-}  // namespace
 
 }  // namespace zk

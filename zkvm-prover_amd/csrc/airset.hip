@@ -22,7 +22,7 @@
 //    per active AIR 4 D_a m + 4 (w + n_rot + w_p + n_rot_p) (+ 8 m + 4 (w + w_p) if n_rot + n_rot_p > 0) |
 //    zkhip_stack_proof_words(main columns, log_stack) | zkhip_stack_proof_words(preprocessed columns, log_stack_prep)]
 //
-// The batched form of both (zkhip_airbatch_*, docs/airbatch.md, model tests/airbatch_model.py; kernels in airbatch_dev.hpp): the same
+// The batched form of both (zkhip_airbatch_*, docs/airbatch.md, model tests/airbatch_model.py; kernels: airbatch_dev.hpp, airbatch_pass.hip): the same
 // statements with ONE constraint sum-check and ONE rotation reduction for the whole set, every AIR's point a prefix of the same r (r');
 // shape(), prove_bus() and the stacked opening are shared, prove_batch() and verify_batch() below are its own.
 #include <map>
@@ -690,33 +690,38 @@ struct BatchShape {
     bool any_cons = false;
     size_t o_rounds = 0, o_vals = 0, o_red = 0, o_u = 0, head = 0, total = 0;   // words; head: before the stacked opening
 };
-bool batch_shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus, BatchShape* T) {
-    if (!shape(prm, airs, n_airs, l, with_bus, &T->S)) return false;
+// l_prep >= 0: the keyed form (shape()'s pass-through); its values and u carry the preprocessed parts, and the key's opening follows
+bool batch_shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus, BatchShape* T, int l_prep = -1) {
+    if (!shape(prm, airs, n_airs, l, with_bus, &T->S, l_prep)) return false;
     size_t vals = 0, us = 0;
     for (size_t a = 0; a < n_airs; a++) {
         const ZcPlan& pl = T->S.plans[a];
         if (!pl.active()) continue;
         T->act.push_back(a);
         T->M = std::max(T->M, pl.m), T->D = std::max(T->D, pl.D), T->any_cons |= !pl.proven.empty();
-        vals += 4 * (pl.w + pl.rot.size());
-        if (pl.reduces()) T->red.push_back(a), T->M2 = std::max(T->M2, pl.m), us += 4 * pl.w;
+        vals += 4 * (pl.w + pl.rot.size() + pl.wp + pl.rot_p.size());   // wp = 0 and rot_p empty in the unkeyed form
+        if (pl.reduces()) T->red.push_back(a), T->M2 = std::max(T->M2, pl.m), us += 4 * (pl.w + pl.wp);
     }
     T->o_rounds = 8 + (with_bus ? T->S.gkr_words + 4 * T->S.n_bus : 0);
     T->o_vals = T->o_rounds + 4 * (size_t)T->D * T->M;
     T->o_red = T->o_vals + vals;
     T->o_u = T->o_red + (T->red.empty() ? 0 : 8 * (size_t)T->M2);
     T->head = T->o_u + us;
-    T->total = T->head + T->S.main_words;
+    T->total = T->head + (T->S.total - T->S.head);   // the main opening (keyed: then the key's)
     return true;
 }
 
 // the device prover: one upload, one workspace, launches that do not grow with the number of AIRs
+// key: the keyed form (prm, airs and n_airs are the key's); an AIR with preprocessed columns runs the kernels' PREP form on the key's
+// resident columns, and the key's commitment is opened after the main one
 int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
-                const uint32_t* const* pvs, unsigned l, bool with_bus, DevTranscript* d_t, uint32_t* proof_out, size_t cap, uint32_t* root_out) {
-    const std::string who = "airbatch: ";
+                const uint32_t* const* pvs, unsigned l, bool with_bus, DevTranscript* d_t, uint32_t* proof_out, size_t cap, uint32_t* root_out,
+                const zkhip_airkey* key = nullptr) {
+    const std::string who = key ? "airkey batch: " : "airbatch: ";
     hipStream_t st = ctx->stream;
     BatchShape T;
-    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T)) return set_error(ctx, ZKHIP_ERR_INVALID, who + "the shape does not fit the limits");
+    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T, key ? (int)key->l_prep : -1))
+        return set_error(ctx, ZKHIP_ERR_INVALID, who + "the shape does not fit the limits");
     const Shape& S = T.S;
     if (cap < T.total) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, who + "proof buffer too small");
     size_t n_pv = 0, inact_words = 0;
@@ -729,9 +734,9 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
     }
     const unsigned M = T.M, D = T.D, M2 = T.M2;
     const size_t n_jobs = T.act.size(), n_red = T.red.size();
-    // the jobs: a (D, BUS) class is a run of the table, tallest first; the lowered programs
+    // the jobs: a (D, BUS, PREP) class is a run of the table, tallest first; the lowered programs
     std::vector<size_t> order(T.act);
-    auto cls = [&](size_t a) { return 2 * S.plans[a].D + (with_bus && !S.plans[a].prog.ints.empty() ? 1u : 0u); };
+    auto cls = [&](size_t a) { return 4 * S.plans[a].D + (with_bus && !S.plans[a].prog.ints.empty() ? 2u : 0u) + (S.plans[a].wp ? 1u : 0u); };
     std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return cls(x) != cls(y) ? cls(x) < cls(y) : S.plans[x].m > S.plans[y].m; });
     std::vector<CompiledAir> ca(n_jobs);
     size_t n_cons_max = 1, up_words = 0, tab_words = 0, n_cst = 0, n_ucols = 0, red_vals = 0;
@@ -744,10 +749,11 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
         if (compile_air(pl.prog, &ca[k], &err, &roots) != 0 || ca[k].n_slots > ZC_MAX_SLOTS)
             return set_error(ctx, ZKHIP_ERR_INVALID, who + (err.empty() ? "an AIR needs more than 64 live intermediates" : err));
         n_cons_max = std::max(n_cons_max, pl.proven.size());
-        up_words += pad4(2 * ca[k].code.size() + ca[k].consts.size() + pl.prog.n_pvs + pl.rot.size());
-        const size_t n = (size_t)1 << pl.m, nt = pl.w + pl.rot.size() + (with_bus && !pl.prog.ints.empty() ? 4 : 3);
+        const size_t n_val = pl.w + pl.rot.size() + pl.wp + pl.rot_p.size();   // [v | v' | v_p | v_p']: wp = 0 and rot_p empty without a key
+        up_words += pad4(2 * ca[k].code.size() + ca[k].consts.size() + pl.prog.n_pvs + pl.rot.size() + pl.rot_p.size());
+        const size_t n = (size_t)1 << pl.m, nt = n_val + (with_bus && !pl.prog.ints.empty() ? 4 : 3);
         tab_words += 4 * (size_t)pl.D * SC_NB + 4 * nt * (n / 2) + 4 * nt * std::max<size_t>(n / 4, 1);
-        if (pl.reduces()) tab_words += 8 * n + 8 * SC_NB, n_ucols += pl.w, red_vals += pl.w + pl.rot.size();
+        if (pl.reduces()) tab_words += 8 * n + 8 * SC_NB, n_ucols += pl.w + pl.wp, red_vals += n_val;
         if (with_bus) n_cst += pl.prog.ints.size();
     }
     std::map<unsigned, size_t> eq_at;   // height of an AIR with proven constraints -> its eq table (words from d_ws)
@@ -776,16 +782,18 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
     DevBufs B(ctx);
     // device: [the words before the opening | r (4 M) | r' (4 M') | the inactive AIRs' points], all read back at once
     const size_t o_r = T.head, o_rp = o_r + 4 * (size_t)M, o_inact = o_rp + 4 * (size_t)M2, back_words = o_inact + inact_words;
-    uint32_t *dP = B.get(back_words), *d_obs = B.get(8 + n_pv), *d_ws = B.get(ws_words);
+    uint32_t *dP = B.get(back_words), *d_obs = B.get((key ? 16 : 8) + n_pv), *d_ws = B.get(ws_words);
     if (!dP || !d_obs || !d_ws) return set_error(ctx, ZKHIP_ERR_NOMEM, who + "the workspace does not fit");
-    std::vector<uint32_t> obs(root, root + 8);
+    std::vector<uint32_t> obs;
+    if (key) obs.assign(key->root, key->root + 8);   // the key's root is observed, not sent
+    obs.insert(obs.end(), root, root + 8);
     for (size_t a = 0; a < n_airs; a++) obs.insert(obs.end(), pvs[a], pvs[a] + airs[a].n_pvs);
     ZK_TRY(zkhip_h2d(ctx, d_obs, obs.data(), obs.size() * 4));
     ZK_TRY(transcript_observe(ctx, d_t, d_obs, (uint32_t)obs.size(), true));
     // 2. - 5. the bus part
     std::vector<ZcBus> bus(n_airs);
     const uint32_t* chal = nullptr;
-    if (with_bus) ZK_TRY(prove_bus(ctx, S, airs, n_airs, d_traces, pvs, d_t, B, dP, &bus, nullptr, &chal));
+    if (with_bus) ZK_TRY(prove_bus(ctx, S, airs, n_airs, d_traces, pvs, d_t, B, dP, &bus, key, &chal));
     // the one upload: programs, constants, public values, rotation lists, the interpolation weights, the job tables
     std::vector<uint32_t> up(up_total, 0);
     std::vector<ZbJob> jobs(n_jobs);
@@ -797,8 +805,9 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
         size_t v = 0, u = 0, o = 0;
         for (size_t a : T.act) {
             const ZcPlan& pl = S.plans[a];
-            val_at[a] = v, v += 4 * (pl.w + pl.rot.size());
-            if (pl.reduces()) u_at[a] = u, u += 4 * pl.w, lam_at[a] = o, o += pl.w + pl.rot.size();
+            const size_t n_val = pl.w + pl.rot.size() + pl.wp + pl.rot_p.size();
+            val_at[a] = v, v += 4 * n_val;
+            if (pl.reduces()) u_at[a] = u, u += 4 * (pl.w + pl.wp), lam_at[a] = o, o += n_val;
         }
     }
     uint32_t *tau = d_ws + o_chal, *alpha = tau + 4 * M, *mu = alpha + 4, *lambda = mu + 4;
@@ -806,7 +815,7 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
     struct Cls {
         size_t lo, n;
         unsigned D, slots;
-        bool bus;
+        bool bus, prep;
     };
     std::vector<Cls> classes;
     {
@@ -816,8 +825,8 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
             const size_t a = order[k];
             const ZcPlan& pl = S.plans[a];
             const bool has_bus = with_bus && !pl.prog.ints.empty();
-            const unsigned w = (unsigned)pl.w, n_rot = (unsigned)pl.rot.size();
-            if (classes.empty() || cls(order[classes.back().lo]) != cls(a)) classes.push_back({k, 0, pl.D, 1, has_bus}), wg = 0;
+            const unsigned w = (unsigned)pl.w, n_rot = (unsigned)pl.rot.size(), wp = (unsigned)pl.wp, n_rot_p = (unsigned)pl.rot_p.size();
+            if (classes.empty() || cls(order[classes.back().lo]) != cls(a)) classes.push_back({k, 0, pl.D, 1, has_bus, wp != 0}), wg = 0;
             classes.back().n++, classes.back().slots = std::max(classes.back().slots, ca[k].n_slots);
             const size_t n_code = ca[k].code.size(), n_ins = n_code / 3;
             uint32_t* h = up.data() + at;
@@ -828,18 +837,22 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
                 for (int q = 1; q < 3; q++) {
                     const uint32_t o = ca[k].code[3 * i + q];
                     x[q] = (o >> 28) != K_VAR ? o : (K_VAR << 28) | (((o >> 27) & 1u) ? w + (uint32_t)pl.rot_of[o & 0x07ffffffu] : (o & 0x07ffffffu));
+                    if (wp && (o >> 28) == K_PREP)   // the preprocessed tables follow the main ones
+                        x[q] = (K_VAR << 28) | (w + n_rot + (((o >> 27) & 1u) ? wp + (uint32_t)pl.rot_p_of[o & 0x07ffffffu] : (o & 0x07ffffffu)));
                 }
             }
             uint32_t* hp = h + 2 * n_code;
             hp = std::copy(ca[k].consts.begin(), ca[k].consts.end(), hp);
             for (uint32_t i = 0; i < pl.prog.n_pvs; i++) *hp++ = to_monty(pvs[a][i]);
-            std::copy(pl.rot.begin(), pl.rot.end(), hp);
+            hp = std::copy(pl.rot.begin(), pl.rot.end(), hp);
+            std::copy(pl.rot_p.begin(), pl.rot_p.end(), hp);
             const uint32_t* d = d_ws + at;
-            const size_t n = (size_t)1 << pl.m, nt = w + n_rot + (has_bus ? 4 : 3);
+            const size_t n = (size_t)1 << pl.m, nt = w + n_rot + wp + n_rot_p + (has_bus ? 4 : 3);
             ZbJob& jb = jobs[k];
             jb = ZbJob{};
             jb.pg = ZcProg{d, (unsigned)n_ins, d + 2 * n_code, d + 2 * n_code + ca[k].consts.size(), d_ws + o_apow, bus[a].coef, (unsigned)pl.proven.size()};
             jb.xcode = d + n_code, jb.trace = d_traces[a], jb.rot = d + 2 * n_code + ca[k].consts.size() + pl.prog.n_pvs;
+            if (wp) jb.pp = ZcPrep{key->d_prep + key->prep_at[a], jb.rot + n_rot, wp, n_rot_p};   // the key's columns of this AIR
             jb.E2 = bus[a].E2, jb.E = pl.proven.empty() ? bus[a].E2 : d_ws + eq_at[pl.m];
             jb.partial = d_ws + tabs, tabs += 4 * (size_t)pl.D * SC_NB;
             jb.tA = d_ws + tabs, tabs += 4 * nt * (n / 2);
@@ -854,20 +867,23 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
                 for (const Interaction& it : pl.prog.ints) cst.push_back({root_at, to_monty(it.bus + 1), it.sign}), root_at += 1 + it.n_fields;
             }
             job_of[a] = k;
-            at += pad4(2 * n_code + ca[k].consts.size() + pl.prog.n_pvs + n_rot);
+            at += pad4(2 * n_code + ca[k].consts.size() + pl.prog.n_pvs + n_rot + n_rot_p);
             if (pl.reduces()) {   // its reduction buffers follow its tables
                 ZbRot& rj = rots[std::find(T.red.begin(), T.red.end(), a) - T.red.begin()];
                 rj = ZbRot{};
                 rj.trace = d_traces[a], rj.rot = jb.rot, rj.lpow = d_ws + o_lpow + 4 * lam_at[a], rj.E = d_ws + eq_at[pl.m];
                 rj.fa = d_ws + tabs, rj.fb = rj.fa + 4 * n, tabs += 8 * n;
                 rj.partial = d_ws + tabs, tabs += 8 * SC_NB;
-                rj.tA = jb.tA, rj.tB = jb.tB, rj.m = pl.m, rj.w = w, rj.n_rot = n_rot;
+                rj.tA = jb.tA, rj.tB = jb.tB, rj.m = pl.m, rj.w = w, rj.n_rot = n_rot, rj.pp = jb.pp;
                 rj.wgt = mpow(to_monty(2), M2 - pl.m), rj.u_at = (uint32_t)u_at[a];
             }
         }
-        for (size_t a : T.red)
-            for (size_t c = 0; c < S.plans[a].w; c++)
-                ucols.push_back({d_traces[a] + (c << S.plans[a].m), d_ws + eq_at[S.plans[a].m], S.plans[a].m, (uint32_t)(u_at[a] + 4 * c)});
+        for (size_t a : T.red) {   // u, then u_p from the key's columns
+            const ZcPlan& pl = S.plans[a];
+            for (size_t c = 0; c < pl.w; c++) ucols.push_back({d_traces[a] + (c << pl.m), d_ws + eq_at[pl.m], pl.m, (uint32_t)(u_at[a] + 4 * c)});
+            for (size_t c = 0; c < pl.wp; c++)
+                ucols.push_back({key->d_prep + key->prep_at[a] + (c << pl.m), d_ws + eq_at[pl.m], pl.m, (uint32_t)(u_at[a] + 4 * (pl.w + c))});
+        }
         // s(t), t > d, from s(0..d); and 1 / prod_{i != t} (t - i) over 0..D
         auto small = [](unsigned x) { return to_monty(x); };
         for (unsigned d = 1; d < ZB_PTS; d++)
@@ -914,7 +930,7 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
             if (!alive) continue;
             const ZbJob& last = jobs[c.lo + alive - 1];
             KernelScope ks(ctx, i ? "zb_pass" : "zb_round0");
-            zb_launch(c.D, c.bus, st, last.first_wg + last.n_wg, (size_t)c.slots * ZC_W * (i ? 16 : 4), d_jobs + c.lo, (uint32_t)alive, i,
+            zb_launch(c.D, c.bus, c.prep, st, last.first_wg + last.n_wg, (size_t)c.slots * ZC_W * (i ? 16 : 4), d_jobs + c.lo, (uint32_t)alive, i,
                       i ? d_r + 4 * (i - 1) : nullptr);
         }
         if (i < M) {
@@ -948,7 +964,8 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
         }
         {
             KernelScope ks(ctx, "zb_combine");
-            hipLaunchKernelGGL(k_zb_combine, dim3(grid_of((size_t)1 << M2), (unsigned)n_red), dim3(256), 0, st, d_rots);
+            if (key) hipLaunchKernelGGL(k_zb_combine_p, dim3(grid_of((size_t)1 << M2), (unsigned)n_red), dim3(256), 0, st, d_rots);
+            else hipLaunchKernelGGL(k_zb_combine, dim3(grid_of((size_t)1 << M2), (unsigned)n_red), dim3(256), 0, st, d_rots);
         }
         ZK_HIP_CHECK(ctx, hipGetLastError());
         const ZbRotTr rtr{d_ws + o_state, dP + T.o_red, d_rp};
@@ -980,16 +997,21 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
     std::vector<uint32_t> h(back_words);
     ZK_TRY(zkhip_d2h(ctx, h.data(), dP, h.size() * 4));
     for (size_t i = T.head; i < h.size(); i++) h[i] = from_monty(h[i]);
-    std::vector<uint32_t> points;
+    std::vector<uint32_t> points, points_p;   // points_p: of the AIRs that have preprocessed columns, for the key's opening
     size_t in_at = o_inact;
     for (size_t a = 0; a < n_airs; a++) {
         const ZcPlan& pl = S.plans[a];
         const size_t from = !pl.active() ? in_at : pl.reduces() ? o_rp : o_r;
         points.insert(points.end(), h.begin() + from, h.begin() + from + 4 * (size_t)pl.m);
+        if (key && pl.wp) points_p.insert(points_p.end(), h.begin() + from, h.begin() + from + 4 * (size_t)pl.m);
         if (!pl.active()) in_at += 4 * (size_t)pl.m;
     }
-    // 10. the one stacked opening
+    // 10. the one stacked opening (keyed: then the key's commitment, on the same transcript)
     ZK_TRY(stack_open(ctx, com.sc, d_t, points.data(), S.dims.data(), n_airs, S.col_point.data(), nullptr, proof_out + T.head, cap - T.head));
+    if (key) {
+        const size_t o = T.head + S.main_words;
+        ZK_TRY(stack_open(ctx, key->sc, d_t, points_p.data(), S.dims_p.data(), S.dims_p.size(), S.col_point_p.data(), nullptr, proof_out + o, cap - o));
+    }
     memcpy(proof_out, root, 32);
     memcpy(proof_out + 8, h.data() + 8, (T.head - 8) * 4);
     if (root_out) memcpy(root_out, root, 32);
@@ -997,11 +1019,15 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
 }
 
 // the host verifier of the batched proof; pq_out: with_bus only
+// prep_root: the keyed form, checked against the key's root at l_prep (never reads prep_trace)
 int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs, const uint32_t* const* pvs,
-                 unsigned l, const uint32_t* proof, size_t words, bool with_bus, uint32_t* root_out, uint32_t* pq_out) {
+                 unsigned l, const uint32_t* proof, size_t words, bool with_bus, uint32_t* root_out, uint32_t* pq_out,
+                 const uint32_t* prep_root = nullptr, unsigned l_prep = 0) {
     BatchShape T;
-    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T)) return ZKHIP_ERR_INVALID;
+    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T, prep_root ? (int)l_prep : -1)) return ZKHIP_ERR_INVALID;
     const Shape& S = T.S;
+    for (size_t i = 0; prep_root && i < 8; i++)
+        if (prep_root[i] >= P) return ZKHIP_ERR_INVALID;
     for (size_t a = 0; a < n_airs; a++) {
         if (airs[a].n_pvs && !pvs[a]) return ZKHIP_ERR_INVALID;
         for (size_t i = 0; i < airs[a].n_pvs; i++)
@@ -1014,6 +1040,7 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
         if (proof[i] >= P) return ZKHIP_ERR_VERIFY;
     HostChallenger ch;
     ch.observe_canon(prefix, n_prefix);
+    if (prep_root) ch.observe_canon(prep_root, 8);
     ch.observe_canon(proof, 8);
     for (size_t a = 0; a < n_airs; a++) ch.observe_canon(pvs[a], airs[a].n_pvs);
     const Ext one = ext_one();
@@ -1091,26 +1118,29 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
     // 7. the values: sum_j mu^j [eq(tau_a, r_a) sum_k alpha^k C_k + eq(rho_a, r_a) (the bus part)] = the last claim
     ch.observe_canon(q, T.o_red - T.o_vals);
     std::vector<const uint32_t*> vals(n_airs, nullptr), claimed(n_airs, nullptr);
+    std::vector<const uint32_t*> claimed_p(n_airs, nullptr);   // keyed: the w_p values the key's opening must show
     Ext rhs = ext_zero();
     mup = one;
     for (size_t a : T.act) {
         const ZcPlan& pl = S.plans[a];
         const unsigned m = pl.m;
-        const size_t w = pl.w, n_rot = pl.rot.size();
-        std::vector<Ext> v(w), vn(n_rot);
+        const size_t w = pl.w, n_rot = pl.rot.size(), wp = pl.wp, n_rot_p = pl.rot_p.size();
+        std::vector<Ext> v(w), vn(n_rot), vp(wp), vpn(n_rot_p);   // v, v', v_p, v_p'
         for (size_t j = 0; j < w; j++) v[j] = ext_from_canon(q + 4 * j);
         for (size_t t = 0; t < n_rot; t++) vn[t] = ext_from_canon(q + 4 * (w + t));
-        vals[a] = q, q += 4 * (w + n_rot);
+        for (size_t j = 0; j < wp; j++) vp[j] = ext_from_canon(q + 4 * (w + n_rot + j));
+        for (size_t t = 0; t < n_rot_p; t++) vpn[t] = ext_from_canon(q + 4 * (w + n_rot + wp + t));
+        vals[a] = q, q += 4 * (w + n_rot + wp + n_rot_p);
         Ext first = one, last = one, g = ext_zero();
         for (unsigned j = 0; j < m; j++) first = ext_mul(first, ext_sub(one, r[j])), last = ext_mul(last, r[j]);
         if (!pl.proven.empty()) {
-            const std::vector<Ext> val = zc_eval_host(pl, pl.reach, v.data(), vn.data(), first, last, pvs[a]);
+            const std::vector<Ext> val = zc_eval_host(pl, pl.reach, v.data(), vn.data(), first, last, pvs[a], vp.data(), vpn.data());
             Ext c = ext_zero(), ap = one;
             for (uint32_t k : pl.proven) c = ext_add(c, ext_mul(ap, val[k])), ap = ext_mul(ap, alpha);
             g = ext_mul(eq_eval(tau.data(), r.data(), m), c);
         }
         if (!pl.bus_roots.empty()) {
-            const std::vector<Ext> val = zc_eval_host(pl, pl.bus_reach, v.data(), vn.data(), first, last, pvs[a]);
+            const std::vector<Ext> val = zc_eval_host(pl, pl.bus_reach, v.data(), vn.data(), first, last, pvs[a], vp.data(), vpn.data());
             Ext c = ext_zero();
             for (size_t k = 0; k < coef[a].size(); k++) c = ext_add(c, ext_mul(coef[a][k], val[pl.bus_roots[k]]));
             g = ext_add(g, ext_mul(eq_eval(rho.data(), r.data(), m), c));
@@ -1122,13 +1152,14 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
     // 8. the batched rotation reduction
     if (!T.red.empty()) {
         const Ext lambda = ch.sample_ext();
-        std::vector<std::vector<Ext>> lp(n_airs);   // lambda^(o_a + k) over the AIR's [v | v']
+        std::vector<std::vector<Ext>> lp(n_airs);   // lambda^(o_a + k) over the AIR's [v | v' | v_p | v_p']
         Ext x = one;
         claim = ext_zero();
         for (size_t a : T.red) {
             const ZcPlan& pl = S.plans[a];
             Ext acc = ext_zero();
-            for (size_t k = 0; k < pl.w + pl.rot.size(); k++) lp[a].push_back(x), acc = ext_add(acc, ext_mul(x, ext_from_canon(vals[a] + 4 * k))), x = ext_mul(x, lambda);
+            const size_t n_val = pl.w + pl.rot.size() + pl.wp + pl.rot_p.size();
+            for (size_t k = 0; k < n_val; k++) lp[a].push_back(x), acc = ext_add(acc, ext_mul(x, ext_from_canon(vals[a] + 4 * k))), x = ext_mul(x, lambda);
             claim = ext_add(claim, ext_mul(ext_pow(two, M2 - pl.m), acc));
         }
         for (unsigned i = 0; i < M2; i++, q += 8) {
@@ -1145,7 +1176,11 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
             Ext ua = ext_zero(), ub = ext_zero();
             for (size_t j = 0; j < pl.w; j++) ua = ext_add(ua, ext_mul(lp[a][j], ext_from_canon(q + 4 * j)));
             for (size_t t = 0; t < pl.rot.size(); t++) ub = ext_add(ub, ext_mul(lp[a][pl.w + t], ext_from_canon(q + 4 * pl.rot[t])));
-            claimed[a] = q, q += 4 * pl.w;
+            const uint32_t* qp = q + 4 * pl.w;   // u_p
+            const size_t o = pl.w + pl.rot.size();
+            for (size_t j = 0; j < pl.wp; j++) ua = ext_add(ua, ext_mul(lp[a][o + j], ext_from_canon(qp + 4 * j)));
+            for (size_t t = 0; t < pl.rot_p.size(); t++) ub = ext_add(ub, ext_mul(lp[a][o + pl.wp + t], ext_from_canon(qp + 4 * pl.rot_p[t])));
+            claimed[a] = q, claimed_p[a] = pl.wp ? qp : nullptr, q += 4 * (pl.w + pl.wp);
             want = ext_add(want, ext_add(ext_mul(ua, eq_eval(r.data(), rp.data(), pl.m)), ext_mul(ub, zc_rot_eval(r.data(), rp.data(), pl.m))));
         }
         if (!ext_eq(want, claim)) return ZKHIP_ERR_VERIFY;
@@ -1154,7 +1189,7 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
     std::vector<uint32_t> points;
     for (size_t a = 0; a < n_airs; a++) {
         const ZcPlan& pl = S.plans[a];
-        if (pl.active() && !pl.reduces()) claimed[a] = vals[a];
+        if (pl.active() && !pl.reduces()) claimed[a] = vals[a], claimed_p[a] = pl.wp ? vals[a] + 4 * (pl.w + pl.rot.size()) : nullptr;
         for (unsigned j = 0; j < pl.m; j++) {
             uint32_t c4[4];
             ext_to_canon(c4, !pl.active() ? ch.sample_ext() : pl.reduces() ? rp[j] : r[j]);
@@ -1166,6 +1201,18 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
     size_t col = 0;
     for (size_t a = 0; a < n_airs; col += airs[a].width, a++)
         if (claimed[a] && memcmp(claimed[a], op + 4 * col, 16 * airs[a].width) != 0) return ZKHIP_ERR_VERIFY;
+    if (prep_root) {   // the key's opening, against the verifier's own root: an inactive AIR with preprocessed columns is in it too
+        std::vector<uint32_t> pts;
+        size_t at = 0;
+        for (size_t a = 0; a < n_airs; at += 4 * (size_t)S.plans[a].m, a++)
+            if (S.plans[a].wp) pts.insert(pts.end(), points.begin() + at, points.begin() + at + 4 * (size_t)S.plans[a].m);
+        const uint32_t* op2 = op + S.main_words;
+        ZK_TRY(stack_verify_host(ch, prm, prep_root, S.lh_p.data(), S.lh_p.size(), l_prep, pts.data(), S.dims_p.data(), S.dims_p.size(),
+                                 S.col_point_p.data(), op2, words - T.head - S.main_words));
+        col = 0;
+        for (size_t a = 0; a < n_airs; col += S.plans[a].wp, a++)
+            if (claimed_p[a] && memcmp(claimed_p[a], op2 + 4 * col, 16 * S.plans[a].wp) != 0) return ZKHIP_ERR_VERIFY;
+    }
     if (root_out) memcpy(root_out, proof, 32);
     if (pq_out && with_bus) memcpy(pq_out, proof + 8, 32);
     return ZKHIP_OK;
@@ -1289,6 +1336,29 @@ int zkhip_airkey_verify(const zkhip_whir_params* params, const uint32_t* prefix,
     if (!params || (n_prefix && !prefix) || !airs || !prep_root || !pvs || !proof || log_stack_prep > ZKHIP_WHIR_MAX_LOG_N) return ZKHIP_ERR_INVALID;
     return verify(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, root_out, with_bus ? pq_out : nullptr, prep_root,
                   log_stack_prep);
+}
+
+size_t zkhip_airkey_batch_proof_words(const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, unsigned log_stack,
+                                      unsigned log_stack_prep, int with_bus) {
+    if (log_stack_prep > ZKHIP_WHIR_MAX_LOG_N) return 0;
+    BatchShape T;
+    return batch_shape(params, airs, n_airs, log_stack, with_bus != 0, &T, (int)log_stack_prep) ? T.total : 0;
+}
+
+int zkhip_airkey_batch_prove(zkhip_ctx* ctx, zkhip_airkey* key, int with_bus, const uint32_t* const* d_traces, const uint32_t* const* pvs,
+                             unsigned log_stack, zkhip_transcript* transcript, uint32_t* proof_out, size_t cap, uint32_t* root_out) {
+    ZK_BIND_DEVICE(ctx);
+    if (!ctx || !key || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
+    return prove_batch(ctx, &key->params, key->airs.data(), key->airs.size(), d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out,
+                       cap, root_out, key);
+}
+
+int zkhip_airkey_batch_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
+                              const uint32_t* prep_root, unsigned log_stack_prep, const uint32_t* const* pvs, unsigned log_stack, int with_bus,
+                              const uint32_t* proof, size_t words, uint32_t* root_out, uint32_t* pq_out) {
+    if (!params || (n_prefix && !prefix) || !airs || !prep_root || !pvs || !proof || log_stack_prep > ZKHIP_WHIR_MAX_LOG_N) return ZKHIP_ERR_INVALID;
+    return verify_batch(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, root_out, pq_out, prep_root,
+                        log_stack_prep);
 }
 
 int zkhip_zerocheck_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
