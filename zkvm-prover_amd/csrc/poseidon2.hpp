@@ -26,6 +26,10 @@ struct Poseidon2Diag {
     static constexpr uint32_t INV_8 = (1u << 29);             // 2^-3  * 2^32
     static constexpr uint32_t INV_16 = (1u << 28);            // 2^-4  * 2^32
     static constexpr uint32_t INV_2_27 = (1u << 5);           // 2^-27 * 2^32
+    // the whole diagonal, Montgomery form (n * 2^32 mod p = n * 0x0ffffffe for the small integers)
+    static constexpr uint32_t MONTY[16] = {
+        P - 0x1ffffffcu, 0x0ffffffeu, 0x1ffffffcu, 0x07ffffffu, 0x2ffffffau, 0x3ffffff8u, P - 0x07ffffffu, P - 0x2ffffffau,
+        P - 0x3ffffff8u, INV_2_8,     INV_4,       INV_8,       INV_2_27,    P - INV_2_8, P - INV_16,      P - INV_2_27};
 };
 
 ZK_HD uint32_t mdouble(uint32_t x) { return red_2p(x << 1); }
@@ -122,6 +126,126 @@ ZK_HD void p2_internal_linear(uint32_t s[16]) {
     s[13] = msub(sum, mdiv_pow2<8>(s[13]));                   // -1/2^8
     s[14] = msub(sum, mdiv_pow2<4>(s[14]));                   // -1/16
     s[15] = msub(sum, mdiv_pow2<27>(s[15]));                  // -1/2^27
+}
+
+// ---- the thirteen partial rounds with the linear layer deferred ---------------------------------------------------------------
+// Lanes 1..15 pass no S-box between the two external groups, so the round-wise form canonicalises them thirteen times for nothing.
+// With v = lanes 1..15 at entry, y_r = lane 0 after round r's S-box and sum_r = y_r + (sum of lanes 1..15 before round r):
+//     sum_r   = y_r + SUM_i d_i^r v_i + SUM_{k<r} A_{r-1-k} sum_k,     A_j = SUM_i d_i^j   (i = 1..15)
+//     lane 0 <- sum_r - 2 y_r
+//     v_13,i  = d_i^13 v_i + SUM_{k<13} d_i^{12-k} sum_k
+// -- dot products of the untouched v and the thirteen sums with constant rows, exact field arithmetic, so every word is what the
+// round-wise form gives.  All weights are Montgomery residues in [0, p) computed at compile time from the diagonal; the table is
+// laid out in the order the rounds consume it:
+//     round r at r*16 + r(r-1)/2:  rc_r - p,  d_1^r .. d_15^r,  A_{r-1} .. A_0          (16 + r words)
+//     lane i at 286 + 14 (i - 1):  d_i^13, d_i^12 .. d_i^0                              (14 words)
+constexpr int P2D_FINAL_OFF = 13 * 16 + 78, P2D_WORDS = P2D_FINAL_OFF + 15 * 14;
+struct Poseidon2Deferred {
+    uint32_t v[P2D_WORDS];
+};
+constexpr uint32_t p2d_mulmod(uint32_t a, uint32_t b) { return (uint32_t)((uint64_t)a * b % P); }
+constexpr Poseidon2Deferred poseidon2_deferred_table() {
+    uint32_t rinv = 1, b = MONTY_ONE;                       // 2^-32 = (2^32)^(p-2) mod p
+    for (uint32_t e = P - 2; e; e >>= 1) {
+        if (e & 1) rinv = p2d_mulmod(rinv, b);
+        b = p2d_mulmod(b, b);
+    }
+    uint32_t pw[16][14] = {}, a[13] = {};                   // pw[i][j] = d_i^j, a[j] = A_j, Montgomery form
+    for (int i = 1; i < 16; i++) {
+        pw[i][0] = MONTY_ONE;
+        for (int j = 1; j < 14; j++) pw[i][j] = p2d_mulmod(p2d_mulmod(pw[i][j - 1], Poseidon2Diag::MONTY[i]), rinv);
+    }
+    for (int j = 0; j < 13; j++)
+        for (int i = 1; i < 16; i++) a[j] = (uint32_t)(((uint64_t)a[j] + pw[i][j]) % P);
+    Poseidon2Deferred t{};
+    for (int r = 0; r < 13; r++) {
+        const int o = r * 16 + r * (r - 1) / 2;
+        t.v[o] = Poseidon2Consts::RC[64 + r] - P;
+        for (int i = 1; i < 16; i++) t.v[o + i] = pw[i][r];
+        for (int k = 0; k < r; k++) t.v[o + 16 + k] = a[r - 1 - k];
+    }
+    for (int i = 1; i < 16; i++)
+        for (int k = 0; k < 14; k++) t.v[P2D_FINAL_OFF + 14 * (i - 1) + k] = pw[i][13 - k];
+    return t;
+}
+struct Poseidon2DeferredConsts {
+    static constexpr Poseidon2Deferred T = poseidon2_deferred_table();
+};
+
+// Unsigned 64-bit accumulation of products of residues in [0, p): four products stay below 4 p^2 < 2^64 (2^64 = 4.55 p^2).  A fold
+// replaces the high word h by h * (2^32 mod p) = h * (2^28 - 2): t < 2^60 + 2^32 < 0.29 p^2 afterwards, so four more products fit
+// (4.29 p^2).  One multiply-class instruction per four products instead of a reduction per term.
+// (device: the folded value is pinned with an empty asm -- the compiler otherwise sums every group of four into an accumulator of its own
+// and pays a 64-bit addition per group to join them)
+ZK_HD uint64_t p2d_fold(uint64_t t) {
+    t = (uint64_t)(uint32_t)(t >> 32) * MONTY_ONE + (uint32_t)t;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(t));
+#endif
+    return t;
+}
+// t * 2^-32 mod p in [0, p): after a fold t < 0.29 p^2, so (t + m p) / 2^32 < 0.14 p + p < 2p and one conditional subtraction ends it
+// (t + m p < 0.29 p^2 + 2^32 p < 2^64)
+ZK_HD uint32_t p2d_reduce(uint64_t t) {
+    t = p2d_fold(t);
+    const uint32_t m = (uint32_t)t * MONTY_NEG_MU;
+    return red_2p((uint32_t)((t + (uint64_t)m * P) >> 32));
+}
+// One more product into the accumulator, folding first when it already holds four (n is a compile-time count after unrolling).
+#define ZK_P2D_MAC(x, wk)                      \
+    do {                                       \
+        if (n == 4) t = p2d_fold(t), n = 0;    \
+        t += (uint64_t)(x) * (wk);             \
+        n++;                                   \
+    } while (0)
+// s: the state between the two external groups, every word in [0, p); w: the table above (constant address space on the device, so the
+// weights arrive by scalar loads and take no vector registers).  Every diagonal entry takes the general product: a term costs one
+// v_mad_u64_u32 (4.2 issue cycles), and no specialised form of a +-1, +-2^k entry is cheaper than that -- a modular addition alone is
+// three full-rate instructions (6.6), docs/partial_rounds.md.
+template <class W>
+ZK_HD void p2_internal_rounds_deferred(uint32_t (&s)[16], W w) {
+    uint32_t sm[13];
+#pragma unroll
+    for (int r = 0; r < 13; r++) {
+        const int o = r * 16 + r * (r - 1) / 2;
+        uint64_t t = 0;
+        int n = 0;
+#pragma unroll
+        for (int i = 1; i < 16; i++) ZK_P2D_MAC(s[i], w[o + i]);
+#pragma unroll
+        for (int k = 0; k < r; k++) ZK_P2D_MAC(sm[k], w[o + 16 + k]);
+        const uint32_t y = sbox7_rcs(s[0], w[o]);
+        ZK_P2D_MAC(y, MONTY_ONE);
+        sm[r] = p2d_reduce(t);
+        s[0] = msub(sm[r], mdouble(y));                       // -2 y + sum, as in p2_internal_linear
+    }
+#pragma unroll
+    for (int i = 1; i < 16; i++) {
+        const int o = P2D_FINAL_OFF + 14 * (i - 1);
+        uint64_t t = (uint64_t)s[i] * w[o];
+        int n = 1;
+#pragma unroll
+        for (int k = 0; k < 13; k++) ZK_P2D_MAC(sm[k], w[o + 1 + k]);
+        s[i] = p2d_reduce(t);
+    }
+}
+#undef ZK_P2D_MAC
+// the whole permutation with the deferred partial rounds (host and device): what the bulk kernels' rolled form computes
+ZK_HD void poseidon2_permute_deferred(uint32_t (&s)[16]) {
+    p2_external_linear(s);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) s[i] = sbox7_rc(s[i], Poseidon2Consts::RC[r * 16 + i]);
+        p2_external_linear(s);
+    }
+    p2_internal_rounds_deferred(s, Poseidon2DeferredConsts::T.v);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) s[i] = sbox7_rc(s[i], Poseidon2Consts::RC[77 + r * 16 + i]);
+        p2_external_linear(s);
+    }
 }
 
 ZK_HD void poseidon2_permute(uint32_t s[16]) {

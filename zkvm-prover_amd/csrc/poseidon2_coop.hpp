@@ -44,6 +44,8 @@ constexpr Poseidon2RcShifted poseidon2_rc_shifted() {
 }
 static __constant__ const Poseidon2RcShifted POSEIDON2_RCS_CONST = poseidon2_rc_shifted();
 __device__ const Poseidon2RcShifted POSEIDON2_RCS_DEV = poseidon2_rc_shifted();
+// weights of the deferred partial rounds (poseidon2.hpp), read by scalar loads like the round constants
+static __constant__ const Poseidon2Deferred POSEIDON2_DEFERRED_CONST = poseidon2_deferred_table();
 __device__ __forceinline__ void poseidon2_permute_rolled(uint32_t (&s)[16]) {
     typedef const __attribute__((address_space(4))) uint32_t* cptr;
     cptr rc = (cptr)POSEIDON2_RCS_CONST.v;
@@ -54,11 +56,21 @@ __device__ __forceinline__ void poseidon2_permute_rolled(uint32_t (&s)[16]) {
         for (int i = 0; i < 16; i++) s[i] = sbox7_rcs(s[i], rc[r * 16 + i]);
         p2_external_linear(s);
     }
+#ifdef ZK_P2_ROUNDWISE
+    // the round-wise partial rounds (every lane canonical after every round), kept for A/B builds
 #pragma unroll 1
     for (int r = 0; r < 13; r++) {
         s[0] = sbox7_rcs(s[0], rc[64 + r]);
         p2_internal_linear(s);
     }
+#else
+    // the linear layer deferred over the thirteen rounds (poseidon2.hpp), straight-line: the sums stay in registers
+    // (the table's address passes through an empty asm: with every index a constant the compiler would otherwise fold the loads into
+    // ~500 literals, move half of them into vector registers and turn the power-of-two weights into 64-bit shifts)
+    cptr w = (cptr)POSEIDON2_DEFERRED_CONST.v;
+    asm("" : "+s"(w));
+    p2_internal_rounds_deferred(s, w);
+#endif
 #pragma unroll 1
     for (int r = 0; r < 4; r++) {
 #pragma unroll
