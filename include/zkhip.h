@@ -627,7 +627,7 @@ int zkhip_stack_verify(const zkhip_whir_params *params, const uint32_t *prefix, 
 
 /* ---- the AIR zero-check (docs/zerocheck.md): a proof that the main traces of n_airs AIRs satisfy, on every row, the constraints of
  *      their programs that reach no PERM / CHAL / EXPOSED leaf (what air.py check_trace checks; the LogUp-phase constraints are the
- *      bus proof's business).  All main columns (AIRs in caller order, columns in column order; a cached-main section is ignored) are
+ *      bus proof's business).  All main columns (AIRs in caller order, columns in column order; a cached-main section is ignored except by zkhip_airkey_cached_*) are
  *      ONE stacked WHIR commitment at log_stack; per AIR a sum-check of log_height rounds of degree D = d + 1 (d = the largest
  *      multilinear degree of a proven constraint: cells, is_first, is_last, is_transition count 1), the column values at its point,
  *      a degree-2 reduction of the next-row values to the same columns, and one stacked opening with one point per AIR.
@@ -745,6 +745,46 @@ int zkhip_airkey_batch_prove(zkhip_ctx *ctx, zkhip_airkey *key, int with_bus, co
 int zkhip_airkey_batch_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const zkhip_air *airs, size_t n_airs,
                               const uint32_t *prep_root, unsigned log_stack_prep, const uint32_t *const *pvs, unsigned log_stack,
                               int with_bus, const uint32_t *proof, size_t words, uint32_t *root_out, uint32_t *pq_out);
+
+/* ---- the keyed batched form with cached partitions (docs/cached_main.md): the keyed batched form for AIR sets in which an AIR's
+ *      program declares its first cached_width main columns a cached main partition (a CACHED section).  Each such AIR's partition is
+ *      ONE stacked WHIR commitment of its own (cached_width columns at the AIR's height, at log_stack_cached[a]), made once, outside
+ *      any proof, by zkhip_airkey_commit_cached and used by any number of proofs; the proof's main commitment holds the common columns
+ *      only (columns cached_width .. width - 1 of every AIR).  After prep_root both sides observe the cached roots (sent, AIR order),
+ *      then the main root; the bus part, the sum-check, the values and the reduction are zkhip_airkey_batch_prove's (a cached column
+ *      is a main column to the programs, v, v' and u); after the main opening and the key's comes, per AIR with a partition in AIR
+ *      order, one stacked opening of the partition's commitment at that AIR's point, whose values must equal the first cached_width
+ *      entries of u (of v where the AIR does not reduce; an inactive AIR's stand).
+ *      Proof words: [cached roots 8 n_c | root 8 | the keyed batched form's middle | zkhip_stack_proof_words(common columns, log_stack)
+ *      | the key's opening | per cached AIR zkhip_stack_proof_words(cached_width columns of its height, log_stack_cached[a])].
+ *      Refused (ZKHIP_ERR_INVALID; zkhip_airkey_cached_proof_words returns 0): what zkhip_airkey_batch_* refuses with the same
+ *      with_bus, a set in which no AIR has a CACHED section (zkhip_airkey_batch_*'s case), a partition zkhip_stack_width refuses at
+ *      its log_stack_cached[a], common columns it refuses at log_stack; at prove time a cached AIR whose handle is NULL or was made
+ *      for another AIR index, height, width or parameter set.  log_stack_cached has n_airs entries, read only where the AIR has a
+ *      CACHED section. ---- */
+typedef struct zkhip_cached_main zkhip_cached_main;
+/* Commits the first cached_width columns of the key's AIR `air`.  d_cols: device, column-major Montgomery, stride 1 << log_height (the
+ * AIR's trace pointer will do).  The handle owns a gathered copy of the columns: it may outlive d_cols, is never modified by a prove
+ * call and serves any number of them; zkhip_airkey_destroy does not destroy it.  root_out: HOST, 8 canonical words, may be NULL
+ * (synchronises): the program commitment a verifier compares the proof's cached root with. */
+int zkhip_airkey_commit_cached(zkhip_ctx *ctx, zkhip_airkey *key, size_t air, const uint32_t *d_cols, unsigned log_stack_cached,
+                               zkhip_cached_main **out, uint32_t *root_out);
+void zkhip_cached_main_destroy(zkhip_ctx *ctx, zkhip_cached_main *cached);
+size_t zkhip_airkey_cached_proof_words(const zkhip_whir_params *params, const zkhip_air *airs, size_t n_airs, unsigned log_stack,
+                                       unsigned log_stack_prep, const unsigned *log_stack_cached, int with_bus);
+/* Device prover; arguments as zkhip_airkey_batch_prove, plus cached: n_airs handles, NULL where the AIR has no CACHED section.
+ * d_traces[a] holds the whole trace, cached columns first; no partition is committed here.  Workspace as for
+ * zkhip_airkey_batch_prove. */
+int zkhip_airkey_cached_prove(zkhip_ctx *ctx, zkhip_airkey *key, int with_bus, const uint32_t *const *d_traces, const uint32_t *const *pvs,
+                              zkhip_cached_main *const *cached, unsigned log_stack, zkhip_transcript *transcript, uint32_t *proof_out,
+                              size_t cap, uint32_t *root_out);
+/* Host verifier, needs no device and reads neither a trace nor prep_trace.  Each cached opening is checked against the root the
+ * proof sent; cached_roots_out (8 n_c canonical words, AIR order, may be NULL) hands those roots back for the caller to compare with
+ * the commitments it holds. */
+int zkhip_airkey_cached_verify(const zkhip_whir_params *params, const uint32_t *prefix, size_t n_prefix, const zkhip_air *airs, size_t n_airs,
+                               const uint32_t *prep_root, unsigned log_stack_prep, const unsigned *log_stack_cached,
+                               const uint32_t *const *pvs, unsigned log_stack, int with_bus, const uint32_t *proof, size_t words,
+                               uint32_t *root_out, uint32_t *pq_out, uint32_t *cached_roots_out);
 
 /* Field offsets of a proof, in 32-bit words from its start (the layout is static for given parameters and AIR shapes:
  * DESIGN.md section 4).  The counterpart of `Proof::<SC>::decode_from_bytes` (crates/verifier/src/verifier.rs:62) for this

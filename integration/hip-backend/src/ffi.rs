@@ -91,6 +91,10 @@ pub struct zkhip_stack_commitment {
 pub struct zkhip_airkey {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct zkhip_cached_main {
+    _private: [u8; 0],
+}
 
 // docs/whir.md
 #[repr(C)]
@@ -483,6 +487,19 @@ extern "C" {
                                      n_airs: usize, prep_root: *const u32, log_stack_prep: c_uint, pvs: *const *const u32,
                                      log_stack: c_uint, with_bus: c_int, proof: *const u32, words: usize, root_out: *mut u32,
                                      pq_out: *mut u32) -> c_int;
+    // the keyed batched form with cached main partitions: each partition a commitment of its own, made once (docs/cached_main.md)
+    pub fn zkhip_airkey_commit_cached(ctx: *mut zkhip_ctx, key: *mut zkhip_airkey, air: usize, d_cols: *const u32, log_stack_cached: c_uint,
+                                      out: *mut *mut zkhip_cached_main, root_out: *mut u32) -> c_int;
+    pub fn zkhip_cached_main_destroy(ctx: *mut zkhip_ctx, cached: *mut zkhip_cached_main);
+    pub fn zkhip_airkey_cached_proof_words(params: *const zkhip_whir_params, airs: *const zkhip_air, n_airs: usize, log_stack: c_uint,
+                                           log_stack_prep: c_uint, log_stack_cached: *const c_uint, with_bus: c_int) -> usize;
+    pub fn zkhip_airkey_cached_prove(ctx: *mut zkhip_ctx, key: *mut zkhip_airkey, with_bus: c_int, d_traces: *const *const u32,
+                                     pvs: *const *const u32, cached: *const *mut zkhip_cached_main, log_stack: c_uint,
+                                     transcript: *mut zkhip_transcript, proof_out: *mut u32, cap: usize, root_out: *mut u32) -> c_int;
+    pub fn zkhip_airkey_cached_verify(params: *const zkhip_whir_params, prefix: *const u32, n_prefix: usize, airs: *const zkhip_air,
+                                      n_airs: usize, prep_root: *const u32, log_stack_prep: c_uint, log_stack_cached: *const c_uint,
+                                      pvs: *const *const u32, log_stack: c_uint, with_bus: c_int, proof: *const u32, words: usize,
+                                      root_out: *mut u32, pq_out: *mut u32, cached_roots_out: *mut u32) -> c_int;
 
     // the reference's stored-proof container (OpenVM-v1 Proof<SC>, bincode)
     pub fn zkhip_proof_decode_v1(bytes: *const u8, len: usize, kind: c_int, out: *mut zkhip_v1_summary) -> c_int;

@@ -5,11 +5,14 @@ calls zkhip_zerocheck_prove plus zkhip_bus_gkr_prove (which prove less: their bu
 zkhip_prove.  Shapes: the lookup key of tools/gkr_bench.py (a sender of 2^20 rows, a table of 2^16) and the 42-chip ChipSet with a
 main-column range table in place of its preprocessed one, and `chipset42_keyed`: ChipSet().gen() as generated, with its preprocessed
 range table, proven through the key (Context.airkey; key generation is timed on its own, log_stack_prep = 4): a `keyed` row
-(AirKey.prove) and, from the same key in the same run, a `keyed_batch` row (AirKey.prove_batch).  Parameters (b, k, final_log) = (1, 4, 6), 80 queries and 16 bits of
+(AirKey.prove) and, from the same key in the same run, a `keyed_batch` row (AirKey.prove_batch); `chipset42_cached`: the same set with
+the four leading columns of chip 30 (one of its tallest, 2^16 rows, 8 columns) declared a cached main partition (docs/cached_main.md,
+log_stack_cached = 16): a `keyed_batch` row (AirKey.prove_batch, which ignores the section), a `cached_batch` row
+(AirKey.prove_batch_cached) and a `commit_cached` row (AirKey.commit_cached, once per program) from the same key in the same run.  Parameters (b, k, final_log) = (1, 4, 6), 80 queries and 16 bits of
 grinding in every round; v1 parameters z.DEFAULT_PARAMS.  Every figure is the median of --reps runs after one warm-up.  Prints one
 JSON object.
 
-  python tools/airset_bench.py [--reps 3] [--shapes lookup20x16,chipset42,chipset42_keyed] [--no-v1]"""
+  python tools/airset_bench.py [--reps 3] [--shapes lookup20x16,chipset42,chipset42_keyed,chipset42_cached] [--no-v1]"""
 import argparse
 import json
 import os
@@ -43,13 +46,24 @@ def _chipset():
     return chips + [dict(program=tb.program(), log_height=1, width=2, n_pvs=0, trace=np.array([[0, 1], counts % z.P], dtype=np.uint32), pvs=NOPV)]
 
 
+CACHED_CHIP, CACHED_WIDTH, CACHED_LOG_STACK = 30, 4, 16
+
+
+def _chipset_cached():
+    airs = air.ChipSet().gen()
+    airs[CACHED_CHIP] = dict(airs[CACHED_CHIP], program=air.with_cached_width(airs[CACHED_CHIP]["program"], CACHED_WIDTH))
+    return airs
+
+
 SHAPES = {
     # (AIRs, log_stack)
     "lookup20x16": (lambda: _lookup(20, 16), 20),
     "chipset42": (_chipset, 20),
     "chipset42_keyed": (lambda: air.ChipSet().gen(), 20),
+    "chipset42_cached": (_chipset_cached, 20),
 }
-KEYED = {"chipset42_keyed": 4}   # shape -> log_stack_prep
+KEYED = {"chipset42_keyed": 4, "chipset42_cached": 4}   # shape -> log_stack_prep
+CACHED = {"chipset42_cached": {CACHED_CHIP: CACHED_LOG_STACK}}   # shape -> AIR -> log_stack_cached
 
 
 def _group(by_name):
@@ -69,7 +83,8 @@ def main():
     a = ap.parse_args()
     zk = z.Context(0)
     prm = z.WhirParams.make(1, 4, 6, 16, 80)
-    out = {"airbatch": [], "airset": [], "zerocheck": [], "bus_gkr": [], "v1": [], "keyed": [], "keyed_batch": [], "keygen": []}
+    out = {"airbatch": [], "airset": [], "zerocheck": [], "bus_gkr": [], "v1": [], "keyed": [], "keyed_batch": [], "keygen": [],
+           "cached_batch": [], "commit_cached": []}
 
     def note(r):
         print(json.dumps({k: v for k, v in r.items() if k != "by_name"}), file=sys.stderr)
@@ -108,6 +123,27 @@ def main():
                      zb_launches={n: v["launches"] for n, v in r["by_name"].items() if n.startswith("zb_")})
             out["keyed_batch"].append(r)
             note(r)
+            if name in CACHED:   # the same set with the partition committed once, outside the proof (docs/cached_main.md)
+                lsc = [CACHED[name].get(i) for i in range(len(airs))]
+                r = _profiled(zk, lambda: [key.commit_cached(i, d[i], x).close() for i, x in enumerate(lsc) if x is not None], a.reps)
+                r.update(common, log_stack_cached=CACHED[name])
+                out["commit_cached"].append(r)
+                note(r)
+                cached = [key.commit_cached(i, d[i], x) if x is not None else None for i, x in enumerate(lsc)]
+
+                def cached_batch():
+                    proof["c"] = key.prove_batch_cached(d, pvs, cached, l, [1])[1]
+
+                r = _profiled(zk, cached_batch, a.reps)
+                roots = z.airkey_cached_verify(prm, [1], vairs, key.root, lpr, lsc, pvs, l, proof["c"])[2]
+                assert roots.tolist() == [c.root.tolist() for c in cached if c is not None]
+                r.update(common, log_stack_prep=lpr, proof_words=z.airkey_cached_proof_words(prm, vairs, l, lpr, lsc), split=_group(r["by_name"]),
+                         zb_launches={n: v["launches"] for n, v in r["by_name"].items() if n.startswith("zb_")})
+                out["cached_batch"].append(r)
+                note(r)
+                for c in cached:
+                    if c is not None:
+                        c.close()
             key.close()
             if not a.no_v1:
                 pk = z.ProvingKey(zk, z.DEFAULT_PARAMS, airs)

@@ -349,6 +349,12 @@ def load_library():
                                                 u32p, sz, u32p, u32p]),
         "zkhip_airkey_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, C.POINTER(_Air), sz, u32p, C.c_uint, C.POINTER(u32p), C.c_uint, C.c_int,
                                           u32p, sz, u32p, u32p]),
+        "zkhip_airkey_commit_cached": (C.c_int, [vp, vp, sz, vp, C.c_uint, C.POINTER(vp), u32p]),
+        "zkhip_cached_main_destroy": (None, [vp, vp]),
+        "zkhip_airkey_cached_proof_words": (sz, [C.POINTER(WhirParams), C.POINTER(_Air), sz, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.c_int]),
+        "zkhip_airkey_cached_prove": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(u32p), C.POINTER(vp), C.c_uint, vp, u32p, sz, u32p]),
+        "zkhip_airkey_cached_verify": (C.c_int, [C.POINTER(WhirParams), u32p, sz, C.POINTER(_Air), sz, u32p, C.c_uint, C.POINTER(C.c_uint),
+                                                 C.POINTER(u32p), C.c_uint, C.c_int, u32p, sz, u32p, u32p, u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -1434,9 +1440,32 @@ class AirKey:
         airkey_batch_verify."""
         return self._prove(True, traces, pvs, log_stack, prefix, with_bus)
 
-    def _prove(self, batch, traces, pvs, log_stack, prefix, with_bus):
+    def commit_cached(self, air_index, trace, log_stack_cached):
+        """The cached main partition of the key's AIR `air_index` (docs/cached_main.md): the first cached_width columns of `trace` (a
+        device tensor, column-major Montgomery, stride 2^log_height: the AIR's whole trace will do) in ONE stacked commitment at
+        log_stack_cached.  The CachedMain owns a copy of the columns, serves any number of prove_batch_cached calls and is closed by
+        the caller; its `root` is the commitment a verifier compares the proof's cached root with."""
+        h = C.c_void_p()
+        root = np.zeros(8, dtype=np.uint32)
+        self.ctx._check(self.ctx.lib.zkhip_airkey_commit_cached(self.ctx.h, self.h, air_index, trace.data_ptr(), log_stack_cached, C.byref(h),
+                                                                _u32p(root)))
+        a = self.airs[air_index]
+        return CachedMain(self.ctx, h, air_index, int(a["log_height"]), _cached_width_of(a["program"]), log_stack_cached, root)
+
+    def prove_batch_cached(self, traces, pvs, cached, log_stack, prefix, with_bus=True):
+        """The keyed batched proof with cached partitions: `cached` has one entry per AIR, a CachedMain where the AIR's program has a
+        CACHED section and None elsewhere; `traces` hold the whole traces, cached columns first.  Returns (root of the common
+        columns' commitment, proof words); check with airkey_cached_verify."""
+        if len(cached) != len(self.airs):
+            raise ZkhipError("prove_batch_cached: one entry of `cached` per AIR")
+        lsc = [c.log_stack_cached if c is not None else 0 for c in cached]
+        return self._prove(True, traces, pvs, log_stack, prefix, with_bus, cached=cached,
+                           words=airkey_cached_proof_words(self.params, self.airs, log_stack, self.log_stack_prep, lsc, with_bus))
+
+    def _prove(self, batch, traces, pvs, log_stack, prefix, with_bus, cached=None, words=None):
         ctx = self.ctx
-        words = (airkey_batch_proof_words if batch else airkey_proof_words)(self.params, self.airs, log_stack, self.log_stack_prep, with_bus)
+        if cached is None:
+            words = (airkey_batch_proof_words if batch else airkey_proof_words)(self.params, self.airs, log_stack, self.log_stack_prep, with_bus)
         tr = Transcript(ctx)
         pre = np.ascontiguousarray(prefix, dtype=np.uint32)
         if pre.size:
@@ -1445,8 +1474,13 @@ class AirKey:
         pa, keep = _pvs_array(pvs)
         proof = np.zeros(max(words, 1), dtype=np.uint32)
         root = np.zeros(8, dtype=np.uint32)
-        fn = ctx.lib.zkhip_airkey_batch_prove if batch else ctx.lib.zkhip_airkey_prove
-        rc = fn(ctx.h, self.h, int(bool(with_bus)), tp, pa, log_stack, tr.h, _u32p(proof), proof.size, _u32p(root))
+        if cached is not None:
+            cp = (C.c_void_p * len(cached))(*[c.h if c is not None else None for c in cached])
+            rc = ctx.lib.zkhip_airkey_cached_prove(ctx.h, self.h, int(bool(with_bus)), tp, pa, cp, log_stack, tr.h, _u32p(proof), proof.size,
+                                                   _u32p(root))
+        else:
+            fn = ctx.lib.zkhip_airkey_batch_prove if batch else ctx.lib.zkhip_airkey_prove
+            rc = fn(ctx.h, self.h, int(bool(with_bus)), tp, pa, log_stack, tr.h, _u32p(proof), proof.size, _u32p(root))
         tr.close()
         ctx._check(rc)
         return root, proof[:words]
@@ -1454,6 +1488,35 @@ class AirKey:
     def close(self):
         if self.h:
             self.ctx.lib.zkhip_airkey_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _cached_width_of(program):
+    """the cached_width of an AIR program's CACHED section (after the constraints and the PREP section), 0 without one"""
+    w = np.asarray(program).reshape(-1)
+    q = 4 + 3 * int(w[1]) + int(w[2])
+    if q + 2 <= w.size and int(w[q]) == 0x50504B5A:   # PREP_MAGIC
+        q += 2
+    return int(w[q + 1]) if q + 2 <= w.size and int(w[q]) == 0x43414B5A else 0   # CACHED_MAGIC
+
+
+class CachedMain:
+    """A cached main partition (zkhip_cached_main): the stacked commitment of the first `cached_width` main columns of the AIR
+    `air_index` of a key, at `log_stack_cached`; `root` is its 8 canonical words.  Made by AirKey.commit_cached."""
+
+    def __init__(self, ctx, h, air_index, log_height, cached_width, log_stack_cached, root):
+        self.ctx, self.h, self.root = ctx, h, root
+        self.air_index, self.log_height, self.cached_width, self.log_stack_cached = air_index, log_height, cached_width, log_stack_cached
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.zkhip_cached_main_destroy(self.ctx.h, self.h)
             self.h = None
 
     def __del__(self):
@@ -1583,6 +1646,45 @@ def airkey_batch_proof_words(params, airs, log_stack, log_stack_prep, with_bus=T
     """words of a keyed batched proof of these AIR shapes (`prep` is not read); 0 for a refused shape"""
     arr, keep = _air_structs([{k: v for k, v in a.items() if k != "prep"} for a in airs])
     return int(load_library().zkhip_airkey_batch_proof_words(C.byref(params), arr, len(airs), log_stack, log_stack_prep, int(bool(with_bus))))
+
+
+def _cached_stacks(airs, log_stack_cached):
+    lsc = np.ascontiguousarray([0 if x is None else int(x) for x in log_stack_cached], dtype=np.uint32)
+    if lsc.size != len(airs):
+        raise ZkhipError("log_stack_cached holds one entry per AIR")
+    return lsc
+
+
+def airkey_cached_proof_words(params, airs, log_stack, log_stack_prep, log_stack_cached, with_bus=True):
+    """words of a keyed batched proof with cached partitions (docs/cached_main.md); log_stack_cached: one entry per AIR, read where the
+    AIR's program has a CACHED section (None will do elsewhere); 0 for a refused shape"""
+    arr, keep = _air_structs([{k: v for k, v in a.items() if k != "prep"} for a in airs])
+    lsc = _cached_stacks(airs, log_stack_cached)
+    return int(load_library().zkhip_airkey_cached_proof_words(C.byref(params), arr, len(airs), log_stack, log_stack_prep, _uip(lsc),
+                                                              int(bool(with_bus))))
+
+
+def airkey_cached_verify(params, prefix, airs, prep_root, log_stack_prep, log_stack_cached, pvs, log_stack, proof, with_bus=True):
+    """Host verifier of a keyed batched proof with cached partitions (AirKey.prove_batch_cached; needs no GPU, reads neither a trace nor
+    `prep`).  Returns what airkey_batch_verify returns plus the cached roots the proof sent, an [n_c, 8] array in AIR order: (root,
+    cached_roots), with_bus: (root, (P, Q), cached_roots).  Comparing them with the commitments the caller holds is the caller's part."""
+    lib = load_library()
+    pre, pw = _gkr_words(prefix, proof)
+    arr, keep = _air_structs([{k: v for k, v in a.items() if k != "prep"} for a in airs])
+    pa, keep2 = _pvs_array(pvs)
+    pr = np.ascontiguousarray(prep_root, dtype=np.uint32).reshape(-1)
+    if pr.size != 8:
+        raise ZkhipError("airkey_cached_verify: prep_root holds 8 words")
+    lsc = _cached_stacks(airs, log_stack_cached)
+    n_c = sum(1 for a in airs if _cached_width_of(a["program"]))
+    root, pq, cr = np.zeros(8, dtype=np.uint32), np.zeros(8, dtype=np.uint32), np.zeros((max(n_c, 1), 8), dtype=np.uint32)
+    rc = lib.zkhip_airkey_cached_verify(C.byref(params), _u32p(pre), pre.size, arr, len(airs), _u32p(pr), log_stack_prep, _uip(lsc), pa, log_stack,
+                                        int(bool(with_bus)), _u32p(pw), pw.size, _u32p(root), _u32p(pq), _u32p(cr))
+    if rc != 0:
+        e = ZkhipError("zkhip_airkey_cached_verify refused the proof (%d)" % rc)
+        e.code = rc
+        raise e
+    return (root, pq, cr[:n_c]) if with_bus else (root, cr[:n_c])
 
 
 def airkey_batch_verify(params, prefix, airs, prep_root, log_stack_prep, pvs, log_stack, proof, with_bus=True):

@@ -25,6 +25,11 @@
 // The batched form of both (zkhip_airbatch_*, docs/airbatch.md, model tests/airbatch_model.py; kernels: airbatch_dev.hpp, airbatch_pass.hip): the same
 // statements with ONE constraint sum-check and ONE rotation reduction for the whole set, every AIR's point a prefix of the same r (r');
 // shape(), prove_bus() and the stacked opening are shared, prove_batch() and verify_batch() below are its own.
+//
+// The keyed batched form with cached partitions (zkhip_airkey_cached_*, docs/cached_main.md, model tests/cached_batch_model.py): an AIR's
+// leading cached_width main columns are a stacked commitment of their own, made once (zkhip_cached_main); the main commitment holds the
+// common columns, the cached roots lead the transcript and the proof, and each partition is opened at its AIR's point after the key's
+// opening.  It is prove_batch() and verify_batch() with the handles / log_stack_cached as data; every other form ignores the section.
 #include <map>
 
 #include "airbatch_dev.hpp"
@@ -38,6 +43,16 @@ struct zkhip_airkey {
     uint32_t* d_prep = nullptr;                    // every preprocessed column end to end, Montgomery, AIRs in caller order
     std::vector<size_t> prep_at;                   // AIR -> its first word in d_prep
     zkhip_stack_commitment* sc = nullptr;          // the stacked commitment of those columns at l_prep
+    uint32_t root[8] = {};
+};
+
+// a cached main partition (docs/cached_main.md): the stacked commitment of the first cw main columns of one AIR of a key, made once by
+// zkhip_airkey_commit_cached and opened, never modified, by every zkhip_airkey_cached_prove that is handed it
+struct zkhip_cached_main {
+    zkhip_whir_params params{};
+    size_t air = 0;                       // the AIR of the key it was made for
+    unsigned m = 0, cw = 0, l = 0;        // that AIR's log height, its cached width, log_stack_cached
+    zkhip_stack_commitment* sc = nullptr; // owns the gathered copy of the columns
     uint32_t root[8] = {};
 };
 
@@ -209,10 +224,17 @@ struct Shape {
     std::vector<unsigned> lh_p, col_point_p, dims_p;
     std::vector<size_t> prep_airs;   // the AIRs with preprocessed columns
     size_t main_words = 0;           // the main stacked opening's words (the key's opening follows it)
+    // the cached form only (docs/cached_main.md); elsewhere a CACHED section is ignored: cw is 0 everywhere and pre is 0
+    std::vector<size_t> cw;            // AIR -> its cached width: those leading columns are not in the main commitment
+    std::vector<size_t> cached_airs;   // the AIRs with a cached partition
+    std::vector<size_t> cached_words;  // per such AIR: the words of its partition's stacked opening (they follow the key's)
+    size_t pre = 0, prep_words = 0;    // the cached roots' words before the main root; the key's opening's words
 };
 // false = refused.  Without with_bus the AIRs' interactions are ignored: their plans have no bus roots (and another D).
 // l_prep >= 0: the keyed form at log_stack_prep = l_prep
-bool shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus, Shape* S, int l_prep = -1) {
+// l_cached (per AIR, read where the AIR has a CACHED section): the keyed form with cached partitions
+bool shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus, Shape* S, int l_prep = -1,
+           const unsigned* l_cached = nullptr) {
     const bool keyed = l_prep >= 0;
     if (!prm || !airs || n_airs < 1 || n_airs > ZKHIP_STACK_MAX_POINTS) return false;
     S->plans.resize(n_airs);
@@ -230,7 +252,9 @@ bool shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, u
         if (n_cols > ZKHIP_STACK_MAX_COLS) return false;
         S->head += pl.active() ? pl.words() : 0;
         S->dims.push_back(airs[a].log_height);
-        for (size_t c = 0; c < airs[a].width; c++) S->lh.push_back(airs[a].log_height), S->col_point.push_back((unsigned)a);
+        S->cw.push_back(l_cached ? pl.prog.cached_width : 0);
+        if (S->cw[a]) S->cached_airs.push_back(a);
+        for (size_t c = S->cw[a]; c < airs[a].width; c++) S->lh.push_back(airs[a].log_height), S->col_point.push_back((unsigned)a);
         if (!with_bus) continue;
         S->b_at.push_back(pl.prog.ints.empty() ? (size_t)-1 : S->n_bus++);
         for (size_t j = 0; j < pl.prog.ints.size(); j++) S->blocks.push_back({(unsigned)a, (unsigned)j, pl.m, 0});
@@ -255,7 +279,17 @@ bool shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, u
         if (S->prep_airs.empty()) return false;   // no PREP anywhere: the unkeyed calls' case
         const size_t sp = zkhip_stack_proof_words(prm, S->lh_p.data(), S->lh_p.size(), (unsigned)l_prep);
         if (!sp) return false;
-        S->total += sp;
+        S->prep_words = sp, S->total += sp;
+    }
+    if (l_cached) {
+        if (!keyed || S->cached_airs.empty()) return false;   // no CACHED anywhere: zkhip_airkey_batch_*'s case
+        for (size_t a : S->cached_airs) {
+            const std::vector<unsigned> lhc(S->cw[a], S->plans[a].m);
+            const size_t sc = zkhip_stack_proof_words(prm, lhc.data(), lhc.size(), l_cached[a]);
+            if (!sc) return false;
+            S->cached_words.push_back(sc), S->total += sc;
+        }
+        S->pre = 8 * S->cached_airs.size(), S->head += S->pre, S->total += S->pre;
     }
     return true;
 }
@@ -691,8 +725,10 @@ struct BatchShape {
     size_t o_rounds = 0, o_vals = 0, o_red = 0, o_u = 0, head = 0, total = 0;   // words; head: before the stacked opening
 };
 // l_prep >= 0: the keyed form (shape()'s pass-through); its values and u carry the preprocessed parts, and the key's opening follows
-bool batch_shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus, BatchShape* T, int l_prep = -1) {
-    if (!shape(prm, airs, n_airs, l, with_bus, &T->S, l_prep)) return false;
+// l_cached: the cached form (shape()'s pass-through): the cached roots lead the proof, the partitions' openings end it
+bool batch_shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, unsigned l, bool with_bus, BatchShape* T, int l_prep = -1,
+                 const unsigned* l_cached = nullptr) {
+    if (!shape(prm, airs, n_airs, l, with_bus, &T->S, l_prep, l_cached)) return false;
     size_t vals = 0, us = 0;
     for (size_t a = 0; a < n_airs; a++) {
         const ZcPlan& pl = T->S.plans[a];
@@ -702,27 +738,37 @@ bool batch_shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_a
         vals += 4 * (pl.w + pl.rot.size() + pl.wp + pl.rot_p.size());   // wp = 0 and rot_p empty in the unkeyed form
         if (pl.reduces()) T->red.push_back(a), T->M2 = std::max(T->M2, pl.m), us += 4 * (pl.w + pl.wp);
     }
-    T->o_rounds = 8 + (with_bus ? T->S.gkr_words + 4 * T->S.n_bus : 0);
+    T->o_rounds = T->S.pre + 8 + (with_bus ? T->S.gkr_words + 4 * T->S.n_bus : 0);
     T->o_vals = T->o_rounds + 4 * (size_t)T->D * T->M;
     T->o_red = T->o_vals + vals;
     T->o_u = T->o_red + (T->red.empty() ? 0 : 8 * (size_t)T->M2);
     T->head = T->o_u + us;
-    T->total = T->head + (T->S.total - T->S.head);   // the main opening (keyed: then the key's)
+    T->total = T->head + (T->S.total - T->S.head);   // the main opening (keyed: then the key's; cached: then the partitions')
     return true;
 }
 
 // the device prover: one upload, one workspace, launches that do not grow with the number of AIRs
 // key: the keyed form (prm, airs and n_airs are the key's); an AIR with preprocessed columns runs the kernels' PREP form on the key's
 // resident columns, and the key's commitment is opened after the main one
+// cached (per AIR, null where the AIR has no CACHED section): the cached form (docs/cached_main.md); the main commitment holds the
+// common columns only, the handles' roots lead the transcript and the proof, and each handle is opened at its AIR's point at the end
 int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
                 const uint32_t* const* pvs, unsigned l, bool with_bus, DevTranscript* d_t, uint32_t* proof_out, size_t cap, uint32_t* root_out,
-                const zkhip_airkey* key = nullptr) {
-    const std::string who = key ? "airkey batch: " : "airbatch: ";
+                const zkhip_airkey* key = nullptr, zkhip_cached_main* const* cached = nullptr) {
+    const std::string who = cached ? "airkey cached: " : key ? "airkey batch: " : "airbatch: ";
     hipStream_t st = ctx->stream;
     BatchShape T;
-    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T, key ? (int)key->l_prep : -1))
+    std::vector<unsigned> l_cached;
+    for (size_t a = 0; cached && a < n_airs; a++) l_cached.push_back(cached[a] ? cached[a]->l : 0);
+    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T, key ? (int)key->l_prep : -1, cached ? l_cached.data() : nullptr))
         return set_error(ctx, ZKHIP_ERR_INVALID, who + "the shape does not fit the limits");
     const Shape& S = T.S;
+    for (size_t a : S.cached_airs) {
+        const zkhip_cached_main* c = cached[a];
+        if (!c || !c->sc || c->air != a || c->m != S.plans[a].m || c->cw != S.cw[a] || memcmp(&c->params, prm, sizeof(*prm)) != 0)
+            return set_error(ctx, ZKHIP_ERR_INVALID, who + "a cached partition's handle is null or was made for another AIR, height or width");
+    }
+    const size_t pre = S.pre;
     if (cap < T.total) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, who + "proof buffer too small");
     size_t n_pv = 0, inact_words = 0;
     for (size_t a = 0; a < n_airs; a++) {
@@ -768,10 +814,10 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
     for (size_t a : T.act)
         if (!S.plans[a].proven.empty() && !eq_at.count(S.plans[a].m)) eq_at[S.plans[a].m] = o_end, o_end += 4 * ((size_t)1 << S.plans[a].m);
     const size_t o_tabs = o_end, ws_words = o_tabs + tab_words;
-    // 1. commit: every main column, AIRs in caller order
+    // 1. commit: every main column, AIRs in caller order (the cached form: the common columns; the partitions were committed before)
     std::vector<const uint32_t*> cols;
     for (size_t a = 0; a < n_airs; a++)
-        for (size_t c = 0; c < airs[a].width; c++) cols.push_back(d_traces[a] + (c << airs[a].log_height));
+        for (size_t c = S.cw[a]; c < airs[a].width; c++) cols.push_back(d_traces[a] + (c << airs[a].log_height));
     struct Com {
         zkhip_ctx* ctx;
         zkhip_stack_commitment* sc = nullptr;
@@ -782,10 +828,11 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
     DevBufs B(ctx);
     // device: [the words before the opening | r (4 M) | r' (4 M') | the inactive AIRs' points], all read back at once
     const size_t o_r = T.head, o_rp = o_r + 4 * (size_t)M, o_inact = o_rp + 4 * (size_t)M2, back_words = o_inact + inact_words;
-    uint32_t *dP = B.get(back_words), *d_obs = B.get((key ? 16 : 8) + n_pv), *d_ws = B.get(ws_words);
+    uint32_t *dP = B.get(back_words), *d_obs = B.get((key ? 16 : 8) + pre + n_pv), *d_ws = B.get(ws_words);
     if (!dP || !d_obs || !d_ws) return set_error(ctx, ZKHIP_ERR_NOMEM, who + "the workspace does not fit");
     std::vector<uint32_t> obs;
     if (key) obs.assign(key->root, key->root + 8);   // the key's root is observed, not sent
+    for (size_t a : S.cached_airs) obs.insert(obs.end(), cached[a]->root, cached[a]->root + 8);   // cached..., common
     obs.insert(obs.end(), root, root + 8);
     for (size_t a = 0; a < n_airs; a++) obs.insert(obs.end(), pvs[a], pvs[a] + airs[a].n_pvs);
     ZK_TRY(zkhip_h2d(ctx, d_obs, obs.data(), obs.size() * 4));
@@ -793,7 +840,7 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
     // 2. - 5. the bus part
     std::vector<ZcBus> bus(n_airs);
     const uint32_t* chal = nullptr;
-    if (with_bus) ZK_TRY(prove_bus(ctx, S, airs, n_airs, d_traces, pvs, d_t, B, dP, &bus, key, &chal));
+    if (with_bus) ZK_TRY(prove_bus(ctx, S, airs, n_airs, d_traces, pvs, d_t, B, dP + pre, &bus, key, &chal));
     // the one upload: programs, constants, public values, rotation lists, the interpolation weights, the job tables
     std::vector<uint32_t> up(up_total, 0);
     std::vector<ZbJob> jobs(n_jobs);
@@ -922,7 +969,7 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
     ZK_HIP_CHECK(ctx, hipGetLastError());
     ZbTr ztr{};
     ztr.mu = mu, ztr.lagx = d_ws + o_lagx, ztr.lagw = d_ws + o_lagw, ztr.cst = (const ZbCst*)(d_ws + o_cst), ztr.chal = chal;
-    ztr.dB = dP + 8 + S.gkr_words, ztr.wgt = d_ws + o_wgt, ztr.claim = d_ws + o_claim, ztr.proof = dP + T.o_rounds, ztr.r = d_r;
+    ztr.dB = dP + pre + 8 + S.gkr_words, ztr.wgt = d_ws + o_wgt, ztr.claim = d_ws + o_claim, ztr.proof = dP + T.o_rounds, ztr.r = d_r;
     for (unsigned i = 0; i <= M; i++) {   // round i; i = M: the tallest AIRs' last fold only
         for (const Cls& c : classes) {
             size_t alive = 0;   // the class's jobs are sorted tallest first: the ones with m >= i are a prefix
@@ -998,10 +1045,11 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
     ZK_TRY(zkhip_d2h(ctx, h.data(), dP, h.size() * 4));
     for (size_t i = T.head; i < h.size(); i++) h[i] = from_monty(h[i]);
     std::vector<uint32_t> points, points_p;   // points_p: of the AIRs that have preprocessed columns, for the key's opening
+    std::vector<size_t> pt_at(n_airs);        // AIR -> its point in h
     size_t in_at = o_inact;
     for (size_t a = 0; a < n_airs; a++) {
         const ZcPlan& pl = S.plans[a];
-        const size_t from = !pl.active() ? in_at : pl.reduces() ? o_rp : o_r;
+        const size_t from = pt_at[a] = !pl.active() ? in_at : pl.reduces() ? o_rp : o_r;
         points.insert(points.end(), h.begin() + from, h.begin() + from + 4 * (size_t)pl.m);
         if (key && pl.wp) points_p.insert(points_p.end(), h.begin() + from, h.begin() + from + 4 * (size_t)pl.m);
         if (!pl.active()) in_at += 4 * (size_t)pl.m;
@@ -1012,8 +1060,15 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
         const size_t o = T.head + S.main_words;
         ZK_TRY(stack_open(ctx, key->sc, d_t, points_p.data(), S.dims_p.data(), S.dims_p.size(), S.col_point_p.data(), nullptr, proof_out + o, cap - o));
     }
-    memcpy(proof_out, root, 32);
-    memcpy(proof_out + 8, h.data() + 8, (T.head - 8) * 4);
+    size_t o = T.head + S.main_words + S.prep_words;
+    for (size_t k = 0; k < S.cached_airs.size(); o += S.cached_words[k], k++) {   // each partition's commitment at its AIR's point
+        const size_t a = S.cached_airs[k];
+        const std::vector<unsigned> zero(S.cw[a], 0);
+        ZK_TRY(stack_open(ctx, cached[a]->sc, d_t, h.data() + pt_at[a], &S.dims[a], 1, zero.data(), nullptr, proof_out + o, cap - o));
+        memcpy(proof_out + 8 * k, cached[a]->root, 32);
+    }
+    memcpy(proof_out + pre, root, 32);
+    memcpy(proof_out + pre + 8, h.data() + pre + 8, (T.head - pre - 8) * 4);
     if (root_out) memcpy(root_out, root, 32);
     return ZKHIP_OK;
 }
@@ -1022,10 +1077,13 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
 // prep_root: the keyed form, checked against the key's root at l_prep (never reads prep_trace)
 int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs, const uint32_t* const* pvs,
                  unsigned l, const uint32_t* proof, size_t words, bool with_bus, uint32_t* root_out, uint32_t* pq_out,
-                 const uint32_t* prep_root = nullptr, unsigned l_prep = 0) {
+                 const uint32_t* prep_root = nullptr, unsigned l_prep = 0, const unsigned* l_cached = nullptr,
+                 uint32_t* cached_roots_out = nullptr) {
     BatchShape T;
-    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T, prep_root ? (int)l_prep : -1)) return ZKHIP_ERR_INVALID;
+    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T, prep_root ? (int)l_prep : -1, l_cached)) return ZKHIP_ERR_INVALID;
     const Shape& S = T.S;
+    const size_t pre = S.pre;   // the cached form: the partitions' roots, sent before the main root
+    const uint32_t* root = proof + pre;
     for (size_t i = 0; prep_root && i < 8; i++)
         if (prep_root[i] >= P) return ZKHIP_ERR_INVALID;
     for (size_t a = 0; a < n_airs; a++) {
@@ -1041,7 +1099,7 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
     HostChallenger ch;
     ch.observe_canon(prefix, n_prefix);
     if (prep_root) ch.observe_canon(prep_root, 8);
-    ch.observe_canon(proof, 8);
+    ch.observe_canon(proof, pre + 8);   // the cached roots (if any), then the main root
     for (size_t a = 0; a < n_airs; a++) ch.observe_canon(pvs[a], airs[a].n_pvs);
     const Ext one = ext_one();
     const size_t n_blk = S.blocks.size();
@@ -1055,7 +1113,7 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
         std::vector<uint32_t> pt(4 * (size_t)S.L);
         uint32_t cl8[8];
         Ext pq[2];
-        ZK_TRY(gkr_verify_host(ch, proof + 8, S.gkr_words, S.L, pt.data(), cl8, pq));
+        ZK_TRY(gkr_verify_host(ch, root + 8, S.gkr_words, S.L, pt.data(), cl8, pq));
         if (!ext_eq(pq[0], ext_zero()) || ext_eq(pq[1], ext_zero())) return ZKHIP_ERR_VERIFY;
         for (unsigned j = 0; j < S.L; j++) rho[j] = ext_from_canon(pt.data() + 4 * j);
         const Ext pstar = ext_from_canon(cl8), qstar = ext_from_canon(cl8 + 4);
@@ -1067,7 +1125,7 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
             eb[b] = e, pad = ext_sub(pad, e);
         }
         kappa = ch.sample_ext();
-        qB = proof + 8 + S.gkr_words;
+        qB = root + 8 + S.gkr_words;
         Ext lhs = ext_mul(kappa, pad);
         for (size_t i = 0; i < S.n_bus; i++) lhs = ext_add(lhs, ext_from_canon(qB + 4 * i));
         ch.observe_canon(qB, 4 * S.n_bus);
@@ -1197,10 +1255,10 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
         }
     }
     const uint32_t* op = proof + T.head;
-    ZK_TRY(stack_verify_host(ch, prm, proof, S.lh.data(), S.lh.size(), l, points.data(), S.dims.data(), n_airs, S.col_point.data(), op, S.main_words));
-    size_t col = 0;
-    for (size_t a = 0; a < n_airs; col += airs[a].width, a++)
-        if (claimed[a] && memcmp(claimed[a], op + 4 * col, 16 * airs[a].width) != 0) return ZKHIP_ERR_VERIFY;
+    ZK_TRY(stack_verify_host(ch, prm, root, S.lh.data(), S.lh.size(), l, points.data(), S.dims.data(), n_airs, S.col_point.data(), op, S.main_words));
+    size_t col = 0;   // the main opening shows the common columns: all of them where there is no cached partition
+    for (size_t a = 0; a < n_airs; col += airs[a].width - S.cw[a], a++)
+        if (claimed[a] && memcmp(claimed[a] + 4 * S.cw[a], op + 4 * col, 16 * (airs[a].width - S.cw[a])) != 0) return ZKHIP_ERR_VERIFY;
     if (prep_root) {   // the key's opening, against the verifier's own root: an inactive AIR with preprocessed columns is in it too
         std::vector<uint32_t> pts;
         size_t at = 0;
@@ -1208,13 +1266,26 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
             if (S.plans[a].wp) pts.insert(pts.end(), points.begin() + at, points.begin() + at + 4 * (size_t)S.plans[a].m);
         const uint32_t* op2 = op + S.main_words;
         ZK_TRY(stack_verify_host(ch, prm, prep_root, S.lh_p.data(), S.lh_p.size(), l_prep, pts.data(), S.dims_p.data(), S.dims_p.size(),
-                                 S.col_point_p.data(), op2, words - T.head - S.main_words));
+                                 S.col_point_p.data(), op2, S.prep_words));
         col = 0;
         for (size_t a = 0; a < n_airs; col += S.plans[a].wp, a++)
             if (claimed_p[a] && memcmp(claimed_p[a], op2 + 4 * col, 16 * S.plans[a].wp) != 0) return ZKHIP_ERR_VERIFY;
     }
-    if (root_out) memcpy(root_out, proof, 32);
-    if (pq_out && with_bus) memcpy(pq_out, proof + 8, 32);
+    // each cached partition's opening, against the root the proof sent, at its AIR's point: it shows the first cw entries of u (of v
+    // where the AIR does not reduce); an inactive AIR's values stand
+    const uint32_t* op3 = op + S.main_words + S.prep_words;
+    size_t at = 0;
+    for (size_t a = 0, k = 0; a < n_airs; at += 4 * (size_t)S.plans[a].m, a++) {
+        if (!S.cw[a]) continue;
+        const std::vector<unsigned> lhc(S.cw[a], S.plans[a].m), zero(S.cw[a], 0);
+        ZK_TRY(stack_verify_host(ch, prm, proof + 8 * k, lhc.data(), lhc.size(), l_cached[a], points.data() + at, &S.dims[a], 1, zero.data(), op3,
+                                 S.cached_words[k]));
+        if (claimed[a] && memcmp(claimed[a], op3, 16 * S.cw[a]) != 0) return ZKHIP_ERR_VERIFY;
+        op3 += S.cached_words[k++];
+    }
+    if (cached_roots_out) memcpy(cached_roots_out, proof, 4 * pre);
+    if (root_out) memcpy(root_out, root, 32);
+    if (pq_out && with_bus) memcpy(pq_out, root + 8, 32);
     return ZKHIP_OK;
 }
 
@@ -1270,6 +1341,34 @@ int airkey_create(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air*
     if (root_out) memcpy(root_out, key->root, 32);
     guard.key = nullptr;
     *out = key;
+    return ZKHIP_OK;
+}
+
+void cached_main_destroy(zkhip_ctx* ctx, zkhip_cached_main* c) {
+    if (!c) return;
+    stack_destroy(ctx, c->sc);   // synchronises
+    delete c;
+}
+
+// the first cached_width columns of the key's AIR `air` as ONE stacked commitment at l_cached; stack_commit gathers a copy it owns
+int commit_cached(zkhip_ctx* ctx, const zkhip_airkey* key, size_t air, const uint32_t* d_cols, unsigned l_cached, zkhip_cached_main** out,
+                  uint32_t* root_out) {
+    if (air >= key->airs.size()) return set_error(ctx, ZKHIP_ERR_INVALID, "airkey cached: AIR index");
+    ZcPlan pl;
+    if (!zc_plan(key->airs[air], &pl, false, true) || !pl.prog.cached_width)
+        return set_error(ctx, ZKHIP_ERR_INVALID, "airkey cached: the AIR has no CACHED section");
+    zkhip_cached_main* c = new zkhip_cached_main();
+    c->params = key->params, c->air = air, c->m = pl.m, c->cw = (unsigned)pl.prog.cached_width, c->l = l_cached;
+    std::vector<const uint32_t*> cols;
+    for (size_t k = 0; k < c->cw; k++) cols.push_back(d_cols + (k << pl.m));
+    const std::vector<unsigned> lh(c->cw, pl.m);
+    const int rc = stack_commit(ctx, &key->params, cols.data(), lh.data(), cols.size(), l_cached, &c->sc, c->root);   // synchronises
+    if (rc != ZKHIP_OK) {
+        cached_main_destroy(ctx, c);
+        return rc;
+    }
+    if (root_out) memcpy(root_out, c->root, 32);
+    *out = c;
     return ZKHIP_OK;
 }
 }  // namespace
@@ -1359,6 +1458,44 @@ int zkhip_airkey_batch_verify(const zkhip_whir_params* params, const uint32_t* p
     if (!params || (n_prefix && !prefix) || !airs || !prep_root || !pvs || !proof || log_stack_prep > ZKHIP_WHIR_MAX_LOG_N) return ZKHIP_ERR_INVALID;
     return verify_batch(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, root_out, pq_out, prep_root,
                         log_stack_prep);
+}
+
+int zkhip_airkey_commit_cached(zkhip_ctx* ctx, zkhip_airkey* key, size_t air, const uint32_t* d_cols, unsigned log_stack_cached,
+                               zkhip_cached_main** out, uint32_t* root_out) {
+    ZK_BIND_DEVICE(ctx);
+    if (!ctx || !key || !d_cols || !out) return ZKHIP_ERR_INVALID;
+    return commit_cached(ctx, key, air, d_cols, log_stack_cached, out, root_out);
+}
+
+void zkhip_cached_main_destroy(zkhip_ctx* ctx, zkhip_cached_main* cached) {
+    ZK_BIND_DEVICE(ctx);
+    cached_main_destroy(ctx, cached);
+}
+
+size_t zkhip_airkey_cached_proof_words(const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, unsigned log_stack,
+                                       unsigned log_stack_prep, const unsigned* log_stack_cached, int with_bus) {
+    if (!log_stack_cached || log_stack_prep > ZKHIP_WHIR_MAX_LOG_N) return 0;
+    BatchShape T;
+    return batch_shape(params, airs, n_airs, log_stack, with_bus != 0, &T, (int)log_stack_prep, log_stack_cached) ? T.total : 0;
+}
+
+int zkhip_airkey_cached_prove(zkhip_ctx* ctx, zkhip_airkey* key, int with_bus, const uint32_t* const* d_traces, const uint32_t* const* pvs,
+                              zkhip_cached_main* const* cached, unsigned log_stack, zkhip_transcript* transcript, uint32_t* proof_out,
+                              size_t cap, uint32_t* root_out) {
+    ZK_BIND_DEVICE(ctx);
+    if (!ctx || !key || !d_traces || !pvs || !cached || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
+    return prove_batch(ctx, &key->params, key->airs.data(), key->airs.size(), d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out,
+                       cap, root_out, key, cached);
+}
+
+int zkhip_airkey_cached_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
+                               const uint32_t* prep_root, unsigned log_stack_prep, const unsigned* log_stack_cached, const uint32_t* const* pvs,
+                               unsigned log_stack, int with_bus, const uint32_t* proof, size_t words, uint32_t* root_out, uint32_t* pq_out,
+                               uint32_t* cached_roots_out) {
+    if (!params || (n_prefix && !prefix) || !airs || !prep_root || !log_stack_cached || !pvs || !proof || log_stack_prep > ZKHIP_WHIR_MAX_LOG_N)
+        return ZKHIP_ERR_INVALID;
+    return verify_batch(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, root_out, pq_out, prep_root,
+                        log_stack_prep, log_stack_cached, cached_roots_out);
 }
 
 int zkhip_zerocheck_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
