@@ -449,7 +449,7 @@ def fp2_twin(name, family, n=None, log_h=None):
 
 
 def signed_divmod_cases(v, p, L):
-    """which branches of Signed<NW>::signed_divmod (csrc/bigint_signed.hpp) the accumulator v takes, and the quotient's magnitude"""
+    """which branches of Signed<NW>::signed_divmod (csrc/limb_dev.hpp) the accumulator v takes, and the quotient's magnitude"""
     cases = set()
     q = abs(v // p)
     if v < 0 and v % p == 0:

@@ -1,4 +1,4 @@
-"""GPU: the limb-chip trace generators (csrc/modular.hip, ecc.hip, fp2.hip with bigint_signed.hpp, int256.hip, keccak.hip, sha256.hip) on
+"""GPU: the limb-chip trace generators (csrc/modular.hip, ecc.hip, fp2.hip with limb_dev.hpp, int256.hip, keccak.hip, sha256.hip) on
 the boundary operand sets of tests/limb_boundary_inputs.py: every family cell for cell against the twin, count for count against the twin
 and against a numpy recount from the trace's own cells, the result columns against Python's integers; row counts across wave and workgroup
 boundaries with the padding rows zero; the histogram's two extremes; timestamps at 0, P - 1, P, 2^32 - 1; refused records between accepted

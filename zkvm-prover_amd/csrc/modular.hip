@@ -6,15 +6,13 @@
 // (openvm-algebra-circuit, un-vendored).
 #include <string.h>
 
-#include <map>
-#include <mutex>
-#include <vector>
+#include <utility>
 
 #include "../../include/zkhip.h"
 #include "../../include/zkhip_modular.hpp"
 #include "babybear.hpp"
-#include "hist.hpp"
-#include "zkhip_internal.hpp"
+#include "limb_dev.hpp"
+#include "tracegen_common.hpp"
 
 namespace zk {
 namespace {
@@ -23,11 +21,6 @@ namespace md = zkhip::modular;
 struct ModWords {
     uint32_t w[12];
 };
-
-__global__ void k_mod_repr(uint32_t* c, size_t n, int to_m) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) c[i] = to_m ? to_monty(c[i] % P) : from_monty(c[i]);
-}
 
 // NW = words of the modulus: 8 (32 limbs) or 12 (48 limbs: the BLS12-381 base field, crates/circuits/batch-circuit/openvm.toml:18-21)
 template <int NW>
@@ -38,10 +31,8 @@ __global__ __launch_bounds__(256) void k_modmul_trace(const uint32_t* __restrict
     constexpr int L = 4 * NW;
     const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (row >= N) return;
-    if (row >= n) {
-        for (size_t c = 0; c < C.WIDTH; c++) trace[c * N + row] = 0u;
-        return;
-    }
+    const RowWriter w{trace, N, row};
+    if (row >= n) return w.zero(C.WIDTH);
     uint32_t a[NW], b[NW], prod[2 * NW], rem[NW + 1], quo[NW];
     const size_t ro = rec_stride * row + (rec_stride - 2 * NW);
     const uint32_t op_in = rec_stride == 2 * NW + 1 ? recs[rec_stride * row] : 0u;   // 0 mul, 1 add, 2 sub, 3 div (the record then holds the quotient x / y and y)
@@ -79,33 +70,7 @@ __global__ __launch_bounds__(256) void k_modmul_trace(const uint32_t* __restrict
             prod[i + NW] = (uint32_t)c;
         }
     }
-#pragma unroll
-    for (int i = 0; i <= NW; i++) rem[i] = 0;
-#pragma unroll
-    for (int i = 0; i < NW; i++) quo[i] = 0;
-    bool overflow = false;
-    for (int bit = 64 * NW - 1; bit >= 0; bit--) {
-        for (int k = NW; k > 0; k--) rem[k] = (rem[k] << 1) | (rem[k - 1] >> 31);
-        rem[0] = (rem[0] << 1) | ((prod[bit >> 5] >> (bit & 31)) & 1u);
-        bool ge = rem[NW] != 0;
-        if (!ge) {
-            ge = true;
-            for (int k = NW - 1; k >= 0; k--)
-                if (rem[k] != pm.w[k]) {
-                    ge = rem[k] > pm.w[k];
-                    break;
-                }
-        }
-        if (ge) {
-            uint32_t br = 0;
-            for (int k = 0; k <= NW; k++) {
-                const uint64_t d = (uint64_t)rem[k] - (k < NW ? pm.w[k] : 0u) - br;
-                rem[k] = (uint32_t)d, br = (uint32_t)(d >> 32) & 1u;
-            }
-            if (bit >= 32 * NW) overflow = true;
-            else quo[bit >> 5] |= 1u << (bit & 31);
-        }
-    }
+    const bool overflow = divmod_bits<NW, 2 * NW, NW>(prod, pm.w, quo, rem);
     if (overflow) atomicAdd(bad, 1u);   // the quotient does not fit L limbs: operands far above the modulus
     if (op == md::OP_SUB) {             // a - b + q P = r: q is 0 or 1 and the numerator was already reduced
         bool any = false;
@@ -113,80 +78,33 @@ __global__ __launch_bounds__(256) void k_modmul_trace(const uint32_t* __restrict
         if (any) atomicAdd(bad, 1u);    // |a - b| >= P
         quo[0] = sub_wrapped ? 1u : 0u;
     }
-    auto byte_of = [](const uint32_t* w, int i) -> uint32_t { return (w[i >> 2] >> (8 * (i & 3))) & 255u; };
-    auto put = [&](size_t col, uint32_t v) { trace[col * N + row] = to_monty(v); };
-    for (int i = 0; i < L; i++) {
-        put(C.A + i, byte_of(a, i)), put(C.B + i, byte_of(b, i)), put(C.Q + i, byte_of(quo, i)), put(C.R + i, byte_of(rem, i));
-    }
-    for (int i = 0; i < L; i += 2) {
-        hist_add(bitwise_range, byte_of(a, i) * 256 + byte_of(a, i + 1)), hist_add(bitwise_range, byte_of(b, i) * 256 + byte_of(b, i + 1));
-        hist_add(bitwise_range, byte_of(quo, i) * 256 + byte_of(quo, i + 1)), hist_add(bitwise_range, byte_of(rem, i) * 256 + byte_of(rem, i + 1));
-    }
-    // carries of the limb equations: position k of a b - q P - r, plus the carry in, is 256 times the carry out
-    int64_t c = 0;
+    emit_limbs<L>(w, C.A, a, bitwise_range), emit_limbs<L>(w, C.B, b, bitwise_range), emit_limbs<L>(w, C.Q, quo, bitwise_range), emit_limbs<L>(w, C.R, rem, bitwise_range);
+    // carries of the limb equations: position k of a b - q P - r
     const int64_t q_sign = op == md::OP_SUB ? -1 : 1;
-    for (int k = 0; k <= (int)C.N_CARRY; k++) {
-        int64_t s = c;
+    emit_carries(w, (int)C.N_CARRY + 1, (int)C.N_CARRY, md::CARRY_OFFSET, tuple_y, C.CX, C.CY, !overflow, tuple, bad, [&](int k) {
+        int64_t s = 0;
         for (int i = 0; i < L; i++) {
             const int j = k - i;
             if (j < 0 || j >= L) continue;
-            if (op == md::OP_MUL) s += (int64_t)byte_of(a, i) * byte_of(b, j);
-            s -= q_sign * (int64_t)byte_of(quo, i) * byte_of(pm.w, j);
+            if (op == md::OP_MUL) s += (int64_t)limb_byte(a, i) * limb_byte(b, j);
+            s -= q_sign * (int64_t)limb_byte(quo, i) * limb_byte(pm.w, j);
         }
-        if (k < L && op == md::OP_ADD) s += (int64_t)byte_of(a, k) + byte_of(b, k);
-        if (k < L && op == md::OP_SUB) s += (int64_t)byte_of(a, k) - byte_of(b, k);
-        if (k < L) s -= byte_of(rem, k);
-        if ((s & 255) != 0 && !overflow) atomicAdd(bad, 1u);   // (cannot happen: a b = q P + r)
-        c = s >> 8;
-        if (k < (int)C.N_CARRY) {
-            const int64_t shifted = c + md::CARRY_OFFSET;
-            const uint32_t v = shifted < 0 || shifted >= (int64_t)256 * tuple_y ? 0u : (uint32_t)shifted;
-            if ((int64_t)v != shifted) atomicAdd(bad, 1u);
-            put(C.CX + k, v & 255u), put(C.CY + k, v >> 8);
-            hist_add(tuple, (v & 255u) * tuple_y + (v >> 8));
-        } else if (c != 0 && !overflow) {
-            atomicAdd(bad, 1u);
-        }
-    }
-    // r < P: the most significant differing limb
-    int mark = -1;
-    for (int i = L - 1; i >= 0; i--)
-        if (byte_of(rem, i) != byte_of(pm.w, i)) {
-            mark = i;
-            break;
-        }
-    for (int i = 0; i < L; i++) put(C.MARK + i, i == mark ? 1u : 0u);
-    const uint32_t diff = mark >= 0 ? byte_of(pm.w, mark) - byte_of(rem, mark) : 0u;
-    put(C.DIFF, diff), put(C.REAL, 1u), put(C.IS_ADD, op == md::OP_ADD ? 1u : 0u), put(C.IS_SUB, op == md::OP_SUB ? 1u : 0u);   // (set on equality tests too)
-    hist_add(bitwise_range, ((diff - 1u) & 255u) * 256);
-    // a division's quotient (the a columns) is canonical as well
-    int mark2 = -1;
-    if (is_div)
-        for (int i = L - 1; i >= 0; i--)
-            if (byte_of(a, i) != byte_of(pm.w, i)) {
-                mark2 = byte_of(a, i) < byte_of(pm.w, i) ? i : -2;
-                break;
-            }
-    if (is_div && mark2 < 0) atomicAdd(bad, 1u);   // the record's quotient is not below the modulus
-    for (int i = 0; i < L; i++) put(C.MARK2 + i, i == mark2 ? 1u : 0u);
-    const uint32_t diff2 = mark2 >= 0 ? byte_of(pm.w, mark2) - byte_of(a, mark2) : 0u;
-    put(C.IS_DIV, is_div ? 1u : 0u), put(C.DIFF2, diff2);
+        if (k < L && op == md::OP_ADD) s += (int64_t)limb_byte(a, k) + limb_byte(b, k);
+        if (k < L && op == md::OP_SUB) s += (int64_t)limb_byte(a, k) - limb_byte(b, k);
+        if (k < L) s -= limb_byte(rem, k);
+        return s;   // (a multiple of 256 with the carry in: a b = q P + r)
+    });
+    emit_below<L, false>(w, rem, pm.w, true, C.MARK, C.DIFF, bitwise_range, bad);     // r < P
+    emit_below<L, true>(w, a, pm.w, is_div, C.MARK2, C.DIFF2, bitwise_range, bad);    // a division's quotient (the a columns) is canonical as well
+    w.put(C.REAL, 1u), w.put(C.IS_ADD, op == md::OP_ADD ? 1u : 0u), w.put(C.IS_SUB, op == md::OP_SUB ? 1u : 0u), w.put(C.IS_DIV, is_div ? 1u : 0u);   // (IS_SUB is set on equality tests too)
     uint32_t limb_sum = 0;
-    for (int i = 0; i < L; i++) limb_sum += byte_of(rem, i);
+    for (int i = 0; i < L; i++) limb_sum += limb_byte(rem, i);
     const bool eq = is_eq && limb_sum == 0;
-    put(C.IS_EQ, is_eq ? 1u : 0u), put(C.EQ, eq ? 1u : 0u);
+    w.put(C.IS_EQ, is_eq ? 1u : 0u), w.put(C.EQ, eq ? 1u : 0u);
     trace[(size_t)C.INV * N + row] = is_eq && !eq ? minv(to_monty(limb_sum)) : 0u;   // (Montgomery form, as every cell)
-    if (is_div) hist_add(bitwise_range, ((diff2 - 1u) & 255u) * 256);
 }
 
-// the VM chip's timestamp column: row i carries the timestamp of call i
-__global__ __launch_bounds__(256) void k_modmul_ts(const uint32_t* __restrict__ ts, size_t n, size_t N, uint32_t* __restrict__ col) {
-    const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (row < N) col[row] = row < n ? to_monty(ts[row] % P) : 0u;
-}
-
-std::mutex g_mu;
-std::map<std::pair<md::Modulus, std::pair<uint32_t, uint32_t>>, std::vector<uint32_t>> g_programs;   // per (modulus, buses), kept for the life of the process
+AirCache<std::pair<md::Modulus, std::pair<uint32_t, uint32_t>>> g_programs;   // per (modulus, buses)
 
 }  // namespace
 }  // namespace zk
@@ -204,21 +122,7 @@ int zkhip_modmul_air_x(const uint8_t* modulus, uint32_t n_limbs, uint32_t bitwis
     for (uint8_t v : m) zero = zero && v == 0;
     if (zero) return ZKHIP_ERR_INVALID;
     const md::Cols C(n_limbs);
-    try {
-        std::lock_guard<std::mutex> lk(g_mu);
-        const auto key = std::make_pair(m, std::make_pair(bitwise_bus, tuple_bus));
-        auto it = g_programs.find(key);
-        if (it == g_programs.end()) {
-            zkhip::air::AirBuilder b(C.WIDTH, 0);
-            md::modmul_air(b, m, bitwise_bus, tuple_bus);
-            it = g_programs.emplace(key, b.program()).first;
-        }
-        out->program = it->second.data(), out->program_len = it->second.size(), out->log_height = 0, out->width = C.WIDTH, out->n_pvs = 0;
-        out->prep_trace = nullptr, out->prep_commit = nullptr;
-    } catch (const std::exception&) {
-        return ZKHIP_ERR_INVALID;
-    }
-    return ZKHIP_OK;
+    return g_programs.get(std::make_pair(m, std::make_pair(bitwise_bus, tuple_bus)), C.WIDTH, [&](zkhip::air::AirBuilder& b) { md::modmul_air(b, m, bitwise_bus, tuple_bus); }, out);
 }
 int zkhip_modmul_air(const uint8_t modulus[32], uint32_t bitwise_bus, uint32_t tuple_bus, zkhip_air* out) { return zkhip_modmul_air_x(modulus, 32, bitwise_bus, tuple_bus, out); }
 
@@ -259,28 +163,19 @@ static int modular_tracegen(zkhip_ctx* ctx, uint32_t n_words, const uint32_t* mo
                             uint32_t* d_bitwise_trace, uint32_t* d_tuple_counts, uint32_t size_x, uint32_t size_y) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !modulus || !d_trace || !d_bitwise_trace || !d_tuple_counts || log_height > 24 || (n && !d_records) || (n_words != 8 && n_words != 12)) return ZKHIP_ERR_INVALID;
-    const size_t N = (size_t)1 << log_height, T = (size_t)size_x * size_y;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "modmul_tracegen: more records than rows");
-    if (size_x < 256 || size_y < 128 || T > ((size_t)1 << 27)) return set_error(ctx, ZKHIP_ERR_INVALID, "modmul_tracegen: the tuple table must cover (x < 256, y < 128)");
+    const size_t N = (size_t)1 << log_height;
+    ZK_TRY(tracegen_shape(ctx, "modmul_tracegen", n, N, size_x, size_y, 128));
     ModWords pm{};
     memcpy(pm.w, modulus, 4 * n_words);
     const size_t rec_stride = 2 * n_words + (with_op ? 1 : 0);
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "modmul_tracegen");
-    const unsigned tb = (unsigned)((T + 255) / 256), bb = (unsigned)(((size_t)1 << 16) + 255) / 256;
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_mod_repr, dim3(tb), dim3(256), 0, ctx->stream, d_tuple_counts, T, 0);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_mod_repr, dim3(bb), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 0);   // the range column of the 8-bit table
-    if (n_words == 8)
-        hipLaunchKernelGGL(k_modmul_trace<8>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_records, rec_stride, n, N, pm, d_trace, d_bitwise_trace,
-                           d_tuple_counts, size_y, (uint32_t*)flag);
-    else
-        hipLaunchKernelGGL(k_modmul_trace<12>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_records, rec_stride, n, N, pm, d_trace, d_bitwise_trace,
-                           d_tuple_counts, size_y, (uint32_t*)flag);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_mod_repr, dim3(tb), dim3(256), 0, ctx->stream, d_tuple_counts, T, 1);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_mod_repr, dim3(bb), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 1);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return tracegen_finish(ctx, flag, "modular tracegen (a quotient beyond the modulus's limbs, operands of a subtraction further apart than the modulus, or an unknown operation)");
+    const auto kernel = n_words == 8 ? k_modmul_trace<8> : k_modmul_trace<12>;
+    return tracegen_frame(
+        ctx, "modmul_tracegen", {{d_tuple_counts, (size_t)size_x * size_y}, {d_bitwise_trace, BITWISE_WORDS}},   // (the range column of the 8-bit table)
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_records, rec_stride, n, N, pm, d_trace, d_bitwise_trace, d_tuple_counts,
+                               size_y, bad);
+        },
+        "modular tracegen (a quotient beyond the modulus's limbs, operands of a subtraction further apart than the modulus, or an unknown operation)");
 }
 
 int zkhip_modmul_tracegen(zkhip_ctx* ctx, const uint32_t modulus[8], const uint32_t* d_records, size_t n, unsigned log_height, uint32_t* d_trace,
@@ -302,11 +197,7 @@ int zkhip_vm_modmul_tracegen_x(zkhip_ctx* ctx, uint32_t n_words, const uint32_t*
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || (n && !d_ts) || (n_words != 8 && n_words != 12)) return ZKHIP_ERR_INVALID;
     ZK_TRY(zkhip_modular_tracegen_x(ctx, n_words, modulus, d_records, n, log_height, d_trace, d_bitwise_trace, d_tuple_counts, size_x, size_y));   // (op | a | b) records
-    const size_t N = (size_t)1 << log_height;
-    KernelScope ks(ctx, "vm_modmul_timestamps");
-    hipLaunchKernelGGL(k_modmul_ts, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_ts, n, N, d_trace + (size_t)md::Cols(4 * n_words).TS * N);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return ZKHIP_OK;
+    return call_timestamps(ctx, "vm_modmul_timestamps", d_ts, n, log_height, d_trace + ((size_t)md::Cols(4 * n_words).TS << log_height));
 }
 int zkhip_vm_modmul_tracegen(zkhip_ctx* ctx, const uint32_t modulus[8], const uint32_t* d_records, const uint32_t* d_ts, size_t n, unsigned log_height,
                              uint32_t* d_trace, uint32_t* d_bitwise_trace, uint32_t* d_tuple_counts, uint32_t size_x, uint32_t size_y) {

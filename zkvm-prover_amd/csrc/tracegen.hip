@@ -14,7 +14,7 @@
 #include "poseidon2.hpp"
 #include "hist.hpp"
 #include "poseidon2_coop.hpp"
-#include "zkhip_internal.hpp"
+#include "tracegen_common.hpp"
 
 #include <algorithm>
 
@@ -124,9 +124,12 @@ __global__ __launch_bounds__(256) void k_range_counts(const uint32_t* __restrict
 }
 // integer histogram <-> Montgomery counts (counts stay far below p: at most 2^27 rows x a few hundred columns per call,
 // and the sum is reduced mod p, which is what the bus argument needs anyway)
-__global__ void k_counts_repr(uint32_t* c, size_t n, int to_m) {
+__global__ void k_table_repr(uint32_t* c, size_t n, int to_m) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) c[i] = to_m ? to_monty(c[i] % P) : from_monty(c[i]);
+}
+void table_repr(zkhip_ctx* ctx, uint32_t* d, size_t words, bool to_m) {
+    hipLaunchKernelGGL(k_table_repr, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, ctx->stream, d, words, to_m ? 1 : 0);
 }
 
 int range_counts_tracegen(zkhip_ctx* ctx, const uint32_t* d_values, size_t n, unsigned log_table, uint32_t* d_counts, int accumulate) {
@@ -135,14 +138,13 @@ int range_counts_tracegen(zkhip_ctx* ctx, const uint32_t* d_values, size_t n, un
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "range_counts_tracegen");
-    const unsigned tb = (unsigned)((T + 255) / 256);
     if (!accumulate) ZK_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, T * 4, ctx->stream));
-    else if (!ctx->tables_canonical) hipLaunchKernelGGL(k_counts_repr, dim3(tb), dim3(256), 0, ctx->stream, d_counts, T, 0);
+    else tables_repr(ctx, {{d_counts, T}}, false);
     if (n) {
         const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 32 - 1) / (256 * 32), 1024);
         hipLaunchKernelGGL(k_range_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_values, n, log_table, d_counts, (uint32_t*)flag);
     }
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_counts_repr, dim3(tb), dim3(256), 0, ctx->stream, d_counts, T, 1);
+    tables_repr(ctx, {{d_counts, T}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return tracegen_finish(ctx, flag, "range_counts_tracegen (values outside the table)");
 }

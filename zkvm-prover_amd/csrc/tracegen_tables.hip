@@ -24,15 +24,10 @@
 #include "../../include/zkhip.h"
 #include "hist.hpp"
 #include "babybear.hpp"
-#include "zkhip_internal.hpp"
+#include "tracegen_common.hpp"
 
 namespace zk {
 namespace {
-
-__global__ void k_tab_repr(uint32_t* c, size_t n, int to_m) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) c[i] = to_m ? to_monty(c[i] % P) : from_monty(c[i]);
-}
 
 // hist[x * size_y + y] += 1 for every request; x / y Montgomery words of the requesting trace columns
 __global__ __launch_bounds__(256) void k_tuple_counts(const uint32_t* __restrict__ xs, const uint32_t* __restrict__ ys, size_t n,
@@ -127,14 +122,13 @@ extern "C" int zkhip_range_tuple_counts_tracegen(zkhip_ctx* ctx, const uint32_t*
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "range_tuple_tracegen");
-    const unsigned tb = (unsigned)((T + 255) / 256);
     if (!accumulate) ZK_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, T * 4, ctx->stream));
-    else if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_counts, T, 0);
+    else tables_repr(ctx, {{d_counts, T}}, false);
     if (n) {
         const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
         hipLaunchKernelGGL(k_tuple_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_x, d_y, n, size_x, size_y, d_counts, (uint32_t*)flag);
     }
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_counts, T, 1);
+    tables_repr(ctx, {{d_counts, T}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, "range_tuple_counts_tracegen");
 }
@@ -147,14 +141,13 @@ extern "C" int zkhip_bitwise_lookup_tracegen(zkhip_ctx* ctx, const uint32_t* d_x
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "bitwise_lookup_tracegen");
-    const unsigned tb = (unsigned)((T + 255) / 256);
     if (!accumulate) ZK_HIP_CHECK(ctx, hipMemsetAsync(d_trace, 0, T * 4, ctx->stream));
-    else if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_trace, T, 0);
+    else tables_repr(ctx, {{d_trace, T}}, false);
     if (n) {
         const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
         hipLaunchKernelGGL(k_bitwise_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_x, d_y, d_op, n, num_bits, d_trace, (uint32_t*)flag);
     }
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_trace, T, 1);
+    tables_repr(ctx, {{d_trace, T}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, "bitwise_lookup_tracegen");
 }
@@ -252,10 +245,10 @@ extern "C" int zkhip_rv32_alu_tracegen(zkhip_ctx* ctx, const uint32_t* d_opcode,
     KernelScope ks(ctx, "rv32_alu_tracegen");
     // the XOR multiplicity column of the 8-bit bitwise lookup table (column 1 of its 2 x 2^16 trace): Montgomery -> counts -> Montgomery
     uint32_t* xor_col = d_bitwise_trace + (1u << 16);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, xor_col, (size_t)1 << 16, 0);
+    tables_repr(ctx, {{xor_col, (size_t)1 << 16}}, false);
     hipLaunchKernelGGL(k_rv32_alu, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, xor_col,
                        (uint32_t*)flag);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, xor_col, (size_t)1 << 16, 1);
+    tables_repr(ctx, {{xor_col, (size_t)1 << 16}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, "rv32_alu_tracegen (opcode > 4)");
 }
@@ -311,10 +304,9 @@ extern "C" int zkhip_rv32_mul_tracegen(zkhip_ctx* ctx, const uint32_t* d_b, cons
     if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_mul_tracegen: more records than rows");
     if (size_x < 256 || size_y < 1024 || T > ((size_t)1 << 27)) return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_mul_tracegen: the tuple table must cover (limb < 256, carry < 1024)");
     KernelScope ks(ctx, "rv32_mul_tracegen");
-    const unsigned tb = (unsigned)((T + 255) / 256);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_tuple_counts, T, 0);
+    tables_repr(ctx, {{d_tuple_counts, T}}, false);
     hipLaunchKernelGGL(k_rv32_mul, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_b, d_c, n, N, d_trace, d_tuple_counts, size_y);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_tuple_counts, T, 1);
+    tables_repr(ctx, {{d_tuple_counts, T}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return ZKHIP_OK;
 }
@@ -373,7 +365,7 @@ extern "C" int zkhip_program_freq_tracegen(zkhip_ctx* ctx, const uint32_t* d_pc_
     if (n)
         hipLaunchKernelGGL(k_program_freq, dim3((unsigned)std::min<size_t>((n + 256 * 32 - 1) / (256 * 32), 1024)), dim3(256), 0, ctx->stream, d_pc_index, n, N,
                            d_freq, (uint32_t*)flag);
-    hipLaunchKernelGGL(k_tab_repr, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_freq, N, 1);
+    table_repr(ctx, d_freq, N, true);   // (counted from zero: converted in either table mode)
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, "program_freq_tracegen (instruction index beyond the program)");
 }
@@ -458,10 +450,10 @@ extern "C" int zkhip_rv32_lt_tracegen(zkhip_ctx* ctx, const uint32_t* d_opcode, 
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "rv32_lt_tracegen");
     // the RANGE multiplicity column of the 8-bit bitwise lookup table (column 0 of its 2 x 2^16 trace)
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 0);
+    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, false);
     hipLaunchKernelGGL(k_rv32_lt, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, d_bitwise_trace,
                        (uint32_t*)flag);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 1);
+    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, "rv32_lt_tracegen (opcode > 1)");
 }
@@ -585,10 +577,10 @@ extern "C" int zkhip_rv32_shift_tracegen(zkhip_ctx* ctx, const uint32_t* d_opcod
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "rv32_shift_tracegen");
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(512), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)2 << 16, 0);  // both columns
+    tables_repr(ctx, {{d_bitwise_trace, (size_t)2 << 16}}, false);  // both columns
     hipLaunchKernelGGL(k_rv32_shift, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace,
                        d_bitwise_trace, d_bitwise_trace + (1u << 16), (uint32_t*)flag);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(512), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)2 << 16, 1);
+    tables_repr(ctx, {{d_bitwise_trace, (size_t)2 << 16}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, "rv32_shift_tracegen (opcode > 2)");
 }
@@ -710,10 +702,10 @@ extern "C" int zkhip_rv32_branch_lt_tracegen(zkhip_ctx* ctx, const uint32_t* d_o
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "rv32_branch_lt_tracegen");
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 0);
+    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, false);
     hipLaunchKernelGGL(k_rv32_branch_lt, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_a, d_b, d_imm, n, N, d_trace,
                        d_bitwise_trace, (uint32_t*)flag);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 1);
+    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, "rv32_branch_lt_tracegen (opcode > 3 or offset not a field element)");
 }
@@ -832,9 +824,9 @@ int jump_chip_tracegen(zkhip_ctx* ctx, const char* name, size_t n, unsigned log_
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, name);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 0);
+    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, false);
     launch(dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), N, (uint32_t*)flag);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 1);
+    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, name);
 }
@@ -937,13 +929,10 @@ extern "C" int zkhip_rv32_mulh_tracegen(zkhip_ctx* ctx, const uint32_t* d_opcode
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "rv32_mulh_tracegen");
-    const unsigned tb = (unsigned)((T + 255) / 256);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_tuple_counts, T, 0);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 0);
+    tables_repr(ctx, {{d_tuple_counts, T}, {d_bitwise_trace, (size_t)1 << 16}}, false);
     hipLaunchKernelGGL(k_rv32_mulh, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, d_tuple_counts, size_y,
                        d_bitwise_trace, (uint32_t*)flag);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_tuple_counts, T, 1);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 1);
+    tables_repr(ctx, {{d_tuple_counts, T}, {d_bitwise_trace, (size_t)1 << 16}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, "rv32_mulh_tracegen (opcode > 2)");
 }
@@ -1105,13 +1094,10 @@ extern "C" int zkhip_rv32_divrem_tracegen(zkhip_ctx* ctx, const uint32_t* d_opco
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "rv32_divrem_tracegen");
-    const unsigned tb = (unsigned)((T + 255) / 256);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_tuple_counts, T, 0);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 0);
+    tables_repr(ctx, {{d_tuple_counts, T}, {d_bitwise_trace, (size_t)1 << 16}}, false);
     hipLaunchKernelGGL(k_rv32_divrem, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, d_tuple_counts,
                        size_y, d_bitwise_trace, (uint32_t*)flag);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_tuple_counts, T, 1);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(256), dim3(256), 0, ctx->stream, d_bitwise_trace, (size_t)1 << 16, 1);
+    tables_repr(ctx, {{d_tuple_counts, T}, {d_bitwise_trace, (size_t)1 << 16}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, "rv32_divrem_tracegen (opcode > 3)");
 }
@@ -1235,14 +1221,13 @@ extern "C" int zkhip_var_range_counts_tracegen(zkhip_ctx* ctx, const uint32_t* d
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "var_range_counts_tracegen");
-    const unsigned tb = (unsigned)((T + 255) / 256);
     if (!accumulate) ZK_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, T * 4, ctx->stream));
-    else if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_counts, T, 0);
+    else tables_repr(ctx, {{d_counts, T}}, false);
     if (n) {
         const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
         hipLaunchKernelGGL(k_var_range_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_values, d_bits, const_bits, n, max_bits, d_counts, (uint32_t*)flag);
     }
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_counts, T, 1);
+    tables_repr(ctx, {{d_counts, T}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, "var_range_counts_tracegen (bits > max_bits or value >= 2^bits)");
 }
@@ -1287,10 +1272,9 @@ extern "C" int zkhip_castf_tracegen(zkhip_ctx* ctx, const uint32_t* d_x, size_t 
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "castf_tracegen");
-    const unsigned tb = (unsigned)((T + 255) / 256);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_var_range_counts, T, 0);
+    tables_repr(ctx, {{d_var_range_counts, T}}, false);
     hipLaunchKernelGGL(k_castf, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_x, n, N, d_trace, d_var_range_counts, (uint32_t*)flag);
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_tab_repr, dim3(tb), dim3(256), 0, ctx->stream, d_var_range_counts, T, 1);
+    tables_repr(ctx, {{d_var_range_counts, T}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return finish_counts(ctx, flag, "castf_tracegen (value >= 2^30)");
 }

@@ -18,7 +18,7 @@
 #include "../../include/zkhip_vm_circuit.hpp"
 #include "babybear.hpp"
 #include "hist.hpp"
-#include "zkhip_internal.hpp"
+#include "tracegen_common.hpp"
 
 namespace zk {
 int poseidon2_air_tracegen(zkhip_ctx* ctx, const uint32_t* d_inputs, size_t n_perms, unsigned log_height, uint32_t* d_trace);
@@ -119,10 +119,6 @@ __global__ __launch_bounds__(256) void k_rows_to_trace(const uint32_t* __restric
     trace[i] = to_monty(v);
 }
 
-__global__ void k_counts_repr(uint32_t* c, size_t n, int to_m) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) c[i] = to_m ? to_monty(c[i] % P) : from_monty(c[i]);
-}
 __global__ __launch_bounds__(256) void k_range_counts_scaled(const uint32_t* __restrict__ values, size_t n, uint32_t scale, uint32_t T,
                                                              uint32_t* __restrict__ hist, uint32_t* __restrict__ bad) {
     __shared__ uint32_t hk[HOT_SLOTS], hc[HOT_SLOTS];
@@ -476,14 +472,13 @@ int zkhip_range_counts_scaled_tracegen(zkhip_ctx* ctx, const uint32_t* d_values,
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "range_counts_scaled_tracegen");
-    const unsigned tb = (unsigned)((T + 255) / 256);
     if (!accumulate) ZK_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, T * 4, ctx->stream));
-    else if (!ctx->tables_canonical) hipLaunchKernelGGL(k_counts_repr, dim3(tb), dim3(256), 0, ctx->stream, d_counts, T, 0);
+    else tables_repr(ctx, {{d_counts, T}}, false);
     if (n) {
         const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
         hipLaunchKernelGGL(k_range_counts_scaled, dim3(blocks), dim3(256), 0, ctx->stream, d_values, n, scale, (uint32_t)T, d_counts, (uint32_t*)flag);
     }
-    if (!ctx->tables_canonical) hipLaunchKernelGGL(k_counts_repr, dim3(tb), dim3(256), 0, ctx->stream, d_counts, T, 1);
+    tables_repr(ctx, {{d_counts, T}}, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return check_flag(ctx, flag, "range_counts_scaled_tracegen (scaled value outside the table)");
 }
