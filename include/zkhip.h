@@ -310,6 +310,28 @@ int zkhip_duplex_tracegen(zkhip_ctx *ctx, const uint32_t *d_n_observed, const ui
 #define ZKHIP_DOMAIN_POINT_WIDTH 54
 int zkhip_domain_point_tracegen(zkhip_ctx *ctx, const uint32_t *d_k, const uint32_t *d_mult, size_t n, unsigned log_height, uint32_t *d_trace);
 
+/* Reduced-opening chip (a piece of the recursion circuit, air.py reduced_opening_air; docs/reduced_opening.md): the reduced opening
+ * ro = sum_i alpha^i (b_i - a_i) of one query at one height class, a_i the opened base-field cells, b_i the extension values at zeta,
+ * alpha the batching challenge, all in F[X] / (X^4 - 11).
+ *   zkhip_reduced_opening_host     the definition: ro of `len` >= 1 elements (a[i], b[4 i ..], canonical) into out[4].  No device.
+ *                                  ZKHIP_ERR_INVALID for len = 0, a NULL pointer or an operand >= p.
+ *   zkhip_reduced_opening_tracegen the chip's trace for n_calls calls.  Records are canonical words: d_alpha[4 c ..] is alpha of call c and
+ *                                  d_len[c] >= 1 its length; d_a (n_elems words) and d_b (4 n_elems words) hold the elements of all
+ *                                  calls end to end, each call in ascending element order (the generator reverses them: row t of a call
+ *                                  holds element len - 1 - t).  Fills d_trace (ZKHIP_REDUCED_OPENING_WIDTH = 18 columns, stride
+ *                                  2^log_height, Montgomery: alpha[4] | a | b[4] | acc[4] | idx | is_first | is_last | is_real | call
+ *                                  with call = c; rows >= n_elems zero).  d_alpha and d_b are 16-byte aligned (every device allocation
+ *                                  is).  The lengths are scanned on the device and never read back; a workgroup of the generator covers
+ *                                  ZKHIP_REDUCED_OPENING_BLOCK_ROWS consecutive rows at a time.  ZKHIP_ERR_INVALID for a length of 0,
+ *                                  sum of d_len != n_elems, n_elems > 2^log_height, n_calls > n_elems, an operand >= p or a NULL pointer
+ *                                  (the first two and the operands are checked on the device, like every generator's records:
+ *                                  zkhip_tracegen_defer_checks). */
+#define ZKHIP_REDUCED_OPENING_WIDTH 18
+#define ZKHIP_REDUCED_OPENING_BLOCK_ROWS 256
+int zkhip_reduced_opening_host(const uint32_t alpha[4], const uint32_t *a, const uint32_t *b, size_t len, uint32_t out[4]);
+int zkhip_reduced_opening_tracegen(zkhip_ctx *ctx, const uint32_t *d_alpha, const uint32_t *d_len, const uint32_t *d_a, const uint32_t *d_b,
+                                   size_t n_calls, size_t n_elems, unsigned log_height, uint32_t *d_trace);
+
 /* System chips: the PROGRAM chip and the execution frames that look instructions up in it.  OpenVM's ProgramAir keeps the program
  * (ZKHIP_PROGRAM_FIELDS = 9 fields per instruction: pc, opcode, operands a..g) as a CACHED main partition and one common column,
  * the execution frequency of each instruction; it receives every instruction that often on the program bus (the first AIR of the

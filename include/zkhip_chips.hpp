@@ -1219,6 +1219,88 @@ inline void domain_point_air(AirBuilder& b, uint32_t point_bus) {
     b.push_interaction(point_bus, {k, acc[NB - 1]}, mult, Kind::Receive);
 }
 
+// air.reduced_opening_air(result_bus): AirBuilder(18, 0) -- ro = sum_i alpha^i (b_i - a_i) of one query at one height class, one element
+// per row, Horner from the call's last element to its first; with result_bus the is_last row sends (call, idx + 1, alpha[4], acc[4])
+inline void reduced_opening_air(AirBuilder& b, int result_bus = -1) {
+    Expr alpha[4], bv[4], acc[4], n_alpha[4], n_b[4], n_acc[4], step[4];
+    for (int i = 0; i < 4; i++) alpha[i] = b.var(i);
+    const Expr a = b.var(4);
+    for (int i = 0; i < 4; i++) bv[i] = b.var(5 + i);
+    for (int i = 0; i < 4; i++) acc[i] = b.var(9 + i);
+    const Expr idx = b.var(13), first = b.var(14), last = b.var(15), real = b.var(16), call = b.var(17);
+    for (int i = 0; i < 4; i++) n_alpha[i] = b.next(i);
+    const Expr n_a = b.next(4);
+    for (int i = 0; i < 4; i++) n_b[i] = b.next(5 + i);
+    for (int i = 0; i < 4; i++) n_acc[i] = b.next(9 + i);
+    const Expr n_idx = b.next(13), n_first = b.next(14), n_real = b.next(16), n_call = b.next(17);
+    for (const Expr& f : {first, last, real}) {
+        const Expr t = f - 1;
+        b.assert_zero(f * t);
+    }
+    const Expr real_m1 = real - 1;
+    b.assert_zero(first * real_m1);
+    b.assert_zero(last * real_m1);
+    {
+        const Expr d = first - real;
+        b.when_first_row(d);
+    }
+    b.assert_zero(first * idx);
+    const Expr term0 = bv[0] - a;
+    for (int i = 0; i < 4; i++) {
+        const Expr d = acc[i] - (i == 0 ? term0 : bv[i]);
+        b.assert_zero(first * d);
+    }
+    const Expr s = real - last;
+    auto step_to = [&](const Expr& e) {   // when_transition(s * e)
+        const Expr g = s * e;
+        b.when_transition(g);
+    };
+    {
+        const Expr d = n_real - 1;
+        step_to(d);
+    }
+    step_to(n_first);
+    for (int i = 0; i < 4; i++) {
+        const Expr d = n_alpha[i] - alpha[i];
+        step_to(d);
+    }
+    {
+        const Expr d = n_call - call;
+        step_to(d);
+    }
+    {
+        const Expr d = n_idx - idx;
+        const Expr e = d - 1;
+        step_to(e);
+    }
+    ext_mul_exprs(acc, alpha, step);
+    const Expr n_term0 = n_b[0] - n_a;
+    for (int i = 0; i < 4; i++) {
+        const Expr d = n_acc[i] - step[i];
+        const Expr e = d - (i == 0 ? n_term0 : n_b[i]);
+        step_to(e);
+    }
+    {
+        const Expr d = n_real - n_first;
+        const Expr g = last * d;
+        b.when_transition(g);
+    }
+    {
+        const Expr d = 1 - real;
+        const Expr g = d * n_real;
+        b.when_transition(g);
+    }
+    b.when_last_row(s);
+    if (result_bus >= 0) {
+        std::vector<Expr> msg;
+        msg.push_back(call);
+        msg.push_back(idx + 1);
+        for (int i = 0; i < 4; i++) msg.push_back(alpha[i]);
+        for (int i = 0; i < 4; i++) msg.push_back(acc[i]);
+        b.push_interaction((uint32_t)result_bus, msg, last, Kind::Send);
+    }
+}
+
 // air.mmcs_claims_air(claims_bus): AirBuilder(19, 0)
 inline void mmcs_claims_air(AirBuilder& b, uint32_t claims_bus) {
     std::vector<Expr> msg;

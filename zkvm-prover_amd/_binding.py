@@ -146,6 +146,7 @@ def load_library():
         "zkhip_domain_point_tracegen": (C.c_int, [vp, vp, vp, sz, C.c_uint, vp]),
         "zkhip_duplex_tracegen": (C.c_int, [vp, vp, vp, vp, sz, C.c_uint, vp, vp]),
         "zkhip_fri_fold_chip_tracegen": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, C.c_uint, vp]),
+        "zkhip_reduced_opening_tracegen": (C.c_int, [vp, vp, vp, vp, vp, sz, sz, C.c_uint, vp]),
         "zkhip_castf_tracegen": (C.c_int, [vp, vp, sz, C.c_uint, vp, vp, C.c_uint]),
         "zkhip_field_arith_tracegen": (C.c_int, [vp, vp, vp, vp, sz, C.c_uint, vp]),
         "zkhip_field_ext_tracegen": (C.c_int, [vp, vp, vp, vp, sz, C.c_uint, vp]),
@@ -193,6 +194,7 @@ def load_library():
         "zkhip_poseidon2_permute_host_avx512": (C.c_int, [u32p]),
         "zkhip_mmcs_verify": (C.c_int, [u32p, C.POINTER(C.c_uint), C.POINTER(sz), sz, C.c_uint64, u32p]),
         "zkhip_fri_fold_row": (C.c_int, [C.c_uint64, C.c_uint, u32p, u32p, u32p, u32p]),
+        "zkhip_reduced_opening_host": (C.c_int, [u32p, u32p, u32p, sz, u32p]),
         "zkhip_logup_exposed_check": (C.c_int, [u32p, sz]),
         "zkhip_proof_decode_v1": (C.c_int, [C.POINTER(C.c_uint8), sz, C.c_int, C.POINTER(_V1Summary)]),
         "zkhip_proof_reencode_v1": (C.c_int, [C.POINTER(C.c_uint8), sz, C.c_int, C.POINTER(C.c_uint8), sz, C.POINTER(sz)]),
@@ -650,6 +652,18 @@ class Context:
         out = torch.empty(19 << log_height, dtype=torch.int32, device=self.device)
         self._check(self.lib.zkhip_fri_fold_chip_tracegen(self.h, *[C.c_void_p(t.data_ptr()) for t in (t_e0, t_e1, t_beta, t_k, t_log_n_out)], t_k.numel(),
                                                           log_height, C.c_void_p(out.data_ptr())))
+        return out
+
+    def reduced_opening_tracegen(self, t_alpha, t_len, t_a, t_b, log_height):
+        """18-column trace of the reduced-opening chip from records (int32 tensors, canonical: alpha [n_calls][4]; the calls' lengths; a
+        [n_elems] and b [n_elems][4], the elements of all calls end to end in ascending order).  t_alpha and t_b must start on a 16-byte
+        boundary (a whole tensor does; a slice that starts at an odd element may not: make it .contiguous().clone() first) -- the call
+        is refused with ZKHIP_ERR_INVALID otherwise."""
+        import torch
+
+        out = torch.empty(REDUCED_OPENING_WIDTH << log_height, dtype=torch.int32, device=self.device)
+        self._check(self.lib.zkhip_reduced_opening_tracegen(self.h, *[C.c_void_p(t.data_ptr()) for t in (t_alpha, t_len, t_a, t_b)], t_len.numel(),
+                                                            t_a.numel(), log_height, C.c_void_p(out.data_ptr())))
         return out
 
     def castf_tracegen(self, t_x, log_height, t_var_range_counts, max_bits):
@@ -2174,6 +2188,22 @@ def fri_fold_row(index, log_height, beta, e0, e1):
     rc = load_library().zkhip_fri_fold_row(int(index), log_height, _u32p(b), _u32p(a0), _u32p(a1), _u32p(out))
     if rc != 0:
         raise ZkhipError("zkhip_fri_fold_row returned %d" % rc)
+    return out
+
+
+REDUCED_OPENING_WIDTH = 18          # ZKHIP_REDUCED_OPENING_WIDTH
+REDUCED_OPENING_BLOCK_ROWS = 256    # ZKHIP_REDUCED_OPENING_BLOCK_ROWS: consecutive rows per workgroup pass of the generator
+
+
+def reduced_opening_host(alpha, a, b):
+    """ro = sum_i alpha^i (b_i - a_i) on canonical words (alpha [4], a [len], b [len][4]); returns 4 canonical words."""
+    al, av, bv = (np.ascontiguousarray(v, dtype=np.uint32).reshape(-1) for v in (alpha, a, b))
+    if al.size != 4 or bv.size != 4 * av.size:
+        raise ZkhipError("reduced_opening_host: alpha has 4 words and b four per element of a")
+    out = np.zeros(4, dtype=np.uint32)
+    rc = load_library().zkhip_reduced_opening_host(_u32p(al), _u32p(av), _u32p(bv), av.size, _u32p(out))
+    if rc != 0:
+        raise ZkhipError("zkhip_reduced_opening_host returned %d" % rc)
     return out
 
 

@@ -1721,6 +1721,59 @@ def domain_point_air(point_bus):
     return b
 
 
+REDUCED_OPENING_WIDTH = 18
+
+
+def reduced_opening_air(result_bus=None):
+    """The reduced opening of one query at one height class, in-circuit -- the piece of the recursion circuit between the opened rows
+    and the fold loop: ro = sum_i alpha^i (b_i - a_i) with a_i the opened base-field cells p_i(x), b_i the extension values p_i(zeta)
+    and alpha the batching challenge.  Columns alpha[4] | a | b[4] | acc[4] | idx | is_first | is_last | is_real | call.  A call of
+    L >= 1 elements takes L consecutive rows and is walked by Horner from its last element to its first: row t holds element L - 1 - t
+    and idx = t; acc = b - a on the first row (a is a base cell: it leaves coordinate 0 only), acc = acc_prev * alpha + (b - a) in
+    F[X] / (X^4 - 11) on every later one, and the acc of the is_last row is ro.  With s = is_real - is_last a transition row with s = 1
+    hands alpha, call and idx + 1 to a next row that is real and not first; an is_last row is followed by an is_first row or by
+    padding, padding only by padding, and the last trace row has s = 0: no call wraps round.  With `result_bus` the is_last row sends
+    (call, idx + 1, alpha[4], acc[4]).  docs/reduced_opening.md has the argument why a satisfying trace fixes ro.
+
+    DEVIATION FROM OPENVM: its native extension has a chip for exactly this (the FRI reduced-opening chip of openvm-native-circuit).
+    That crate is not vendored, so the shape -- one element per row, a running Horner accumulator, first / last markers -- follows it
+    from recollection; there are no memory-bus reads here (no native address space: include/zkhip_native.hpp) and the operands are
+    cells of the row, not pointers."""
+    b = AirBuilder(REDUCED_OPENING_WIDTH, 0)
+    alpha, a, bv = [b.var(i) for i in range(4)], b.var(4), [b.var(5 + i) for i in range(4)]
+    acc = [b.var(9 + i) for i in range(4)]
+    idx, first, last, real, call = b.var(13), b.var(14), b.var(15), b.var(16), b.var(17)
+    n_alpha, n_a, n_b = [b.next(i) for i in range(4)], b.next(4), [b.next(5 + i) for i in range(4)]
+    n_acc = [b.next(9 + i) for i in range(4)]
+    n_idx, n_first, n_real, n_call = b.next(13), b.next(14), b.next(16), b.next(17)
+    for f in (first, last, real):
+        b.assert_zero(f * (f - 1))
+    b.assert_zero(first * (real - 1))
+    b.assert_zero(last * (real - 1))
+    b.when_first_row(first - real)
+    b.assert_zero(first * idx)
+    term = [bv[0] - a, bv[1], bv[2], bv[3]]
+    for i in range(4):
+        b.assert_zero(first * (acc[i] - term[i]))
+    s = real - last
+    b.when_transition(s * (n_real - 1))
+    b.when_transition(s * n_first)
+    for i in range(4):
+        b.when_transition(s * (n_alpha[i] - alpha[i]))
+    b.when_transition(s * (n_call - call))
+    b.when_transition(s * (n_idx - idx - 1))
+    step = _ext_mul_exprs(acc, alpha)
+    n_term = [n_b[0] - n_a, n_b[1], n_b[2], n_b[3]]
+    for i in range(4):
+        b.when_transition(s * (n_acc[i] - step[i] - n_term[i]))
+    b.when_transition(last * (n_real - n_first))
+    b.when_transition((1 - real) * n_real)
+    b.when_last_row(s)
+    if result_bus is not None:
+        b.push_interaction(result_bus, [call, idx + 1] + alpha + acc, last, "send")
+    return b
+
+
 def hasher_user_air(bus):
     """A chip that needs 2-to-1 compressions (a Merkle-path checker, say): columns left[8] | right[8] | out[8] | is_real;
     it sends (left, right, out) on `bus` when is_real = 1 and relies on the Poseidon2 chip to receive it, i.e. to
