@@ -332,6 +332,24 @@ int zkhip_reduced_opening_host(const uint32_t alpha[4], const uint32_t *a, const
 int zkhip_reduced_opening_tracegen(zkhip_ctx *ctx, const uint32_t *d_alpha, const uint32_t *d_len, const uint32_t *d_a, const uint32_t *d_b,
                                    size_t n_calls, size_t n_elems, unsigned log_height, uint32_t *d_trace);
 
+/* Row-digest chip (a piece of the recursion circuit, air.py mmcs_rows_air; docs/mmcs_rows.md): the sponge between the opened words of one
+ * query for the matrices of one height under one commitment and the row digest zkhip_mmcs_path_tracegen's chip claims for them
+ * (zkhip_hash_slice_host is the definition).  With the path chip and the two Poseidon2 chips it states `Mmcs::verify_batch` from the
+ * opened words to the root.  Records are canonical words: per call c its length d_len[c] >= 1, d_root[8 c ..], d_lvl[c], d_idx[c] and
+ * d_mult[c] (how often the path chip claims this digest); d_values (n_words words) holds the words of all calls end to end.  A call of L
+ * words takes ceil(L / 8) consecutive rows.  Fills d_trace (ZKHIP_MMCS_ROWS_WIDTH = 56 columns, stride 2^log_height, Montgomery:
+ * st_in[16] | st_out[16] | f[8] | is_first | is_last | is_real | root[8] | lvl | idx | mult | call | blk with call = c; rows behind the
+ * last call zero), d_hash_inputs ([2^log_height][16] Montgomery: st_in of every row, the input of zkhip_poseidon2_air_tracegen for the
+ * Poseidon2 chip with 16 output lanes that serves the chip's hash bus) and, unless it is NULL, d_digest ([n_calls][8] CANONICAL: what
+ * zkhip_mmcs_path_tracegen takes as leaf and injected digests).  The lengths are scanned on the device and never read back.
+ * ZKHIP_ERR_INVALID for a length of 0, sum of d_len != n_words, more rows than 2^log_height, a word or record field >= p (checked on
+ * the device like every generator's records: zkhip_tracegen_defer_checks; n_words > 8 * 2^log_height and n_calls > n_words at once), a
+ * NULL pointer or log_height > 27. */
+#define ZKHIP_MMCS_ROWS_WIDTH 56
+int zkhip_mmcs_rows_tracegen(zkhip_ctx *ctx, const uint32_t *d_len, const uint32_t *d_root, const uint32_t *d_lvl, const uint32_t *d_idx,
+                             const uint32_t *d_mult, const uint32_t *d_values, size_t n_calls, size_t n_words, unsigned log_height,
+                             uint32_t *d_trace, uint32_t *d_hash_inputs, uint32_t *d_digest);
+
 /* System chips: the PROGRAM chip and the execution frames that look instructions up in it.  OpenVM's ProgramAir keeps the program
  * (ZKHIP_PROGRAM_FIELDS = 9 fields per instruction: pc, opcode, operands a..g) as a CACHED main partition and one common column,
  * the execution frequency of each instruction; it receives every instruction that often on the program bus (the first AIR of the
@@ -521,7 +539,10 @@ int zkhip_verify_where(const zkhip_params *params, const zkhip_air *airs, size_t
  * zkhip_mmcs_verify: `opening` = the opened rows in matrix order (widths[m] words each) followed by max(log_heights)
  * sibling digests bottom-up; matrix m's row index is index >> (max - log_heights[m]).  ZKHIP_OK / ZKHIP_ERR_VERIFY.
  * zkhip_fri_fold_row: pair `index` of a layer that folds 2^(log_height+1) values (bit-reversed order) to 2^log_height:
- * out = e0 + (beta - x)(e1 - e0)/(-2x), x = two_adic_generator(log_height+1)^bitrev(index, log_height). */
+ * out = e0 + (beta - x)(e1 - e0)/(-2x), x = two_adic_generator(log_height+1)^bitrev(index, log_height).
+ * zkhip_hash_slice_host: the sponge zkhip_mmcs_verify hashes opened rows with (p3 `PaddingFreeSponge<_, 16, 8, 8>`: the state starts at
+ * zero, words overwrite the rate lanes 0..7 eight at a time -- a partial last block its first lanes only -- with a permutation after
+ * each block, the digest is lanes 0..7 of the last output; all zero for len = 0).  ZKHIP_ERR_INVALID for a word >= p. */
 int zkhip_poseidon2_permute_host(uint32_t state[16]);
 /* the same permutation through the host's AVX-512 form (zkvm-prover_amd/csrc/poseidon2_avx512.cpp: what the prover's transcript uses for
  * long absorptions); returns 1 -- state untouched -- on a CPU without AVX-512 */
@@ -531,6 +552,7 @@ int zkhip_poseidon2_permute_host_avx512(uint32_t state[16]);
 int zkhip_poseidon2_permute16_host(uint32_t states[256]);
 int zkhip_mmcs_verify(const uint32_t root[8], const unsigned *log_heights, const size_t *widths, size_t n_mats,
                       uint64_t index, const uint32_t *opening);
+int zkhip_hash_slice_host(const uint32_t *in, size_t len, uint32_t out[8]);
 int zkhip_fri_fold_row(uint64_t index, unsigned log_height, const uint32_t beta[4], const uint32_t e0[4],
                        const uint32_t e1[4], uint32_t out[4]);
 /* the LogUp bus check: n exposed cumulative sums (4 canonical words each, one per AIR with interactions) must add up to zero in

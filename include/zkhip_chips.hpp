@@ -1301,6 +1301,131 @@ inline void reduced_opening_air(AirBuilder& b, int result_bus = -1) {
     }
 }
 
+// air.mmcs_rows_air(hash_bus, claims_bus, values_bus): AirBuilder(56, 0) -- the sponge between the opened words of one query at one height
+// class and the row digest mmcs_path_air claims for them, one permutation per row; the is_last row RECEIVES (root, lvl, idx, st_out[0..8])
+// `mult` times; with values_bus every overwritten lane sends (call, 8 blk + j, st_in[j])
+inline void mmcs_rows_air(AirBuilder& b, uint32_t hash_bus, uint32_t claims_bus, int values_bus = -1) {
+    Expr st_in[16], st_out[16], f[8], root[8], n_in[16], n_f[8], n_root[8];
+    for (int i = 0; i < 16; i++) st_in[i] = b.var(i);
+    for (int i = 0; i < 16; i++) st_out[i] = b.var(16 + i);
+    for (int j = 0; j < 8; j++) f[j] = b.var(32 + j);
+    const Expr first = b.var(40), last = b.var(41), real = b.var(42);
+    for (int i = 0; i < 8; i++) root[i] = b.var(43 + i);
+    const Expr lvl = b.var(51), idx = b.var(52), mult = b.var(53), call = b.var(54), blk = b.var(55);
+    for (int i = 0; i < 16; i++) n_in[i] = b.next(i);
+    for (int j = 0; j < 8; j++) n_f[j] = b.next(32 + j);
+    const Expr n_first = b.next(40), n_real = b.next(42);
+    for (int i = 0; i < 8; i++) n_root[i] = b.next(43 + i);
+    const Expr n_lvl = b.next(51), n_idx = b.next(52), n_call = b.next(54), n_blk = b.next(55);
+    auto boolean = [&](const Expr& x) {
+        const Expr t = x - 1;
+        b.assert_zero(x * t);
+    };
+    for (int j = 0; j < 8; j++) boolean(f[j]);
+    boolean(first);
+    boolean(last);
+    boolean(real);
+    b.assert_zero(f[0] - real);
+    for (int j = 0; j < 7; j++) {
+        const Expr t = 1 - f[j];
+        b.assert_zero(f[j + 1] * t);
+    }
+    const Expr pad = 1 - real;
+    b.assert_zero(first * pad);
+    b.assert_zero(last * pad);
+    {
+        const Expr t = 1 - last;
+        b.assert_zero(mult * t);
+    }
+    {
+        const Expr d = first - real;
+        b.when_first_row(d);
+    }
+    const Expr s = real - last;
+    b.when_last_row(s);
+    auto step_to = [&](const Expr& e) {   // when_transition(s * e)
+        const Expr g = s * e;
+        b.when_transition(g);
+    };
+    {
+        const Expr d = n_real - 1;
+        step_to(d);
+    }
+    step_to(n_first);
+    {
+        const Expr d = n_real - n_first;
+        const Expr g = last * d;
+        b.when_transition(g);
+    }
+    {
+        const Expr g = pad * n_real;
+        b.when_transition(g);
+    }
+    {
+        const Expr t = 1 - f[7];
+        b.assert_zero(s * t);
+    }
+    for (int i = 0; i < 8; i++) b.assert_zero(first * st_in[8 + i]);
+    for (int j = 0; j < 8; j++) {
+        const Expr t = 1 - f[j];
+        const Expr u = t * st_in[j];
+        b.assert_zero(first * u);
+    }
+    b.assert_zero(first * blk);
+    for (int i = 0; i < 8; i++) {
+        const Expr d = n_in[8 + i] - st_out[8 + i];
+        step_to(d);
+    }
+    for (int j = 0; j < 8; j++) {
+        const Expr t = 1 - n_f[j];
+        const Expr d = n_in[j] - st_out[j];
+        const Expr u = t * d;
+        step_to(u);
+    }
+    for (int i = 0; i < 8; i++) {
+        const Expr d = n_root[i] - root[i];
+        step_to(d);
+    }
+    {
+        const Expr d = n_lvl - lvl;
+        step_to(d);
+    }
+    {
+        const Expr d = n_idx - idx;
+        step_to(d);
+    }
+    {
+        const Expr d = n_call - call;
+        step_to(d);
+    }
+    {
+        const Expr d = n_blk - blk;
+        const Expr e = d - 1;
+        step_to(e);
+    }
+    {
+        std::vector<Expr> msg;
+        for (int i = 0; i < 16; i++) msg.push_back(st_in[i]);
+        for (int i = 0; i < 16; i++) msg.push_back(st_out[i]);
+        b.push_interaction(hash_bus, msg, real, Kind::Send);
+    }
+    {
+        std::vector<Expr> msg;
+        for (int i = 0; i < 8; i++) msg.push_back(root[i]);
+        msg.push_back(lvl);
+        msg.push_back(idx);
+        for (int i = 0; i < 8; i++) msg.push_back(st_out[i]);
+        b.push_interaction(claims_bus, msg, mult, Kind::Receive);
+    }
+    if (values_bus >= 0) {
+        for (int j = 0; j < 8; j++) {
+            const Expr b8 = blk * 8;
+            const Expr pos = b8 + (int64_t)j;
+            b.push_interaction((uint32_t)values_bus, {call, pos, st_in[j]}, f[j], Kind::Send);
+        }
+    }
+}
+
 // air.mmcs_claims_air(claims_bus): AirBuilder(19, 0)
 inline void mmcs_claims_air(AirBuilder& b, uint32_t claims_bus) {
     std::vector<Expr> msg;

@@ -9,9 +9,11 @@
 //
 // DEVIATION FROM OPENVM (stated, not hidden: ADVICE round 5).  openvm-native-circuit is not vendored, so this is recollection: besides the three
 // chips above, OpenVM's native extension is believed to bring a NATIVE ADDRESS SPACE with its own load / store, branch, jal and range-check
-// chips, and the FRI reduced-opening and Poseidon2 verify-batch chips its in-VM STARK verifier runs on.  Of those only the reduced-opening
+// chips, and the FRI reduced-opening and Poseidon2 verify-batch chips its in-VM STARK verifier runs on.  Of those the reduced-opening
 // chip is built, as a stand-alone core on cells instead of native memory (air.py reduced_opening_air, zkhip_reduced_opening_tracegen,
-// docs/reduced_opening.md); the native address space, its instruction set and the verify-batch chip are not.  The
+// docs/reduced_opening.md), and so is the verify-batch chip, as stand-alone cores that are wired into no circuit yet (air.py
+// mmcs_rows_air + mmcs_path_air + the two Poseidon2 chips: opened words -> row digests -> path -> root; zkhip_mmcs_rows_tracegen,
+// docs/mmcs_rows.md); the native address space and its instruction set are not.  The
 // three arithmetic chips sit behind CUSTOM ecalls (9 / 10 / 11) on the RV32 memory, not behind OpenVM's native opcodes: a guest that uses
 // openvm `verify_stark` (a native-address-space recursion program) cannot run on this executor.  `[app_vm_config.native]` is therefore
 // COVERED IN PART: its field arithmetic, not its instruction set (docs/gaps.md).

@@ -147,6 +147,7 @@ def load_library():
         "zkhip_duplex_tracegen": (C.c_int, [vp, vp, vp, vp, sz, C.c_uint, vp, vp]),
         "zkhip_fri_fold_chip_tracegen": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, C.c_uint, vp]),
         "zkhip_reduced_opening_tracegen": (C.c_int, [vp, vp, vp, vp, vp, sz, sz, C.c_uint, vp]),
+        "zkhip_mmcs_rows_tracegen": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, sz, C.c_uint, vp, vp, vp]),
         "zkhip_castf_tracegen": (C.c_int, [vp, vp, sz, C.c_uint, vp, vp, C.c_uint]),
         "zkhip_field_arith_tracegen": (C.c_int, [vp, vp, vp, vp, sz, C.c_uint, vp]),
         "zkhip_field_ext_tracegen": (C.c_int, [vp, vp, vp, vp, sz, C.c_uint, vp]),
@@ -195,6 +196,7 @@ def load_library():
         "zkhip_mmcs_verify": (C.c_int, [u32p, C.POINTER(C.c_uint), C.POINTER(sz), sz, C.c_uint64, u32p]),
         "zkhip_fri_fold_row": (C.c_int, [C.c_uint64, C.c_uint, u32p, u32p, u32p, u32p]),
         "zkhip_reduced_opening_host": (C.c_int, [u32p, u32p, u32p, sz, u32p]),
+        "zkhip_hash_slice_host": (C.c_int, [u32p, sz, u32p]),
         "zkhip_logup_exposed_check": (C.c_int, [u32p, sz]),
         "zkhip_proof_decode_v1": (C.c_int, [C.POINTER(C.c_uint8), sz, C.c_int, C.POINTER(_V1Summary)]),
         "zkhip_proof_reencode_v1": (C.c_int, [C.POINTER(C.c_uint8), sz, C.c_int, C.POINTER(C.c_uint8), sz, C.POINTER(sz)]),
@@ -665,6 +667,20 @@ class Context:
         self._check(self.lib.zkhip_reduced_opening_tracegen(self.h, *[C.c_void_p(t.data_ptr()) for t in (t_alpha, t_len, t_a, t_b)], t_len.numel(),
                                                             t_a.numel(), log_height, C.c_void_p(out.data_ptr())))
         return out
+
+    def mmcs_rows_tracegen(self, t_len, t_root, t_lvl, t_idx, t_mult, t_values, log_height, digests=True):
+        """(56-column trace of the row-digest chip, [2^log_height][16] permutation inputs for the Poseidon2 chip with 16 output lanes,
+        the calls' digests [n_calls][8] CANONICAL or None) from records (int32 tensors, canonical: per call its length, root [n_calls][8],
+        lvl, idx and mult; the words of all calls end to end).  digests=False passes d_digest = NULL."""
+        import torch
+
+        tr = torch.empty(MMCS_ROWS_WIDTH << log_height, dtype=torch.int32, device=self.device)
+        hin = torch.empty(16 << log_height, dtype=torch.int32, device=self.device)
+        dg = torch.zeros(8 * t_len.numel(), dtype=torch.int32, device=self.device) if digests else None
+        self._check(self.lib.zkhip_mmcs_rows_tracegen(self.h, *[C.c_void_p(t.data_ptr()) for t in (t_len, t_root, t_lvl, t_idx, t_mult, t_values)],
+                                                      t_len.numel(), t_values.numel(), log_height, C.c_void_p(tr.data_ptr()), C.c_void_p(hin.data_ptr()),
+                                                      C.c_void_p(dg.data_ptr()) if digests else None))
+        return tr, hin, dg
 
     def castf_tracegen(self, t_x, log_height, t_var_range_counts, max_bits):
         """6-column trace of the native CASTF chip from records (int32 tensor of values < 2^30); the limb checks are added to
@@ -2204,6 +2220,19 @@ def reduced_opening_host(alpha, a, b):
     rc = load_library().zkhip_reduced_opening_host(_u32p(al), _u32p(av), _u32p(bv), av.size, _u32p(out))
     if rc != 0:
         raise ZkhipError("zkhip_reduced_opening_host returned %d" % rc)
+    return out
+
+
+MMCS_ROWS_WIDTH = 56                # ZKHIP_MMCS_ROWS_WIDTH
+
+
+def hash_slice_host(words):
+    """p3 `PaddingFreeSponge<_, 16, 8, 8>` of canonical words (the row hash of zkhip_mmcs_verify); returns 8 canonical words."""
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+    out = np.zeros(8, dtype=np.uint32)
+    rc = load_library().zkhip_hash_slice_host(_u32p(w), w.size, _u32p(out))
+    if rc != 0:
+        raise ZkhipError("zkhip_hash_slice_host returned %d" % rc)
     return out
 
 

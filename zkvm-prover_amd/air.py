@@ -1774,6 +1774,71 @@ def reduced_opening_air(result_bus=None):
     return b
 
 
+MMCS_ROWS_WIDTH = 56
+
+
+def mmcs_rows_air(hash_bus, claims_bus, values_bus=None):
+    """The sponge between the opened words and the row digests mmcs_path_air claims, in-circuit (p3 `PaddingFreeSponge<_, 16, 8, 8>`,
+    zkhip_hash_slice_host) -- with the path chip and the two Poseidon2 chips, `Mmcs::verify_batch` from the opened words to the root.
+    Columns st_in[16] | st_out[16] | f[8] | is_first | is_last | is_real | root[8] | lvl | idx | mult | call | blk.  A call is all opened
+    words of one query for the matrices of one height under one commitment, in matrix order: L >= 1 words on ceil(L / 8) consecutive
+    rows, one permutation a row.  f is the prefix of rate lanes this row's words overwrote (all eight except on a call's last row); the
+    other lanes carry the previous row's st_out (zero on the first row); st_out = Poseidon2(st_in) is requested on `hash_bus` (the
+    32-field message of poseidon2_air(bus, out_lanes=16)).  The is_last row RECEIVES (root, lvl, idx, st_out[0..8]) on `claims_bus`,
+    `mult` times -- field by field the message mmcs_path_air sends; mult is a count, since queries whose indices share high bits claim
+    the same row of a short matrix.  With `values_bus` every overwritten lane sends (call, 8 blk + j, st_in[j]): where the words come
+    from is bound there.  The flags follow reduced_opening_air's skeleton (s = is_real - is_last).  docs/mmcs_rows.md has the argument
+    why a satisfying trace fixes the digest."""
+    b = AirBuilder(MMCS_ROWS_WIDTH, 0)
+    st_in, st_out = [b.var(i) for i in range(16)], [b.var(16 + i) for i in range(16)]
+    f = [b.var(32 + j) for j in range(8)]
+    first, last, real = b.var(40), b.var(41), b.var(42)
+    root = [b.var(43 + i) for i in range(8)]
+    lvl, idx, mult, call, blk = (b.var(51 + i) for i in range(5))
+    n_in, n_f = [b.next(i) for i in range(16)], [b.next(32 + j) for j in range(8)]
+    n_first, n_real = b.next(40), b.next(42)
+    n_root = [b.next(43 + i) for i in range(8)]
+    n_lvl, n_idx, n_call, n_blk = b.next(51), b.next(52), b.next(54), b.next(55)
+    for x in f + [first, last, real]:
+        b.assert_zero(x * (x - 1))
+    b.assert_zero(f[0] - real)
+    for j in range(7):
+        b.assert_zero(f[j + 1] * (1 - f[j]))
+    pad = 1 - real
+    b.assert_zero(first * pad)
+    b.assert_zero(last * pad)
+    b.assert_zero(mult * (1 - last))
+    b.when_first_row(first - real)
+    s = real - last
+    b.when_last_row(s)
+    b.when_transition(s * (n_real - 1))
+    b.when_transition(s * n_first)
+    b.when_transition(last * (n_real - n_first))
+    b.when_transition(pad * n_real)
+    b.assert_zero(s * (1 - f[7]))
+    for i in range(8):
+        b.assert_zero(first * st_in[8 + i])
+    for j in range(8):
+        b.assert_zero(first * ((1 - f[j]) * st_in[j]))
+    b.assert_zero(first * blk)
+    for i in range(8):
+        b.when_transition(s * (n_in[8 + i] - st_out[8 + i]))
+    for j in range(8):
+        b.when_transition(s * ((1 - n_f[j]) * (n_in[j] - st_out[j])))
+    for i in range(8):
+        b.when_transition(s * (n_root[i] - root[i]))
+    b.when_transition(s * (n_lvl - lvl))
+    b.when_transition(s * (n_idx - idx))
+    b.when_transition(s * (n_call - call))
+    b.when_transition(s * (n_blk - blk - 1))
+    b.push_interaction(hash_bus, st_in + st_out, real, "send")
+    b.push_interaction(claims_bus, root + [lvl, idx] + st_out[:8], mult, "receive")
+    if values_bus is not None:
+        for j in range(8):
+            b.push_interaction(values_bus, [call, blk * 8 + j, st_in[j]], f[j], "send")
+    return b
+
+
 def hasher_user_air(bus):
     """A chip that needs 2-to-1 compressions (a Merkle-path checker, say): columns left[8] | right[8] | out[8] | is_real;
     it sends (left, right, out) on `bus` when is_real = 1 and relies on the Poseidon2 chip to receive it, i.e. to

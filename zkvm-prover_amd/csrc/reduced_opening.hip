@@ -4,9 +4,9 @@
 // rows before it, so the generator is not one lane per record: the accumulator column is a SCAN over the rows under the monoid of affine
 // maps x -> x m + v of the extension field.  A row's map is (alpha, b - a); the first row of a call has m = 0, which forgets whatever came
 // before it -- the segments need no flags.  Five launches on the context's stream, none of which waits on another workgroup:
-//   k_ro_len_sums   the sum of the lengths of each slice of calls
-//   k_ro_offsets    off[c] = the first row of call c (exclusive scan of the lengths; each workgroup adds the slices before its own), the
-//                   checks on the lengths
+//   k_ro_len_sums   the sum of the lengths of each slice of calls                                                    (call_offsets.hpp, shared
+//   k_ro_offsets    off[c] = the first row of call c (exclusive scan of the lengths; each workgroup adds the slices      with mmcs_rows.hip)
+//                   before its own), the checks on the lengths
 //   k_ro_pass<0>    the composed map of each workgroup's rows
 //   k_ro_carries    one wave scans those: the accumulator in front of each workgroup's first row
 //   k_ro_pass<1>    the rows: call and element from the offsets, operands, the scan again from the carry, the 18 columns
@@ -17,16 +17,12 @@
 
 #include "../../include/zkhip.h"
 #include "babybear.hpp"
+#include "call_offsets.hpp"
 #include "lds_barrier.hpp"
 #include "tracegen_common.hpp"
 
 namespace zk {
 namespace {
-
-constexpr unsigned RO_W = ZKHIP_REDUCED_OPENING_BLOCK_ROWS;   // rows of one pass of a workgroup = its lanes
-constexpr unsigned RO_WAVES = RO_W / 64;
-constexpr unsigned RO_MAX_BLOCKS = 1024;                      // workgroups per launch (4 per CU): what k_ro_carries scans, 64 at a time
-static_assert(RO_W % 64 == 0 && RO_W <= 1024, "a workgroup pass is a whole number of waves");
 
 // x -> x m + v
 struct Affine {
@@ -54,66 +50,6 @@ __device__ __forceinline__ Affine affine_ld(const uint32_t* p) { return Affine{E
 __device__ __forceinline__ void affine_st(uint32_t* p, const Affine& f) {
 #pragma unroll
     for (int q = 0; q < 4; q++) p[q] = f.m.c[q], p[4 + q] = f.v.c[q];
-}
-
-// ---- the offsets: an exclusive scan of the lengths in 64 bits (2^27 lengths of 32 bits cannot overflow it) --------------------------------
-__device__ __forceinline__ uint64_t u64_shfl_up(uint64_t v, unsigned off) {
-    return ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(v >> 32), off, 64) << 32) | (uint32_t)__shfl_up((int)(uint32_t)v, off, 64);
-}
-// the inclusive scan of one value per lane over the workgroup and the workgroup's sum; `tot` (LDS, a word per wave) is free again on return
-__device__ __forceinline__ uint64_t block_scan_u64(uint64_t v, uint64_t* tot, uint64_t* total) {
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (unsigned off = 1; off < 64; off <<= 1) {
-        const uint64_t o = u64_shfl_up(v, off);
-        if (lane >= off) v += o;
-    }
-    zk_syncthreads();   // (every wave has read what the call before left in `tot`)
-    if (lane == 63) tot[wave] = v;
-    zk_syncthreads();
-    uint64_t before = 0, all = 0;
-    for (unsigned w = 0; w < RO_WAVES; w++) {
-        const uint64_t t = tot[w];
-        before += w < wave ? t : 0;
-        all += t;
-    }
-    *total = all;
-    return v + before;
-}
-
-// per_block: calls per workgroup, a multiple of RO_W
-__global__ __launch_bounds__(RO_W) void k_ro_len_sums(const uint32_t* __restrict__ len, size_t n_calls, size_t per_block, uint64_t* __restrict__ sums) {
-    __shared__ uint64_t tot[RO_WAVES];
-    const size_t begin = (size_t)blockIdx.x * per_block, end = std::min(begin + per_block, n_calls);
-    uint64_t s = 0;
-    for (size_t i = begin + threadIdx.x; i < end; i += RO_W) s += len[i];
-    uint64_t all;
-    block_scan_u64(s, tot, &all);
-    if (threadIdx.x == 0) sums[blockIdx.x] = all;
-}
-
-// off[c] = min(len[0] + .. + len[c - 1], n_elems + 1) for c <= n_calls; refuses a length of 0 and a total other than n_elems
-__global__ __launch_bounds__(RO_W) void k_ro_offsets(const uint32_t* __restrict__ len, size_t n_calls, size_t n_elems, size_t per_block,
-                                                     const uint64_t* __restrict__ sums, uint32_t* __restrict__ off, uint32_t* __restrict__ bad) {
-    __shared__ uint64_t tot[RO_WAVES];
-    const size_t begin = (size_t)blockIdx.x * per_block, end = std::min(begin + per_block, n_calls);
-    const uint64_t cap = (uint64_t)n_elems + 1;
-    uint64_t pre = 0, base;
-    for (unsigned j = threadIdx.x; j < blockIdx.x; j += RO_W) pre += sums[j];
-    block_scan_u64(pre, tot, &base);
-    for (size_t start = begin; start < end; start += RO_W) {
-        const size_t i = start + threadIdx.x;
-        const uint32_t l = i < end ? len[i] : 0u;
-        if (i < end && l == 0) atomicAdd(bad, 1u);
-        uint64_t all;
-        const uint64_t incl = block_scan_u64(l, tot, &all);
-        if (i < end) off[i] = (uint32_t)std::min(base + incl - l, cap);
-        base += all;
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        off[n_calls] = (uint32_t)std::min(base, cap);
-        if (base != (uint64_t)n_elems) atomicAdd(bad, 1u);
-    }
 }
 
 // ---- the rows --------------------------------------------------------------------------------------------------------------------------
@@ -279,13 +215,12 @@ int zkhip_reduced_opening_tracegen(zkhip_ctx* ctx, const uint32_t* d_alpha, cons
         ZK_HIP_CHECK(ctx, hipMemsetAsync(d_trace, 0, (size_t)ZKHIP_REDUCED_OPENING_WIDTH * N * 4, ctx->stream));
         return ZKHIP_OK;
     }
-    // calls per workgroup of the offset kernels and rows per workgroup of the passes: whole passes, at most RO_MAX_BLOCKS workgroups.  A
-    // workgroup of the passes takes at least two of them where the trace has two: half the maps for k_ro_carries at the price of one carried word
+    // rows per workgroup of the passes: whole passes, at most RO_MAX_BLOCKS workgroups.  A workgroup of the passes takes at least two of
+    // them where the trace has two: half the maps for k_ro_carries at the price of one carried word
     const auto whole = [](size_t x) { return (x + RO_W - 1) / RO_W * RO_W; };
-    const size_t calls_per_block = whole((n_calls + RO_MAX_BLOCKS - 1) / RO_MAX_BLOCKS);
     const size_t rows_per_block = std::max<size_t>(whole((N + RO_MAX_BLOCKS - 1) / RO_MAX_BLOCKS), 2 * RO_W);
-    const unsigned len_blocks = (unsigned)((n_calls + calls_per_block - 1) / calls_per_block), row_blocks = (unsigned)((N + rows_per_block - 1) / rows_per_block);
-    // scratch: off[n_calls + 1] | sums[len_blocks] (64 bits) | maps[row_blocks][8] | carry[row_blocks][4]
+    const unsigned row_blocks = (unsigned)((N + rows_per_block - 1) / rows_per_block);
+    // scratch: off[n_calls + 1] | sums[RO_MAX_BLOCKS] (64 bits) | maps[row_blocks][8] | carry[row_blocks][4]
     const size_t off_words = (n_calls + 1 + 3) / 4 * 4;
     void* buf = nullptr;
     ZK_TRY(get_scratch(ctx, 3, (off_words + 2 * (size_t)RO_MAX_BLOCKS + 12 * (size_t)RO_MAX_BLOCKS) * 4, &buf));
@@ -296,8 +231,7 @@ int zkhip_reduced_opening_tracegen(zkhip_ctx* ctx, const uint32_t* d_alpha, cons
     return tracegen_frame(
         ctx, "reduced_opening_tracegen", {},
         [&](uint32_t* bad) {
-            hipLaunchKernelGGL(k_ro_len_sums, dim3(len_blocks), dim3(RO_W), 0, ctx->stream, d_len, n_calls, calls_per_block, sums);
-            hipLaunchKernelGGL(k_ro_offsets, dim3(len_blocks), dim3(RO_W), 0, ctx->stream, d_len, n_calls, n_elems, calls_per_block, (const uint64_t*)sums, off, bad);
+            launch_call_offsets(ctx, d_len, n_calls, n_elems, 0, true, sums, off, bad);   // k_ro_len_sums, k_ro_offsets
             hipLaunchKernelGGL(k_ro_pass<false>, dim3(row_blocks), dim3(RO_W), 0, ctx->stream, in, N, rows_per_block, maps, (uint32_t*)nullptr, bad);
             hipLaunchKernelGGL(k_ro_carries, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t*)maps, row_blocks, carry);
             hipLaunchKernelGGL(k_ro_pass<true>, dim3(row_blocks), dim3(RO_W), 0, ctx->stream, in, N, rows_per_block, carry, d_trace, bad);
