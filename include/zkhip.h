@@ -350,6 +350,38 @@ int zkhip_mmcs_rows_tracegen(zkhip_ctx *ctx, const uint32_t *d_len, const uint32
                              const uint32_t *d_mult, const uint32_t *d_values, size_t n_calls, size_t n_words, unsigned log_height,
                              uint32_t *d_trace, uint32_t *d_hash_inputs, uint32_t *d_digest);
 
+/* FRI query chip (a piece of the recursion circuit, air.py fri_query_air; docs/fri_query.md): one query's fold loop of one FRI proof --
+ * the `for l < n_layers` loop of the host verifier (csrc/verifier.hip) -- n_layers consecutive rows, one per commit-phase layer from the
+ * tallest down.  With index the query's index and log_max the log2 of the tallest LDE height, layer l opens the pair k = index >> (l + 1)
+ * of the tree of height log_max - 1 - l: the value carried so far on side (index >> l) & 1, the proof's sibling on the other; the next
+ * value is fold_row of the pair at beta[l], plus beta[l]^2 ro[l] where a reduced opening joins at that height (has_ro[l] = 1).
+ *   zkhip_fri_query_host      the definition, no device, canonical words: per layer beta[4 l ..], sibling[4 l ..], has_ro[l], ro[4 l ..]
+ *                             (zero under has_ro = 0) and ro_top[4], the value the loop starts from (the reduced opening at log_max);
+ *                             writes per layer e0[4 l ..], e1[4 l ..] (the pair) and eval[4 l ..].  It calls the verifier's own fold_row.
+ *                             ZKHIP_ERR_INVALID for a NULL pointer, log_max > 27, n_layers = 0 or > log_max - 1 (the last row folds into
+ *                             a tree of height >= 1), index >= 2^log_max, a word >= p, has_ro outside {0, 1} or a non-zero ro under
+ *                             has_ro = 0; nothing is written then.
+ *   zkhip_fri_query_tracegen  the chip's trace for n_calls calls.  Records are canonical words: per call c d_n_layers[c], d_log_max[c],
+ *                             d_index[c], d_ro_top[4 c ..]; per row r, all calls end to end in layer order, d_beta[4 r ..], d_root[8 r ..]
+ *                             (the layer's commitment), d_sibling[4 r ..], d_has_ro[r], d_ro[4 r ..].  Fills d_trace
+ *                             (ZKHIP_FRI_QUERY_WIDTH = 61 columns, stride 2^log_height, Montgomery: e0[4] | e1[4] | beta[4] | bsq[4] |
+ *                             x_inv | folded[4] | ro[4] | eval[4] | st_out[16] | root[8] | bit | has_ro | k | lvl | is_first | is_last |
+ *                             is_real | call with call = c; rows behind the last call zero), d_hash_inputs ([2^log_height][16]
+ *                             Montgomery: e0 | e1 | 0^8 of every row, the input of zkhip_poseidon2_air_tracegen for the Poseidon2 chip
+ *                             with 16 output lanes that serves the chip's hash bus) and, unless they are NULL, d_leaf_digest
+ *                             ([n_rows][8] CANONICAL: what zkhip_mmcs_path_tracegen takes as d_leaf) and d_final ([n_calls][4] CANONICAL:
+ *                             the last eval of every call).  The lengths are scanned on the device and never read back.
+ *                             ZKHIP_ERR_INVALID for what the host function refuses, lengths that do not sum to n_rows and more rows than
+ *                             2^log_height (all checked on the device like every generator's records: zkhip_tracegen_defer_checks), and
+ *                             at once for a NULL pointer, log_height > 27 or n_calls > n_rows. */
+#define ZKHIP_FRI_QUERY_WIDTH 61
+int zkhip_fri_query_host(uint64_t index, unsigned log_max, unsigned n_layers, const uint32_t *beta, const uint32_t *sibling,
+                         const uint32_t *has_ro, const uint32_t *ro, const uint32_t ro_top[4], uint32_t *e0, uint32_t *e1, uint32_t *eval);
+int zkhip_fri_query_tracegen(zkhip_ctx *ctx, const uint32_t *d_n_layers, const uint32_t *d_log_max, const uint32_t *d_index,
+                             const uint32_t *d_ro_top, const uint32_t *d_beta, const uint32_t *d_root, const uint32_t *d_sibling,
+                             const uint32_t *d_has_ro, const uint32_t *d_ro, size_t n_calls, size_t n_rows, unsigned log_height,
+                             uint32_t *d_trace, uint32_t *d_hash_inputs, uint32_t *d_leaf_digest, uint32_t *d_final);
+
 /* System chips: the PROGRAM chip and the execution frames that look instructions up in it.  OpenVM's ProgramAir keeps the program
  * (ZKHIP_PROGRAM_FIELDS = 9 fields per instruction: pc, opcode, operands a..g) as a CACHED main partition and one common column,
  * the execution frequency of each instruction; it receives every instruction that often on the program bus (the first AIR of the

@@ -1426,6 +1426,152 @@ inline void mmcs_rows_air(AirBuilder& b, uint32_t hash_bus, uint32_t claims_bus,
     }
 }
 
+// air.fri_query_air(point_bus, hash_bus, claims_bus, ro_bus, layer_bus, final_bus): AirBuilder(61, 0) -- one query's fold loop, a row per
+// commit-phase layer from the tallest down: the fold, eval = folded + beta^2 ro, the chain e'[bit'] = eval, k = 2 k' + bit', lvl' = lvl - 1;
+// the pair is hashed on hash_bus and claimed as leaf k of the tree of height lvl under root on claims_bus (docs/fri_query.md)
+inline void fri_query_air(AirBuilder& b, uint32_t point_bus, uint32_t hash_bus, uint32_t claims_bus, uint32_t ro_bus, int layer_bus = -1, int final_bus = -1) {
+    Expr e0[4], e1[4], beta[4], bsq[4], folded[4], ro[4], ev[4], st_out[16], root[8], n_e0[4], n_e1[4], d[4], prod[4], sq[4], join[4];
+    for (int i = 0; i < 4; i++) e0[i] = b.var(i);
+    for (int i = 0; i < 4; i++) e1[i] = b.var(4 + i);
+    for (int i = 0; i < 4; i++) beta[i] = b.var(8 + i);
+    for (int i = 0; i < 4; i++) bsq[i] = b.var(12 + i);
+    const Expr xinv = b.var(16);
+    for (int i = 0; i < 4; i++) folded[i] = b.var(17 + i);
+    for (int i = 0; i < 4; i++) ro[i] = b.var(21 + i);
+    for (int i = 0; i < 4; i++) ev[i] = b.var(25 + i);
+    for (int i = 0; i < 16; i++) st_out[i] = b.var(29 + i);
+    for (int i = 0; i < 8; i++) root[i] = b.var(45 + i);
+    const Expr bit = b.var(53), has_ro = b.var(54), k = b.var(55), lvl = b.var(56), first = b.var(57), last = b.var(58), real = b.var(59), call = b.var(60);
+    for (int i = 0; i < 4; i++) n_e0[i] = b.next(i);
+    for (int i = 0; i < 4; i++) n_e1[i] = b.next(4 + i);
+    const Expr n_bit = b.next(53), n_k = b.next(55), n_lvl = b.next(56), n_first = b.next(57), n_real = b.next(59), n_call = b.next(60);
+    for (const Expr& f : {first, last, real, bit, has_ro}) {
+        const Expr t = f - 1;
+        b.assert_zero(f * t);
+    }
+    const Expr pad = 1 - real;
+    b.assert_zero(first * pad);
+    b.assert_zero(last * pad);
+    b.assert_zero(has_ro * pad);
+    {
+        const Expr df = first - real;
+        b.when_first_row(df);
+    }
+    const Expr s = real - last;
+    b.when_last_row(s);
+    auto step_to = [&](const Expr& e) {   // when_transition(s * e)
+        const Expr g = s * e;
+        b.when_transition(g);
+    };
+    {
+        const Expr t = n_real - 1;
+        step_to(t);
+    }
+    step_to(n_first);
+    {
+        const Expr t = n_real - n_first;
+        const Expr g = last * t;
+        b.when_transition(g);
+    }
+    {
+        const Expr g = pad * n_real;
+        b.when_transition(g);
+    }
+    for (int i = 0; i < 4; i++) {
+        const Expr t = 1 - has_ro;
+        b.assert_zero(t * ro[i]);
+    }
+    for (int i = 0; i < 4; i++) d[i] = e0[i] - e1[i];
+    ext_mul_exprs(beta, d, prod);
+    ext_mul_exprs(beta, beta, sq);
+    ext_mul_exprs(bsq, ro, join);
+    for (int i = 0; i < 4; i++) {
+        const Expr f2 = folded[i] * 2;
+        const Expr a = f2 - e0[i];
+        const Expr c = a - e1[i];
+        const Expr xp = xinv * prod[i];
+        b.assert_zero(c - xp);
+    }
+    for (int i = 0; i < 4; i++) b.assert_zero(bsq[i] - sq[i]);
+    for (int i = 0; i < 4; i++) {
+        const Expr t = ev[i] - folded[i];
+        b.assert_zero(t - join[i]);
+    }
+    {
+        const Expr t = n_call - call;
+        step_to(t);
+    }
+    {
+        const Expr t = n_lvl - lvl;
+        const Expr u = t + 1;
+        step_to(u);
+    }
+    {
+        const Expr t = n_k * 2;
+        const Expr u = k - t;
+        const Expr v = u - n_bit;
+        step_to(v);
+    }
+    for (int i = 0; i < 4; i++) {
+        const Expr t = n_e1[i] - n_e0[i];
+        const Expr u = n_bit * t;
+        const Expr v = n_e0[i] + u;
+        const Expr w = v - ev[i];
+        step_to(w);
+    }
+    b.push_interaction(point_bus, {k, xinv}, real, Kind::Send);
+    {
+        std::vector<Expr> msg;
+        for (int i = 0; i < 4; i++) msg.push_back(e0[i]);
+        for (int i = 0; i < 4; i++) msg.push_back(e1[i]);
+        for (int i = 0; i < 8; i++) msg.push_back(b.constant(0));
+        for (int i = 0; i < 16; i++) msg.push_back(st_out[i]);
+        b.push_interaction(hash_bus, msg, real, Kind::Send);
+    }
+    {
+        std::vector<Expr> msg;
+        for (int i = 0; i < 8; i++) msg.push_back(root[i]);
+        msg.push_back(lvl);
+        msg.push_back(k);
+        for (int i = 0; i < 8; i++) msg.push_back(st_out[i]);
+        b.push_interaction(claims_bus, msg, real, Kind::Receive);
+    }
+    {
+        std::vector<Expr> msg;
+        msg.push_back(call);
+        msg.push_back(lvl);
+        for (int i = 0; i < 4; i++) msg.push_back(ro[i]);
+        b.push_interaction(ro_bus, msg, has_ro, Kind::Receive);
+    }
+    {
+        std::vector<Expr> msg;
+        msg.push_back(call);
+        msg.push_back(lvl + 1);
+        for (int i = 0; i < 4; i++) {
+            const Expr t = e1[i] - e0[i];
+            const Expr u = bit * t;
+            msg.push_back(e0[i] + u);
+        }
+        b.push_interaction(ro_bus, msg, first, Kind::Receive);
+    }
+    if (layer_bus >= 0) {
+        std::vector<Expr> msg;
+        msg.push_back(call);
+        msg.push_back(lvl);
+        for (int i = 0; i < 4; i++) msg.push_back(beta[i]);
+        for (int i = 0; i < 8; i++) msg.push_back(root[i]);
+        b.push_interaction((uint32_t)layer_bus, msg, real, Kind::Send);
+    }
+    if (final_bus >= 0) {
+        std::vector<Expr> msg;
+        msg.push_back(call);
+        msg.push_back(lvl);
+        msg.push_back(k);
+        for (int i = 0; i < 4; i++) msg.push_back(ev[i]);
+        b.push_interaction((uint32_t)final_bus, msg, last, Kind::Send);
+    }
+}
+
 // air.mmcs_claims_air(claims_bus): AirBuilder(19, 0)
 inline void mmcs_claims_air(AirBuilder& b, uint32_t claims_bus) {
     std::vector<Expr> msg;

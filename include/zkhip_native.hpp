@@ -13,7 +13,9 @@
 // chip is built, as a stand-alone core on cells instead of native memory (air.py reduced_opening_air, zkhip_reduced_opening_tracegen,
 // docs/reduced_opening.md), and so is the verify-batch chip, as stand-alone cores that are wired into no circuit yet (air.py
 // mmcs_rows_air + mmcs_path_air + the two Poseidon2 chips: opened words -> row digests -> path -> root; zkhip_mmcs_rows_tracegen,
-// docs/mmcs_rows.md); the native address space and its instruction set are not.  The
+// docs/mmcs_rows.md).  The fold loop of a FRI query behind the reduced openings is built the same way (air.py fri_query_air with
+// fri_fold_air's line, domain_point_air, mmcs_path_air and the Poseidon2 chips; zkhip_fri_query_tracegen, docs/fri_query.md): a core on
+// cells, wired into no circuit yet.  The native address space and its instruction set are not.  The
 // three arithmetic chips sit behind CUSTOM ecalls (9 / 10 / 11) on the RV32 memory, not behind OpenVM's native opcodes: a guest that uses
 // openvm `verify_stark` (a native-address-space recursion program) cannot run on this executor.  `[app_vm_config.native]` is therefore
 // COVERED IN PART: its field arithmetic, not its instruction set (docs/gaps.md).

@@ -49,6 +49,7 @@ pub const ZKHIP_DOMAIN_POINT_WIDTH: usize = 54;
 pub const ZKHIP_REDUCED_OPENING_WIDTH: usize = 18;
 pub const ZKHIP_REDUCED_OPENING_BLOCK_ROWS: usize = 256;
 pub const ZKHIP_MMCS_ROWS_WIDTH: usize = 56;
+pub const ZKHIP_FRI_QUERY_WIDTH: usize = 61;
 pub const ZKHIP_CASTF_WIDTH: usize = 6;
 pub const ZKHIP_FIELD_ARITH_WIDTH: usize = 8;
 pub const ZKHIP_FIELD_EXT_WIDTH: usize = 20;
@@ -312,6 +313,10 @@ extern "C" {
     pub fn zkhip_mmcs_rows_tracegen(ctx: *mut zkhip_ctx, d_len: *const u32, d_root: *const u32, d_lvl: *const u32, d_idx: *const u32, d_mult: *const u32,
                                     d_values: *const u32, n_calls: usize, n_words: usize, log_height: c_uint, d_trace: *mut u32,
                                     d_hash_inputs: *mut u32, d_digest: *mut u32) -> c_int;
+    pub fn zkhip_fri_query_tracegen(ctx: *mut zkhip_ctx, d_n_layers: *const u32, d_log_max: *const u32, d_index: *const u32, d_ro_top: *const u32,
+                                    d_beta: *const u32, d_root: *const u32, d_sibling: *const u32, d_has_ro: *const u32, d_ro: *const u32,
+                                    n_calls: usize, n_rows: usize, log_height: c_uint, d_trace: *mut u32, d_hash_inputs: *mut u32,
+                                    d_leaf_digest: *mut u32, d_final: *mut u32) -> c_int;
     pub fn zkhip_castf_tracegen(ctx: *mut zkhip_ctx, d_x: *const u32, n: usize, log_height: c_uint, d_trace: *mut u32, d_var_range_counts: *mut u32,
                                 max_bits: c_uint) -> c_int;
     pub fn zkhip_field_arith_tracegen(ctx: *mut zkhip_ctx, d_opcode: *const u32, d_b: *const u32, d_c: *const u32, n: usize, log_height: c_uint,
@@ -403,6 +408,8 @@ extern "C" {
     pub fn zkhip_mmcs_verify(root: *const u32, log_heights: *const c_uint, widths: *const usize, n_mats: usize, index: u64,
                              opening: *const u32) -> c_int;
     pub fn zkhip_hash_slice_host(input: *const u32, len: usize, out: *mut u32) -> c_int;
+    pub fn zkhip_fri_query_host(index: u64, log_max: c_uint, n_layers: c_uint, beta: *const u32, sibling: *const u32, has_ro: *const u32, ro: *const u32,
+                                ro_top: *const u32, e0: *mut u32, e1: *mut u32, eval: *mut u32) -> c_int;
     pub fn zkhip_fri_fold_row(index: u64, log_height: c_uint, beta: *const u32, e0: *const u32, e1: *const u32, out: *mut u32) -> c_int;
     pub fn zkhip_reduced_opening_host(alpha: *const u32, a: *const u32, b: *const u32, len: usize, out: *mut u32) -> c_int;
     pub fn zkhip_logup_exposed_check(exposed: *const u32, n: usize) -> c_int;

@@ -148,6 +148,7 @@ def load_library():
         "zkhip_fri_fold_chip_tracegen": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, C.c_uint, vp]),
         "zkhip_reduced_opening_tracegen": (C.c_int, [vp, vp, vp, vp, vp, sz, sz, C.c_uint, vp]),
         "zkhip_mmcs_rows_tracegen": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, sz, C.c_uint, vp, vp, vp]),
+        "zkhip_fri_query_tracegen": (C.c_int, [vp] * 10 + [sz, sz, C.c_uint, vp, vp, vp, vp]),
         "zkhip_castf_tracegen": (C.c_int, [vp, vp, sz, C.c_uint, vp, vp, C.c_uint]),
         "zkhip_field_arith_tracegen": (C.c_int, [vp, vp, vp, vp, sz, C.c_uint, vp]),
         "zkhip_field_ext_tracegen": (C.c_int, [vp, vp, vp, vp, sz, C.c_uint, vp]),
@@ -197,6 +198,7 @@ def load_library():
         "zkhip_fri_fold_row": (C.c_int, [C.c_uint64, C.c_uint, u32p, u32p, u32p, u32p]),
         "zkhip_reduced_opening_host": (C.c_int, [u32p, u32p, u32p, sz, u32p]),
         "zkhip_hash_slice_host": (C.c_int, [u32p, sz, u32p]),
+        "zkhip_fri_query_host": (C.c_int, [C.c_uint64, C.c_uint, C.c_uint] + [u32p] * 8),
         "zkhip_logup_exposed_check": (C.c_int, [u32p, sz]),
         "zkhip_proof_decode_v1": (C.c_int, [C.POINTER(C.c_uint8), sz, C.c_int, C.POINTER(_V1Summary)]),
         "zkhip_proof_reencode_v1": (C.c_int, [C.POINTER(C.c_uint8), sz, C.c_int, C.POINTER(C.c_uint8), sz, C.POINTER(sz)]),
@@ -681,6 +683,25 @@ class Context:
                                                       t_len.numel(), t_values.numel(), log_height, C.c_void_p(tr.data_ptr()), C.c_void_p(hin.data_ptr()),
                                                       C.c_void_p(dg.data_ptr()) if digests else None))
         return tr, hin, dg
+
+    def fri_query_tracegen(self, t_n_layers, t_log_max, t_index, t_ro_top, t_beta, t_root, t_sibling, t_has_ro, t_ro, log_height, leaf_digests=True,
+                           final=True):
+        """(61-column trace of the FRI query chip, [2^log_height][16] permutation inputs for the Poseidon2 chip with 16 output lanes, the
+        rows' leaf digests [n_rows][8] CANONICAL or None, the calls' last evals [n_calls][4] CANONICAL or None) from records (int32 tensors,
+        canonical: per call its number of layers, log_max, index and ro_top [n_calls][4]; per row, all calls end to end, beta [n_rows][4],
+        root [n_rows][8], sibling [n_rows][4], has_ro and ro [n_rows][4]).  leaf_digests=False / final=False pass NULL."""
+        import torch
+
+        n_calls, n_rows = t_n_layers.numel(), t_has_ro.numel()
+        tr = torch.empty(FRI_QUERY_WIDTH << log_height, dtype=torch.int32, device=self.device)
+        hin = torch.empty(16 << log_height, dtype=torch.int32, device=self.device)
+        dg = torch.empty(8 * n_rows, dtype=torch.int32, device=self.device) if leaf_digests else None
+        fin = torch.empty(4 * n_calls, dtype=torch.int32, device=self.device) if final else None
+        recs = (t_n_layers, t_log_max, t_index, t_ro_top, t_beta, t_root, t_sibling, t_has_ro, t_ro)
+        self._check(self.lib.zkhip_fri_query_tracegen(self.h, *[C.c_void_p(t.data_ptr()) for t in recs], n_calls, n_rows, log_height, C.c_void_p(tr.data_ptr()),
+                                                      C.c_void_p(hin.data_ptr()), C.c_void_p(dg.data_ptr()) if leaf_digests else None,
+                                                      C.c_void_p(fin.data_ptr()) if final else None))
+        return tr, hin, dg, fin
 
     def castf_tracegen(self, t_x, log_height, t_var_range_counts, max_bits):
         """6-column trace of the native CASTF chip from records (int32 tensor of values < 2^30); the limb checks are added to
@@ -2234,6 +2255,23 @@ def hash_slice_host(words):
     if rc != 0:
         raise ZkhipError("zkhip_hash_slice_host returned %d" % rc)
     return out
+
+
+FRI_QUERY_WIDTH = 61                # ZKHIP_FRI_QUERY_WIDTH
+
+
+def fri_query_host(index, log_max, beta, sibling, has_ro, ro, ro_top):
+    """One query's fold loop on canonical words (beta, sibling, ro [n_layers][4], has_ro [n_layers], ro_top [4]); returns
+    (e0, e1, eval), [n_layers][4] canonical each: the pair opened on every layer and the value folded from it."""
+    bt, sb, hs, rv, rt = (np.ascontiguousarray(v, dtype=np.uint32).reshape(-1) for v in (beta, sibling, has_ro, ro, ro_top))
+    n = hs.size
+    if bt.size != 4 * n or sb.size != 4 * n or rv.size != 4 * n or rt.size != 4:
+        raise ZkhipError("fri_query_host: beta, sibling and ro have four words per layer and ro_top has four")
+    e0, e1, ev = (np.zeros((n, 4), dtype=np.uint32) for _ in range(3))
+    rc = load_library().zkhip_fri_query_host(int(index), int(log_max), n, _u32p(bt), _u32p(sb), _u32p(hs), _u32p(rv), _u32p(rt), _u32p(e0), _u32p(e1), _u32p(ev))
+    if rc != 0:
+        raise ZkhipError("zkhip_fri_query_host returned %d" % rc)
+    return e0, e1, ev
 
 
 # ---- the reference's stored-proof container (OpenVM-v1 Proof<SC>, bincode): include/zkhip_codec.hpp ----

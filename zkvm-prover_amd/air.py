@@ -1839,6 +1839,74 @@ def mmcs_rows_air(hash_bus, claims_bus, values_bus=None):
     return b
 
 
+FRI_QUERY_WIDTH = 61
+
+
+def fri_query_air(point_bus, hash_bus, claims_bus, ro_bus, layer_bus=None, final_bus=None):
+    """One query's fold loop of a FRI proof, in-circuit (the `for l < n_layers` loop of the host verifier, csrc/verifier.hip;
+    zkhip_fri_query_host is the definition): what ties fri_fold_air's independent steps into a query.  Columns e0[4] | e1[4] | beta[4] |
+    bsq[4] | x_inv | folded[4] | ro[4] | eval[4] | st_out[16] | root[8] | bit | has_ro | k | lvl | is_first | is_last | is_real | call.
+    A call is one query: n_layers consecutive rows, one per commit-phase layer, from the tallest layer down.  With idx the query's index
+    and log_max the log2 of the tallest LDE height, row t has lvl = log_max - 1 - t (the height of that layer's tree), bit = (idx >> t) & 1
+    and the pair index k = idx >> (t + 1).  Per row: 2 folded = (e0 + e1) + x_inv (beta (e0 - e1)) as in fri_fold_air, bsq = beta beta,
+    eval = folded + bsq ro (ro = 0 unless has_ro: the reduced opening that joins at height lvl); across rows of a call lvl' = lvl - 1,
+    k = 2 k' + bit' and the chain e0' + bit' (e1' - e0') = eval: the value folded on a layer is the one opened on the next.  The row
+    sends (k, x_inv) on `point_bus` (domain_point_air receives it), e0 ++ e1 ++ 0^8 ++ st_out on `hash_bus` (the 32-field message of
+    poseidon2_air(bus, out_lanes=16): a leaf of 8 words is one permutation of the sponge) and RECEIVES (root, lvl, k, st_out[0..8]) on
+    `claims_bus` -- field by field what mmcs_path_air sends for a path's last row: the pair is leaf k of the tree of height lvl under
+    root.  On `ro_bus` it receives (call, lvl, ro) with multiplicity has_ro and, on the first row, (call, lvl + 1, e0 + bit (e1 - e0)):
+    the loop starts from the reduced opening at log_max.  With `layer_bus` every row sends (call, lvl, beta, root), with `final_bus` the
+    is_last row sends (call, lvl, k, eval).  The flags follow reduced_opening_air's skeleton (s = is_real - is_last).
+    docs/fri_query.md has the argument why a satisfying trace with balanced buses fixes the final message."""
+    b = AirBuilder(FRI_QUERY_WIDTH, 0)
+    e0, e1, beta, bsq = ([b.var(4 * j + i) for i in range(4)] for j in range(4))
+    xinv = b.var(16)
+    folded, ro, ev = ([b.var(17 + 4 * j + i) for i in range(4)] for j in range(3))
+    st_out = [b.var(29 + i) for i in range(16)]
+    root = [b.var(45 + i) for i in range(8)]
+    bit, has_ro, k, lvl, first, last, real, call = (b.var(53 + i) for i in range(8))
+    n_e0, n_e1 = [b.next(i) for i in range(4)], [b.next(4 + i) for i in range(4)]
+    n_bit, n_k, n_lvl, n_first, n_real, n_call = b.next(53), b.next(55), b.next(56), b.next(57), b.next(59), b.next(60)
+    for f in (first, last, real, bit, has_ro):
+        b.assert_zero(f * (f - 1))
+    pad = 1 - real
+    b.assert_zero(first * pad)
+    b.assert_zero(last * pad)
+    b.assert_zero(has_ro * pad)
+    b.when_first_row(first - real)
+    s = real - last
+    b.when_last_row(s)
+    b.when_transition(s * (n_real - 1))
+    b.when_transition(s * n_first)
+    b.when_transition(last * (n_real - n_first))
+    b.when_transition(pad * n_real)
+    for i in range(4):
+        b.assert_zero((1 - has_ro) * ro[i])
+    d = [e0[i] - e1[i] for i in range(4)]
+    prod, sq, join = _ext_mul_exprs(beta, d), _ext_mul_exprs(beta, beta), _ext_mul_exprs(bsq, ro)
+    for i in range(4):
+        b.assert_zero(folded[i] * 2 - e0[i] - e1[i] - xinv * prod[i])
+    for i in range(4):
+        b.assert_zero(bsq[i] - sq[i])
+    for i in range(4):
+        b.assert_zero(ev[i] - folded[i] - join[i])
+    b.when_transition(s * (n_call - call))
+    b.when_transition(s * (n_lvl - lvl + 1))
+    b.when_transition(s * (k - n_k * 2 - n_bit))
+    for i in range(4):
+        b.when_transition(s * (n_e0[i] + n_bit * (n_e1[i] - n_e0[i]) - ev[i]))
+    b.push_interaction(point_bus, [k, xinv], real, "send")
+    b.push_interaction(hash_bus, e0 + e1 + [0] * 8 + st_out, real, "send")
+    b.push_interaction(claims_bus, root + [lvl, k] + st_out[:8], real, "receive")
+    b.push_interaction(ro_bus, [call, lvl] + ro, has_ro, "receive")
+    b.push_interaction(ro_bus, [call, lvl + 1] + [e0[i] + bit * (e1[i] - e0[i]) for i in range(4)], first, "receive")
+    if layer_bus is not None:
+        b.push_interaction(layer_bus, [call, lvl] + beta + root, real, "send")
+    if final_bus is not None:
+        b.push_interaction(final_bus, [call, lvl, k] + ev, last, "send")
+    return b
+
+
 def hasher_user_air(bus):
     """A chip that needs 2-to-1 compressions (a Merkle-path checker, say): columns left[8] | right[8] | out[8] | is_real;
     it sends (left, right, out) on `bus` when is_real = 1 and relies on the Poseidon2 chip to receive it, i.e. to
