@@ -24,7 +24,8 @@
 //
 // The batched form of both (zkhip_airbatch_*, docs/airbatch.md, model tests/airbatch_model.py; kernels: airbatch_dev.hpp, airbatch_pass.hip): the same
 // statements with ONE constraint sum-check and ONE rotation reduction for the whole set, every AIR's point a prefix of the same r (r');
-// shape(), prove_bus() and the stacked opening are shared, prove_batch() and verify_batch() below are its own.
+// shape(), prove_bus(), the provers' frame (check_inputs .. open_and_finish) and the verifiers' pieces (verify_start .. verify_openings)
+// are shared; prove() / verify() and prove_batch() / verify_batch() are the two step lists over them.
 //
 // The keyed batched form with cached partitions (zkhip_airkey_cached_*, docs/cached_main.md, model tests/cached_batch_model.py): an AIR's
 // leading cached_width main columns are a stacked commitment of their own, made once (zkhip_cached_main); the main commitment holds the
@@ -452,232 +453,364 @@ int prove_bus(zkhip_ctx* ctx, const Shape& S, const zkhip_air* airs, size_t n_ai
     return ZKHIP_OK;
 }
 
-// either proof: with_bus, the AIR-set proof of docs/airset.md (its step numbers below); without, the zero-check of docs/zerocheck.md.
-// key: the keyed form (prm, airs and n_airs are the key's)
-int prove(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
-          const uint32_t* const* pvs, unsigned l, bool with_bus, DevTranscript* d_t, uint32_t* proof_out, size_t cap, uint32_t* root_out,
-          const zkhip_airkey* key = nullptr) {
-    const std::string who = key ? "airkey: " : with_bus ? "airset: " : "zerocheck: ";
-    Shape S;
-    if (!shape(prm, airs, n_airs, l, with_bus, &S, key ? (int)key->l_prep : -1))
-        return set_error(ctx, ZKHIP_ERR_INVALID, who + "the shape does not fit the limits");
-    if (cap < S.total) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, who + "proof buffer too small");
-    size_t n_pv = 0, pt_words = 0;
-    for (size_t a = 0; a < n_airs; a++) {
-        if (!d_traces[a] || (airs[a].n_pvs && !pvs[a])) return set_error(ctx, ZKHIP_ERR_INVALID, who + "null trace or public values");
-        for (size_t i = 0; i < airs[a].n_pvs; i++)
-            if (pvs[a][i] >= P) return set_error(ctx, ZKHIP_ERR_INVALID, who + "public value not canonical");
-        n_pv += airs[a].n_pvs, pt_words += 4 * (size_t)airs[a].log_height;
+// ---- what prove() and prove_batch() share ---------------------------------------------------------------------------------------
+// what a prove call was handed; key: the keyed form (prm, airs and n_airs are the key's), cached: the cached form (prove_batch only)
+struct ProveIn {
+    zkhip_ctx* ctx; const zkhip_whir_params* prm; const zkhip_air* airs; size_t n_airs; const uint32_t* const* d_traces; const uint32_t* const* pvs;
+    unsigned l; bool with_bus; DevTranscript* d_t; uint32_t* proof_out; size_t cap; uint32_t* root_out; const zkhip_airkey* key;
+    zkhip_cached_main* const* cached;
+};
+// the main commitment of one prove call, destroyed on every way out
+struct MainCom {
+    zkhip_ctx* ctx;
+    zkhip_stack_commitment* sc = nullptr;
+    uint32_t root[8] = {};
+    ~MainCom() { stack_destroy(ctx, sc); }
+};
+// n_pv: the public values of the whole set
+int check_inputs(const ProveIn& in, const std::string& who, size_t* n_pv) {
+    *n_pv = 0;
+    for (size_t a = 0; a < in.n_airs; a++) {
+        if (!in.d_traces[a] || (in.airs[a].n_pvs && !in.pvs[a])) return set_error(in.ctx, ZKHIP_ERR_INVALID, who + "null trace or public values");
+        for (size_t i = 0; i < in.airs[a].n_pvs; i++)
+            if (in.pvs[a][i] >= P) return set_error(in.ctx, ZKHIP_ERR_INVALID, who + "public value not canonical");
+        *n_pv += in.airs[a].n_pvs;
     }
-    // 1. commit: every main column, AIRs in caller order
-    std::vector<const uint32_t*> cols;
-    for (size_t a = 0; a < n_airs; a++)
-        for (size_t c = 0; c < airs[a].width; c++) cols.push_back(d_traces[a] + (c << airs[a].log_height));
-    struct Com {
-        zkhip_ctx* ctx;
-        zkhip_stack_commitment* sc = nullptr;
-        ~Com() { stack_destroy(ctx, sc); }
-    } com{ctx};
-    uint32_t root[8];
-    ZK_TRY(stack_commit(ctx, prm, cols.data(), S.lh.data(), cols.size(), l, &com.sc, root));
-    DevBufs B(ctx);
-    // device: [the words before the opening | the points r'_a (Montgomery)], then the root and the public values to observe
-    uint32_t *dP = B.get(S.head + pt_words), *d_obs = B.get((key ? 16 : 8) + n_pv);
-    if (!dP || !d_obs) return set_error(ctx, ZKHIP_ERR_NOMEM, who + "proof staging");
-    std::vector<uint32_t> obs;
-    if (key) obs.assign(key->root, key->root + 8);   // the key's root is observed, not sent
-    obs.insert(obs.end(), root, root + 8);
-    for (size_t a = 0; a < n_airs; a++) obs.insert(obs.end(), pvs[a], pvs[a] + airs[a].n_pvs);
-    ZK_TRY(zkhip_h2d(ctx, d_obs, obs.data(), obs.size() * 4));
-    ZK_TRY(transcript_observe(ctx, d_t, d_obs, (uint32_t)obs.size(), true));
-    // 2. - 5. the bus part
-    std::vector<ZcBus> bus(n_airs);   // E2 null: an AIR without interactions, or the zero-check
-    if (with_bus) ZK_TRY(prove_bus(ctx, S, airs, n_airs, d_traces, pvs, d_t, B, dP, &bus, key));
-    // 6. - 8. per AIR
-    size_t off = 8 + S.gkr_words + 4 * S.n_bus, poff = S.head;
-    for (size_t a = 0; a < n_airs; a++) {
-        const ZcPlan& pl = S.plans[a];
-        if (key && pl.wp) {   // the kernels' PREP form, on the key's resident columns
-            const uint32_t* prep = key->d_prep + key->prep_at[a];
-            if (bus[a].E2) ZK_TRY((zc_prove_air<true, true>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff, bus[a], prep)));
-            else ZK_TRY((zc_prove_air<false, true>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff, ZcBus{}, prep)));
-        } else if (bus[a].E2) ZK_TRY(zc_prove_air<true>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff, bus[a]));
-        else ZK_TRY(zc_prove_air<false>(ctx, d_t, pl, d_traces[a], pvs[a], dP + off, dP + poff));
-        off += pl.active() ? pl.words() : 0;
-        poff += 4 * (size_t)pl.m;
-    }
-    // 9. the one read-back before the opening: the words so far and the points
-    std::vector<uint32_t> h(S.head + pt_words);
-    ZK_TRY(zkhip_d2h(ctx, h.data(), dP, h.size() * 4));
-    for (size_t i = S.head; i < h.size(); i++) h[i] = from_monty(h[i]);
-    ZK_TRY(stack_open(ctx, com.sc, d_t, h.data() + S.head, S.dims.data(), n_airs, S.col_point.data(), nullptr, proof_out + S.head, cap - S.head));
-    if (key) {   // the key's commitment at the points of the AIRs that have preprocessed columns
-        std::vector<uint32_t> pts;
-        size_t at = S.head;
-        for (size_t a = 0; a < n_airs; at += 4 * (size_t)S.plans[a].m, a++)
-            if (S.plans[a].wp) pts.insert(pts.end(), h.begin() + at, h.begin() + at + 4 * (size_t)S.plans[a].m);
-        const size_t o = S.head + S.main_words;
-        ZK_TRY(stack_open(ctx, key->sc, d_t, pts.data(), S.dims_p.data(), S.dims_p.size(), S.col_point_p.data(), nullptr, proof_out + o, cap - o));
-    }
-    memcpy(proof_out, root, 32);
-    memcpy(proof_out + 8, h.data() + 8, (S.head - 8) * 4);
-    if (root_out) memcpy(root_out, root, 32);
     return ZKHIP_OK;
 }
-
-// ---- the host verifier ---------------------------------------------------------------------------------------------------------
-// of either proof; pq_out: the fraction sum's (P, Q), with_bus only
-// prep_root: the keyed form, checked against the key's root at l_prep
-int verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs, const uint32_t* const* pvs,
-           unsigned l, const uint32_t* proof, size_t words, bool with_bus, uint32_t* root_out, uint32_t* pq_out, const uint32_t* prep_root = nullptr,
-           unsigned l_prep = 0) {
-    Shape S;
-    if (!shape(prm, airs, n_airs, l, with_bus, &S, prep_root ? (int)l_prep : -1)) return ZKHIP_ERR_INVALID;
-    for (size_t i = 0; prep_root && i < 8; i++)
-        if (prep_root[i] >= P) return ZKHIP_ERR_INVALID;
-    for (size_t a = 0; a < n_airs; a++) {
-        if (airs[a].n_pvs && !pvs[a]) return ZKHIP_ERR_INVALID;
-        for (size_t i = 0; i < airs[a].n_pvs; i++)
-            if (pvs[a][i] >= P) return ZKHIP_ERR_INVALID;
+// 1. commit: every main column from S.cw[a] on (0 outside the cached form, whose partitions were committed before), AIRs in caller order
+int commit_main(const ProveIn& in, const Shape& S, MainCom* com) {
+    std::vector<const uint32_t*> cols;
+    for (size_t a = 0; a < in.n_airs; a++)
+        for (size_t c = S.cw[a]; c < in.airs[a].width; c++) cols.push_back(in.d_traces[a] + (c << in.airs[a].log_height));
+    return stack_commit(in.ctx, in.prm, cols.data(), S.lh.data(), cols.size(), in.l, &com->sc, com->root);
+}
+// observed before anything is sampled, through d_obs (obs_words() words): [the key's root (observed, not sent) | the cached roots |
+// the main root | the public values]
+size_t obs_words(const ProveIn& in, const Shape& S, size_t n_pv) { return (in.key ? 16 : 8) + S.pre + n_pv; }
+int observe_start(const ProveIn& in, const Shape& S, uint32_t* d_obs, const uint32_t* root) {
+    std::vector<uint32_t> obs;
+    if (in.key) obs.assign(in.key->root, in.key->root + 8);
+    for (size_t a : S.cached_airs) obs.insert(obs.end(), in.cached[a]->root, in.cached[a]->root + 8);
+    obs.insert(obs.end(), root, root + 8);
+    for (size_t a = 0; a < in.n_airs; a++) obs.insert(obs.end(), in.pvs[a], in.pvs[a] + in.airs[a].n_pvs);
+    ZK_TRY(zkhip_h2d(in.ctx, d_obs, obs.data(), obs.size() * 4));
+    return transcript_observe(in.ctx, in.d_t, d_obs, (uint32_t)obs.size(), true);
+}
+// The closing openings, on one transcript, in this order: the main commitment at every AIR's point, the key's at the points of the
+// AIRs that have preprocessed columns, each cached partition's at its AIR's point.  h: the read-back (the points canonical), pt_at:
+// AIR -> its point in h, head: the words before the main opening.  Then the roots and the head's words go to the proof.
+int open_and_finish(const ProveIn& in, const Shape& S, const MainCom& com, const std::vector<uint32_t>& h, const std::vector<size_t>& pt_at,
+                    size_t head) {
+    std::vector<uint32_t> points, points_p;
+    for (size_t a = 0; a < in.n_airs; a++) {
+        const auto from = h.begin() + pt_at[a], to = from + 4 * (size_t)S.plans[a].m;
+        points.insert(points.end(), from, to);
+        if (in.key && S.plans[a].wp) points_p.insert(points_p.end(), from, to);
     }
-    for (size_t i = 0; i < n_prefix; i++)
-        if (prefix[i] >= P) return ZKHIP_ERR_INVALID;
-    if (words != S.total) return ZKHIP_ERR_VERIFY;
-    for (size_t i = 0; i < S.head; i++)
-        if (proof[i] >= P) return ZKHIP_ERR_VERIFY;
-    HostChallenger ch;
-    ch.observe_canon(prefix, n_prefix);
-    if (prep_root) ch.observe_canon(prep_root, 8);
-    ch.observe_canon(proof, 8);
-    for (size_t a = 0; a < n_airs; a++) ch.observe_canon(pvs[a], airs[a].n_pvs);
+    uint32_t* out = in.proof_out;
+    size_t o = head;
+    ZK_TRY(stack_open(in.ctx, com.sc, in.d_t, points.data(), S.dims.data(), S.dims.size(), S.col_point.data(), nullptr, out + o, in.cap - o));
+    o += S.main_words;
+    if (in.key)
+        ZK_TRY(stack_open(in.ctx, in.key->sc, in.d_t, points_p.data(), S.dims_p.data(), S.dims_p.size(), S.col_point_p.data(), nullptr, out + o, in.cap - o));
+    o += S.prep_words;
+    for (size_t k = 0; k < S.cached_airs.size(); o += S.cached_words[k], k++) {
+        const size_t a = S.cached_airs[k];
+        const std::vector<unsigned> zero(S.cw[a], 0);
+        ZK_TRY(stack_open(in.ctx, in.cached[a]->sc, in.d_t, h.data() + pt_at[a], &S.dims[a], 1, zero.data(), nullptr, out + o, in.cap - o));
+        memcpy(out + 8 * k, in.cached[a]->root, 32);
+    }
+    memcpy(out + S.pre, com.root, 32);
+    memcpy(out + S.pre + 8, h.data() + S.pre + 8, (head - S.pre - 8) * 4);
+    if (in.root_out) memcpy(in.root_out, com.root, 32);
+    return ZKHIP_OK;
+}
+// either proof: with_bus, the AIR-set proof of docs/airset.md (its step numbers below); without, the zero-check of docs/zerocheck.md
+int prove(const ProveIn& in) {
+    zkhip_ctx* ctx = in.ctx;
+    const size_t n_airs = in.n_airs;
+    const zkhip_airkey* key = in.key;
+    const std::string who = key ? "airkey: " : in.with_bus ? "airset: " : "zerocheck: ";
+    Shape S;
+    if (!shape(in.prm, in.airs, n_airs, in.l, in.with_bus, &S, key ? (int)key->l_prep : -1))
+        return set_error(ctx, ZKHIP_ERR_INVALID, who + "the shape does not fit the limits");
+    if (in.cap < S.total) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, who + "proof buffer too small");
+    size_t n_pv = 0;
+    ZK_TRY(check_inputs(in, who, &n_pv));
+    std::vector<size_t> pt_at(n_airs);   // AIR -> its point r'_a, after the words before the opening
+    size_t back_words = S.head;
+    for (size_t a = 0; a < n_airs; a++) pt_at[a] = back_words, back_words += 4 * (size_t)in.airs[a].log_height;
+    MainCom com{ctx};
+    ZK_TRY(commit_main(in, S, &com));   // 1.
+    DevBufs B(ctx);
+    // device: [the words before the opening | the points r'_a (Montgomery)], then the roots and the public values to observe
+    uint32_t *dP = B.get(back_words), *d_obs = B.get(obs_words(in, S, n_pv));
+    if (!dP || !d_obs) return set_error(ctx, ZKHIP_ERR_NOMEM, who + "proof staging");
+    ZK_TRY(observe_start(in, S, d_obs, com.root));
+    // 2. - 5. the bus part
+    std::vector<ZcBus> bus(n_airs);   // E2 null: an AIR without interactions, or the zero-check
+    if (in.with_bus) ZK_TRY(prove_bus(ctx, S, in.airs, n_airs, in.d_traces, in.pvs, in.d_t, B, dP, &bus, key));
+    // 6. - 8. per AIR
+    size_t off = 8 + S.gkr_words + 4 * S.n_bus;
+    for (size_t a = 0; a < n_airs; a++) {
+        const ZcPlan& pl = S.plans[a];
+        const uint32_t *tr = in.d_traces[a], *pv = in.pvs[a];
+        uint32_t *out = dP + off, *pt = dP + pt_at[a];
+        if (key && pl.wp) {   // the kernels' PREP form, on the key's resident columns
+            const uint32_t* prep = key->d_prep + key->prep_at[a];
+            if (bus[a].E2) ZK_TRY((zc_prove_air<true, true>(ctx, in.d_t, pl, tr, pv, out, pt, bus[a], prep)));
+            else ZK_TRY((zc_prove_air<false, true>(ctx, in.d_t, pl, tr, pv, out, pt, ZcBus{}, prep)));
+        } else if (bus[a].E2) ZK_TRY(zc_prove_air<true>(ctx, in.d_t, pl, tr, pv, out, pt, bus[a]));
+        else ZK_TRY(zc_prove_air<false>(ctx, in.d_t, pl, tr, pv, out, pt));
+        off += pl.active() ? pl.words() : 0;
+    }
+    // 9. the one read-back before the openings: the words so far and the points
+    std::vector<uint32_t> h(back_words);
+    ZK_TRY(zkhip_d2h(ctx, h.data(), dP, h.size() * 4));
+    for (size_t i = S.head; i < h.size(); i++) h[i] = from_monty(h[i]);
+    return open_and_finish(in, S, com, h, pt_at, S.head);
+}
+
+// ---- the host verifier: the pieces verify() and verify_batch() share --------------------------------------------------------------
+// what a verify call was handed; prep_root: the keyed form, l_cached: the cached form (verify_batch only)
+struct VerIn {
+    const zkhip_whir_params* prm; const uint32_t* prefix; size_t n_prefix; const zkhip_air* airs; size_t n_airs; const uint32_t* const* pvs;
+    unsigned l; const uint32_t* proof; size_t words; bool with_bus; const uint32_t* prep_root; unsigned l_prep; const unsigned* l_cached;
+};
+// The checks after shape(), refusing in this order: prep_root, the public values, the prefix (ZKHIP_ERR_INVALID), the length, the
+// head's words (ZKHIP_ERR_VERIFY); then the transcript's start.  head, total: the form's words before the main opening and in all.
+int verify_start(HostChallenger& ch, const VerIn& in, const Shape& S, size_t head, size_t total) {
+    for (size_t i = 0; in.prep_root && i < 8; i++)
+        if (in.prep_root[i] >= P) return ZKHIP_ERR_INVALID;
+    for (size_t a = 0; a < in.n_airs; a++) {
+        if (in.airs[a].n_pvs && !in.pvs[a]) return ZKHIP_ERR_INVALID;
+        for (size_t i = 0; i < in.airs[a].n_pvs; i++)
+            if (in.pvs[a][i] >= P) return ZKHIP_ERR_INVALID;
+    }
+    for (size_t i = 0; i < in.n_prefix; i++)
+        if (in.prefix[i] >= P) return ZKHIP_ERR_INVALID;
+    if (in.words != total) return ZKHIP_ERR_VERIFY;
+    for (size_t i = 0; i < head; i++)
+        if (in.proof[i] >= P) return ZKHIP_ERR_VERIFY;
+    ch.observe_canon(in.prefix, in.n_prefix);
+    if (in.prep_root) ch.observe_canon(in.prep_root, 8);
+    ch.observe_canon(in.proof, S.pre + 8);   // the cached roots (none in the per-AIR form), then the main root
+    for (size_t a = 0; a < in.n_airs; a++) ch.observe_canon(in.pvs[a], in.airs[a].n_pvs);
+    return ZKHIP_OK;
+}
+// what the bus part leaves for the later steps; without a bus part it stays as constructed and nothing reads it
+struct BusV {
+    Ext gamma = ext_zero(), kappa = ext_zero();
+    std::vector<Ext> rho, eb, bpow;             // the GKR's point, e_b per block, beta^0 .. beta^LOGUP_MAX_FIELDS
+    std::vector<std::vector<size_t>> blk_of;    // AIR -> its blocks in program order
+    const uint32_t* qB = nullptr;               // the leaf claims B_a
+};
+// the bus part (docs/airset.md, steps 2 - 5), q at the fraction-sum proof's words
+int verify_bus(HostChallenger& ch, const Shape& S, const uint32_t* q, BusV* V) {
     const Ext one = ext_one();
     const size_t n_blk = S.blocks.size();
-    const uint32_t *q = proof + 8, *qB = nullptr;   // qB: the leaf claims B_a
-    Ext gamma = ext_zero(), kappa = ext_zero();
-    std::vector<Ext> rho(S.L), eb(n_blk), bpow(LOGUP_MAX_FIELDS + 1, one);
-    std::vector<std::vector<size_t>> blk_of(n_airs);   // AIR -> its blocks in program order
-    if (with_bus) {
-        // 2. - 4. gamma, beta, the fraction-sum proof: rho, (p*, q*), balance
-        gamma = ch.sample_ext();
-        const Ext beta = ch.sample_ext();
-        std::vector<uint32_t> pt(4 * (size_t)S.L);
-        uint32_t cl8[8];
-        Ext pq[2];
-        ZK_TRY(gkr_verify_host(ch, q, S.gkr_words, S.L, pt.data(), cl8, pq));
-        if (!ext_eq(pq[0], ext_zero()) || ext_eq(pq[1], ext_zero())) return ZKHIP_ERR_VERIFY;
-        for (unsigned j = 0; j < S.L; j++) rho[j] = ext_from_canon(pt.data() + 4 * j);
-        const Ext pstar = ext_from_canon(cl8), qstar = ext_from_canon(cl8 + 4);
-        // 5. the leaf claims
-        Ext pad = one;
-        for (size_t b = 0; b < n_blk; b++) {
-            const AsBlk& k = S.blocks[b];
-            Ext e = one;
-            for (unsigned t = 0; k.m + t < S.L; t++) e = ext_mul(e, ((k.off >> k.m) >> t) & 1u ? rho[k.m + t] : ext_sub(one, rho[k.m + t]));
-            eb[b] = e, pad = ext_sub(pad, e);
-        }
-        kappa = ch.sample_ext();
-        qB = q + S.gkr_words;
-        Ext lhs = ext_mul(kappa, pad);
-        for (size_t i = 0; i < S.n_bus; i++) lhs = ext_add(lhs, ext_from_canon(qB + 4 * i));
-        ch.observe_canon(qB, 4 * S.n_bus);
-        if (!ext_eq(lhs, ext_add(pstar, ext_mul(kappa, qstar)))) return ZKHIP_ERR_VERIFY;
-        q = qB + 4 * S.n_bus;
-        for (unsigned i = 1; i <= LOGUP_MAX_FIELDS; i++) bpow[i] = ext_mul(bpow[i - 1], beta);
-        for (size_t a = 0; a < n_airs; a++) blk_of[a].resize(S.plans[a].prog.ints.size());
-        for (size_t b = 0; b < n_blk; b++) blk_of[S.blocks[b].a][S.blocks[b].j] = b;
+    // 2. - 4. gamma, beta, the fraction-sum proof: rho, (p*, q*), balance
+    V->gamma = ch.sample_ext();
+    const Ext beta = ch.sample_ext();
+    std::vector<uint32_t> pt(4 * (size_t)S.L);
+    uint32_t cl8[8];
+    Ext pq[2];
+    ZK_TRY(gkr_verify_host(ch, q, S.gkr_words, S.L, pt.data(), cl8, pq));
+    if (!ext_eq(pq[0], ext_zero()) || ext_eq(pq[1], ext_zero())) return ZKHIP_ERR_VERIFY;
+    V->rho.resize(S.L);
+    for (unsigned j = 0; j < S.L; j++) V->rho[j] = ext_from_canon(pt.data() + 4 * j);
+    const Ext pstar = ext_from_canon(cl8), qstar = ext_from_canon(cl8 + 4);
+    // 5. the leaf claims: sum_a B_a + kappa (the padding's share) = p* + kappa q*
+    Ext pad = one;
+    V->eb.resize(n_blk);
+    for (size_t b = 0; b < n_blk; b++) {
+        const AsBlk& k = S.blocks[b];
+        Ext e = one;
+        for (unsigned t = 0; k.m + t < S.L; t++) e = ext_mul(e, ((k.off >> k.m) >> t) & 1u ? V->rho[k.m + t] : ext_sub(one, V->rho[k.m + t]));
+        V->eb[b] = e, pad = ext_sub(pad, e);
+    }
+    V->kappa = ch.sample_ext();
+    V->qB = q + S.gkr_words;
+    Ext lhs = ext_mul(V->kappa, pad);
+    for (size_t i = 0; i < S.n_bus; i++) lhs = ext_add(lhs, ext_from_canon(V->qB + 4 * i));
+    ch.observe_canon(V->qB, 4 * S.n_bus);
+    if (!ext_eq(lhs, ext_add(pstar, ext_mul(V->kappa, qstar)))) return ZKHIP_ERR_VERIFY;
+    V->bpow.assign(LOGUP_MAX_FIELDS + 1, one);
+    for (unsigned i = 1; i <= LOGUP_MAX_FIELDS; i++) V->bpow[i] = ext_mul(V->bpow[i - 1], beta);
+    V->blk_of.resize(S.plans.size());
+    for (size_t a = 0; a < S.plans.size(); a++) V->blk_of[a].resize(S.plans[a].prog.ints.size());
+    for (size_t b = 0; b < n_blk; b++) V->blk_of[S.blocks[b].a][S.blocks[b].j] = b;
+    return ZKHIP_OK;
+}
+// AIR a's bus claim B_a - kappa sum_j e_{a,j} (gamma + bus_j + 1), and the coefficients of its bus roots in pl.bus_roots' order:
+// per interaction +-e (its count), then kappa e beta^(i+1) (field i)
+Ext bus_claim(const Shape& S, const BusV& V, size_t a, std::vector<Ext>* coef) {
+    const ZcPlan& pl = S.plans[a];
+    Ext cst = ext_zero();
+    for (size_t j = 0; j < V.blk_of[a].size(); j++) {
+        const Interaction& it = pl.prog.ints[j];
+        const Ext e = V.eb[V.blk_of[a][j]], ke = ext_mul(V.kappa, e);
+        Ext g1 = V.gamma;
+        g1.c[0] = madd(g1.c[0], to_monty(it.bus + 1));
+        cst = ext_add(cst, ext_mul(e, g1));
+        coef->push_back(it.sign ? ext_neg(e) : e);
+        for (uint32_t i = 0; i < it.n_fields; i++) coef->push_back(ext_mul(ke, V.bpow[i + 1]));
+    }
+    return ext_sub(ext_from_canon(V.qB + 4 * S.b_at[a]), ext_mul(V.kappa, cst));
+}
+// m rounds of a sum-check of degree D from q on: a round sends s(0), s(2), .., s(D) (s(1) = claim - s(0)), is observed and answered
+// by r[i]; returns the last claim, q after the rounds
+Ext rounds_host(HostChallenger& ch, const uint32_t*& q, unsigned m, unsigned D, Ext claim, Ext* r) {
+    for (unsigned i = 0; i < m; i++, q += 4 * D) {
+        Ext s[ZKHIP_ZEROCHECK_MAX_DEGREE + 1];
+        s[0] = ext_from_canon(q), s[1] = ext_sub(claim, s[0]);
+        for (unsigned e = 1; e < D; e++) s[e + 1] = ext_from_canon(q + 4 * e);
+        ch.observe_canon(q, 4 * D);
+        r[i] = ch.sample_ext();
+        claim = poly_at(s, D, r[i]);
+    }
+    return claim;
+}
+// One AIR's summand at r[0..m), from its values [v | v' | v_p | v_p'] at q:
+//   eq(tau, r) sum_k alpha^k C_k  (if it has proven constraints)  +  eq(rho, r) sum_k coef_k root_k  (if it has bus roots)
+// parse_air: interaction operands read the current row only, so neither v' nor first / last enters the bus half
+Ext air_summand(const ZcPlan& pl, const uint32_t* q, const uint32_t* pvs, const Ext* tau, const Ext& alpha, const Ext* rho, const std::vector<Ext>& coef,
+                const Ext* r) {
+    const Ext one = ext_one();
+    const size_t w = pl.w, n_rot = pl.rot.size(), wp = pl.wp, n_rot_p = pl.rot_p.size();
+    std::vector<Ext> v(w), vn(n_rot), vp(wp), vpn(n_rot_p);
+    for (size_t j = 0; j < w; j++) v[j] = ext_from_canon(q + 4 * j);
+    for (size_t t = 0; t < n_rot; t++) vn[t] = ext_from_canon(q + 4 * (w + t));
+    for (size_t j = 0; j < wp; j++) vp[j] = ext_from_canon(q + 4 * (w + n_rot + j));
+    for (size_t t = 0; t < n_rot_p; t++) vpn[t] = ext_from_canon(q + 4 * (w + n_rot + wp + t));
+    Ext first = one, last = one, g = ext_zero();
+    for (unsigned j = 0; j < pl.m; j++) first = ext_mul(first, ext_sub(one, r[j])), last = ext_mul(last, r[j]);
+    if (!pl.proven.empty()) {
+        const std::vector<Ext> val = zc_eval_host(pl, pl.reach, v.data(), vn.data(), first, last, pvs, vp.data(), vpn.data());
+        Ext c = ext_zero(), ap = one;
+        for (uint32_t k : pl.proven) c = ext_add(c, ext_mul(ap, val[k])), ap = ext_mul(ap, alpha);
+        g = ext_mul(eq_eval(tau, r, pl.m), c);
+    }
+    if (!pl.bus_roots.empty()) {
+        const std::vector<Ext> val = zc_eval_host(pl, pl.bus_reach, v.data(), vn.data(), first, last, pvs, vp.data(), vpn.data());
+        Ext c = ext_zero();
+        for (size_t k = 0; k < coef.size(); k++) c = ext_add(c, ext_mul(coef[k], val[pl.bus_roots[k]]));
+        g = ext_add(g, ext_mul(eq_eval(rho, r, pl.m), c));
+    }
+    return g;
+}
+// the rotation reduction's start for one AIR: lp = lambda^(o + k) over its n_val values at q, from *x = lambda^o on (left at the
+// next AIR's first power); returns sum_k lp_k value_k
+Ext lambda_comb(const uint32_t* q, size_t n_val, const Ext& lambda, Ext* x, std::vector<Ext>* lp) {
+    Ext acc = ext_zero();
+    for (size_t k = 0; k < n_val; k++) lp->push_back(*x), acc = ext_add(acc, ext_mul(*x, ext_from_canon(q + 4 * k))), *x = ext_mul(*x, lambda);
+    return acc;
+}
+// the rotation reduction's end for one AIR: ua eq(r, rp) + ub rot(r, rp) from [u | u_p] at q and its lambda powers lp over
+// [v | v' | v_p | v_p']: ua takes u and u_p with v's and v_p's powers, ub the rotated columns' entries with v''s and v_p''s
+Ext u_term(const ZcPlan& pl, const Ext* lp, const uint32_t* q, const Ext* r, const Ext* rp) {
+    const size_t w = pl.w, n_rot = pl.rot.size(), wp = pl.wp;
+    const uint32_t* qp = q + 4 * w;   // u_p
+    Ext ua = ext_zero(), ub = ext_zero();
+    for (size_t j = 0; j < w; j++) ua = ext_add(ua, ext_mul(lp[j], ext_from_canon(q + 4 * j)));
+    for (size_t t = 0; t < n_rot; t++) ub = ext_add(ub, ext_mul(lp[w + t], ext_from_canon(q + 4 * pl.rot[t])));
+    for (size_t j = 0; j < wp; j++) ua = ext_add(ua, ext_mul(lp[w + n_rot + j], ext_from_canon(qp + 4 * j)));
+    for (size_t t = 0; t < pl.rot_p.size(); t++) ub = ext_add(ub, ext_mul(lp[w + n_rot + wp + t], ext_from_canon(qp + 4 * pl.rot_p[t])));
+    return ext_add(ext_mul(ua, eq_eval(r, rp, pl.m)), ext_mul(ub, zc_rot_eval(r, rp, pl.m)));
+}
+// The openings, from the proof's word `head` on: the main commitment at every AIR's point; the key's, against the verifier's own
+// root, at the points of the AIRs that have preprocessed columns (an inactive one too); each partition's, against the root the proof
+// sent, at its AIR's point.  points: canonical, AIRs end to end.  claimed[a] (null: none, an inactive AIR's values stand): AIR a's w
+// values, the first S.cw[a] the partition's, the rest the main opening's; claimed_p[a]: its w_p values in the key's opening.
+int verify_openings(HostChallenger& ch, const VerIn& in, const Shape& S, size_t head, const std::vector<uint32_t>& points,
+                    const std::vector<const uint32_t*>& claimed, const std::vector<const uint32_t*>& claimed_p) {
+    const size_t n_airs = in.n_airs;
+    const uint32_t* op = in.proof + head;
+    ZK_TRY(stack_verify_host(ch, in.prm, in.proof + S.pre, S.lh.data(), S.lh.size(), in.l, points.data(), S.dims.data(), n_airs, S.col_point.data(),
+                             op, S.main_words));
+    size_t col = 0;
+    for (size_t a = 0; a < n_airs; col += in.airs[a].width - S.cw[a], a++)
+        if (claimed[a] && memcmp(claimed[a] + 4 * S.cw[a], op + 4 * col, 16 * (in.airs[a].width - S.cw[a])) != 0) return ZKHIP_ERR_VERIFY;
+    op += S.main_words;
+    if (in.prep_root) {
+        std::vector<uint32_t> pts;
+        size_t at = 0;
+        for (size_t a = 0; a < n_airs; at += 4 * (size_t)S.plans[a].m, a++)
+            if (S.plans[a].wp) pts.insert(pts.end(), points.begin() + at, points.begin() + at + 4 * (size_t)S.plans[a].m);
+        ZK_TRY(stack_verify_host(ch, in.prm, in.prep_root, S.lh_p.data(), S.lh_p.size(), in.l_prep, pts.data(), S.dims_p.data(), S.dims_p.size(),
+                                 S.col_point_p.data(), op, S.prep_words));
+        col = 0;
+        for (size_t a = 0; a < n_airs; col += S.plans[a].wp, a++)
+            if (claimed_p[a] && memcmp(claimed_p[a], op + 4 * col, 16 * S.plans[a].wp) != 0) return ZKHIP_ERR_VERIFY;
+    }
+    op += S.prep_words;
+    size_t at = 0;
+    for (size_t a = 0, k = 0; a < n_airs; at += 4 * (size_t)S.plans[a].m, a++) {
+        if (!S.cw[a]) continue;   // every AIR outside the cached form: in.l_cached is not read
+        const std::vector<unsigned> lhc(S.cw[a], S.plans[a].m), zero(S.cw[a], 0);
+        ZK_TRY(stack_verify_host(ch, in.prm, in.proof + 8 * k, lhc.data(), lhc.size(), in.l_cached[a], points.data() + at, &S.dims[a], 1, zero.data(),
+                                 op, S.cached_words[k]));
+        if (claimed[a] && memcmp(claimed[a], op, 16 * S.cw[a]) != 0) return ZKHIP_ERR_VERIFY;
+        op += S.cached_words[k++];
+    }
+    return ZKHIP_OK;
+}
+// the host verifier of either per-AIR proof (docs/airset.md's step numbers; without with_bus docs/zerocheck.md's statement)
+// pq_out: the fraction sum's (P, Q), written whenever non-null: the callers pass null without with_bus (verify_batch tests with_bus itself)
+int verify(const VerIn& in, uint32_t* root_out, uint32_t* pq_out) {
+    const size_t n_airs = in.n_airs;
+    const uint32_t* const* pvs = in.pvs;
+    Shape S;
+    if (!shape(in.prm, in.airs, n_airs, in.l, in.with_bus, &S, in.prep_root ? (int)in.l_prep : -1)) return ZKHIP_ERR_INVALID;
+    HostChallenger ch;
+    ZK_TRY(verify_start(ch, in, S, S.head, S.total));   // 1.
+    const Ext one = ext_one();
+    BusV V;
+    const uint32_t* q = in.proof + 8;
+    if (in.with_bus) {   // 2. - 5.
+        ZK_TRY(verify_bus(ch, S, q, &V));
+        q = V.qB + 4 * S.n_bus;
     }
     std::vector<uint32_t> points;                            // r'_a, canonical, end to end
     std::vector<const uint32_t*> claimed(n_airs, nullptr);   // the w values the opening must show (null: none claimed)
     std::vector<const uint32_t*> claimed_p(n_airs, nullptr); // keyed: the w_p values the key's opening must show
     for (size_t a = 0; a < n_airs; a++) {
         const ZcPlan& pl = S.plans[a];
-        const unsigned m = pl.m, D = pl.D;
-        const size_t w = pl.w, n_rot = pl.rot.size(), wp = pl.wp, n_rot_p = pl.rot_p.size(), n_val = w + n_rot + wp + n_rot_p;
-        const bool has_cons = !pl.proven.empty(), has_bus = !pl.bus_roots.empty();   // the zero-check's plans have no bus roots
+        const unsigned m = pl.m;
+        const size_t w = pl.w, n_rot = pl.rot.size(), wp = pl.wp, n_val = w + n_rot + wp + pl.rot_p.size();
         std::vector<Ext> rp(m);
         if (!pl.active()) {
             for (unsigned j = 0; j < m; j++) rp[j] = ch.sample_ext();
         } else {
-            // 6. the (joint) sum-check
+            // 6. the (joint) sum-check: tau and alpha if it has proven constraints, the bus claim if it has bus roots (the zero-check's
+            // plans have none)
             std::vector<Ext> tau(m), r(m), coef;
             Ext alpha = ext_zero(), claim = ext_zero();
-            if (has_cons) {
+            if (!pl.proven.empty()) {
                 for (unsigned j = 0; j < m; j++) tau[j] = ch.sample_ext();
                 alpha = ch.sample_ext();
             }
-            if (has_bus) {
-                Ext cst = ext_zero();   // sum_j e_{a,j} (gamma + bus_j + 1)
-                for (size_t j = 0; j < blk_of[a].size(); j++) {
-                    const Interaction& it = pl.prog.ints[j];
-                    const Ext e = eb[blk_of[a][j]], ke = ext_mul(kappa, e);
-                    Ext g1 = gamma;
-                    g1.c[0] = madd(g1.c[0], to_monty(it.bus + 1));
-                    cst = ext_add(cst, ext_mul(e, g1));
-                    coef.push_back(it.sign ? ext_neg(e) : e);
-                    for (uint32_t i = 0; i < it.n_fields; i++) coef.push_back(ext_mul(ke, bpow[i + 1]));
-                }
-                claim = ext_sub(ext_from_canon(qB + 4 * S.b_at[a]), ext_mul(kappa, cst));
-            }
-            for (unsigned i = 0; i < m; i++, q += 4 * D) {
-                Ext s[ZKHIP_ZEROCHECK_MAX_DEGREE + 1];
-                s[0] = ext_from_canon(q), s[1] = ext_sub(claim, s[0]);
-                for (unsigned e = 1; e < D; e++) s[e + 1] = ext_from_canon(q + 4 * e);
-                ch.observe_canon(q, 4 * D);
-                r[i] = ch.sample_ext();
-                claim = poly_at(s, D, r[i]);
-            }
+            if (!pl.bus_roots.empty()) claim = bus_claim(S, V, a, &coef);
+            claim = rounds_host(ch, q, m, pl.D, claim, r.data());
             // 7. the values
-            std::vector<Ext> v(w), vn(n_rot), vp(wp), vpn(n_rot_p);   // v, v', v_p, v_p'
-            for (size_t j = 0; j < w; j++) v[j] = ext_from_canon(q + 4 * j);
-            for (size_t t = 0; t < n_rot; t++) vn[t] = ext_from_canon(q + 4 * (w + t));
-            for (size_t j = 0; j < wp; j++) vp[j] = ext_from_canon(q + 4 * (w + n_rot + j));
-            for (size_t t = 0; t < n_rot_p; t++) vpn[t] = ext_from_canon(q + 4 * (w + n_rot + wp + t));
-            ch.observe_canon(q, 4 * n_val);
             const uint32_t* qv = q;
+            ch.observe_canon(qv, 4 * n_val);
             q += 4 * n_val;
-            Ext first = one, last = one;
-            for (unsigned j = 0; j < m; j++) first = ext_mul(first, ext_sub(one, r[j])), last = ext_mul(last, r[j]);
-            Ext rhs = ext_zero();
-            if (has_cons) {   // eq(tau, r) sum_k alpha^k C_k
-                const std::vector<Ext> val = zc_eval_host(pl, pl.reach, v.data(), vn.data(), first, last, pvs[a], vp.data(), vpn.data());
-                Ext c = ext_zero(), ap = one;
-                for (uint32_t k : pl.proven) c = ext_add(c, ext_mul(ap, val[k])), ap = ext_mul(ap, alpha);
-                rhs = ext_mul(eq_eval(tau.data(), r.data(), m), c);
-            }
-            if (has_bus) {   // eq(rho_a, r) sum_j (cc_j count_j + sum_i cf_{j,i} f_{j,i}), coef in pl.bus_roots' order
-                // parse_air: interaction operands read the current row only, so neither v' nor first / last enters
-                const std::vector<Ext> val = zc_eval_host(pl, pl.bus_reach, v.data(), vn.data(), first, last, pvs[a], vp.data(), vpn.data());
-                Ext c = ext_zero();
-                for (size_t k = 0; k < coef.size(); k++) c = ext_add(c, ext_mul(coef[k], val[pl.bus_roots[k]]));
-                rhs = ext_add(rhs, ext_mul(eq_eval(rho.data(), r.data(), m), c));
-            }
-            if (!ext_eq(rhs, claim)) return ZKHIP_ERR_VERIFY;
+            if (!ext_eq(air_summand(pl, qv, pvs[a], tau.data(), alpha, V.rho.data(), coef, r.data()), claim)) return ZKHIP_ERR_VERIFY;
             // 8. the rotation reduction
             if (!pl.reduces()) {
                 rp = r, claimed[a] = qv, claimed_p[a] = wp ? qv + 4 * (w + n_rot) : nullptr;
             } else {
                 const Ext lambda = ch.sample_ext();
-                std::vector<Ext> lp(n_val);   // over [v | v' | v_p | v_p']
+                std::vector<Ext> lp;
                 Ext x = one;
-                claim = ext_zero();
-                for (size_t j = 0; j < n_val; j++) lp[j] = x, claim = ext_add(claim, ext_mul(x, ext_from_canon(qv + 4 * j))), x = ext_mul(x, lambda);
-                for (unsigned i = 0; i < m; i++, q += 8) {
-                    const Ext s0 = ext_from_canon(q), s2 = ext_from_canon(q + 4);
-                    ch.observe_canon(q, 8);
-                    rp[i] = ch.sample_ext();
-                    const Ext sv[3] = {s0, ext_sub(claim, s0), s2};
-                    claim = poly_at(sv, 2, rp[i]);
-                }
-                Ext ua = ext_zero(), ub = ext_zero();
-                for (size_t j = 0; j < w; j++) ua = ext_add(ua, ext_mul(lp[j], ext_from_canon(q + 4 * j)));
-                for (size_t t = 0; t < n_rot; t++) ub = ext_add(ub, ext_mul(lp[w + t], ext_from_canon(q + 4 * pl.rot[t])));
-                const uint32_t* qp = q + 4 * w;   // u_p
-                for (size_t j = 0; j < wp; j++) ua = ext_add(ua, ext_mul(lp[w + n_rot + j], ext_from_canon(qp + 4 * j)));
-                for (size_t t = 0; t < n_rot_p; t++) ub = ext_add(ub, ext_mul(lp[w + n_rot + wp + t], ext_from_canon(qp + 4 * pl.rot_p[t])));
+                claim = lambda_comb(qv, n_val, lambda, &x, &lp);
+                claim = rounds_host(ch, q, m, 2, claim, rp.data());
                 ch.observe_canon(q, 4 * (w + wp));
-                claimed[a] = q, claimed_p[a] = wp ? qp : nullptr, q += 4 * (w + wp);
-                const Ext want = ext_add(ext_mul(ua, eq_eval(r.data(), rp.data(), m)), ext_mul(ub, zc_rot_eval(r.data(), rp.data(), m)));
-                if (!ext_eq(want, claim)) return ZKHIP_ERR_VERIFY;
+                claimed[a] = q, claimed_p[a] = wp ? q + 4 * w : nullptr;
+                if (!ext_eq(u_term(pl, lp.data(), q, r.data(), rp.data()), claim)) return ZKHIP_ERR_VERIFY;
+                q += 4 * (w + wp);
             }
         }
         for (unsigned j = 0; j < m; j++) {
@@ -686,26 +819,11 @@ int verify(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix
             points.insert(points.end(), c4, c4 + 4);
         }
     }
-    // 9. the stacked opening
-    const uint32_t* op = proof + S.head;
-    ZK_TRY(stack_verify_host(ch, prm, proof, S.lh.data(), S.lh.size(), l, points.data(), S.dims.data(), n_airs, S.col_point.data(), op, S.main_words));
-    size_t col = 0;
-    for (size_t a = 0; a < n_airs; col += airs[a].width, a++)
-        if (claimed[a] && memcmp(claimed[a], op + 4 * col, 16 * airs[a].width) != 0) return ZKHIP_ERR_VERIFY;
-    if (prep_root) {   // the key's opening, against the verifier's own root
-        std::vector<uint32_t> pts;
-        size_t at = 0;
-        for (size_t a = 0; a < n_airs; at += 4 * (size_t)S.plans[a].m, a++)
-            if (S.plans[a].wp) pts.insert(pts.end(), points.begin() + at, points.begin() + at + 4 * (size_t)S.plans[a].m);
-        const uint32_t* op2 = op + S.main_words;
-        ZK_TRY(stack_verify_host(ch, prm, prep_root, S.lh_p.data(), S.lh_p.size(), l_prep, pts.data(), S.dims_p.data(), S.dims_p.size(),
-                                 S.col_point_p.data(), op2, words - S.head - S.main_words));
-        col = 0;
-        for (size_t a = 0; a < n_airs; col += S.plans[a].wp, a++)
-            if (claimed_p[a] && memcmp(claimed_p[a], op2 + 4 * col, 16 * S.plans[a].wp) != 0) return ZKHIP_ERR_VERIFY;
-    }
-    if (root_out) memcpy(root_out, proof, 32);
-    if (pq_out) memcpy(pq_out, proof + 8, 32);
+    // 9. the stacked opening, then the key's.  The key's opening takes S.prep_words words: once verify_start has passed the length
+    // check that is the remaining length words - S.head - S.main_words.
+    ZK_TRY(verify_openings(ch, in, S, S.head, points, claimed, claimed_p));
+    if (root_out) memcpy(root_out, in.proof, 32);
+    if (pq_out) memcpy(pq_out, in.proof + 8, 32);
     return ZKHIP_OK;
 }
 
@@ -747,231 +865,216 @@ bool batch_shape(const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_a
     return true;
 }
 
-// the device prover: one upload, one workspace, launches that do not grow with the number of AIRs
-// key: the keyed form (prm, airs and n_airs are the key's); an AIR with preprocessed columns runs the kernels' PREP form on the key's
-// resident columns, and the key's commitment is opened after the main one
-// cached (per AIR, null where the AIR has no CACHED section): the cached form (docs/cached_main.md); the main commitment holds the
-// common columns only, the handles' roots lead the transcript and the proof, and each handle is opened at its AIR's point at the end
-int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
-                const uint32_t* const* pvs, unsigned l, bool with_bus, DevTranscript* d_t, uint32_t* proof_out, size_t cap, uint32_t* root_out,
-                const zkhip_airkey* key = nullptr, zkhip_cached_main* const* cached = nullptr) {
-    const std::string who = cached ? "airkey cached: " : key ? "airkey batch: " : "airbatch: ";
-    hipStream_t st = ctx->stream;
-    BatchShape T;
-    std::vector<unsigned> l_cached;
-    for (size_t a = 0; cached && a < n_airs; a++) l_cached.push_back(cached[a] ? cached[a]->l : 0);
-    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T, key ? (int)key->l_prep : -1, cached ? l_cached.data() : nullptr))
-        return set_error(ctx, ZKHIP_ERR_INVALID, who + "the shape does not fit the limits");
+// ---- the batched device prover: one upload, one workspace, launches that do not grow with the number of AIRs --------------------
+// One job (an active AIR): its lowered program and its footprint in the workspace.  batch_plan() places every piece at the running
+// total and moves the total on: each size is written there once, so the workspace's size and the pieces' places cannot disagree.
+struct ZbSlot {
+    size_t a = 0;
+    CompiledAir ca;                // roots: the proven constraints, then (with_bus) the bus roots
+    bool has_bus = false;
+    size_t up_at = 0;              // in the upload: [code | the extension passes' copy | consts | pvs | rot | rot_p], padded to 4 words
+    size_t partial = 0, tA = 0, tB = 0;   // among the tables (words from o_tabs): 4 D SC_NB; nt tables of n / 2; nt of max(n / 4, 1)
+    size_t red = 0;                // a reducing AIR: [F_a (4 n) | F_b (4 n) | partial (8 SC_NB)], after its tables
+    uint32_t first_wg = 0, n_wg = 0;      // its workgroups, counted from its class's first job
+};
+struct ZbCls {   // a (D, BUS, PREP) class: a run of the job table, tallest first
+    size_t lo, n;
+    unsigned D, slots;
+    bool bus, prep;
+};
+struct BatchPlan {
+    std::vector<ZbSlot> slots;   // class order
+    std::vector<ZbCls> classes;
+    std::map<unsigned, size_t> eq_at;   // height of an AIR with proven constraints -> its eq table (words from d_ws)
+    size_t n_cons_max = 1, n_cst = 0, n_ucols = 0, red_vals = 0, inact_words = 0;
+    // the workspace (words from d_ws): [upload: the jobs' slices | lagx | lagw | ZbJob, ZbCst, ZbRot, ZbCol tables] [tau, alpha, mu,
+    // lambda | alpha powers | lambda powers | weights | claims | states | eq tables | the jobs' tables]
+    size_t o_lagx = 0, o_lagw = 0, o_job = 0, o_cst = 0, o_rot = 0, o_col = 0, up_total = 0;
+    size_t o_chal = 0, o_apow = 0, o_lpow = 0, o_wgt = 0, o_claim = 0, o_state = 0, o_tabs = 0, ws_words = 0;
+    // read back at once (words from dP): [the words before the opening | r (4 M) | r' (4 M') | the inactive AIRs' points]
+    size_t o_r = 0, o_rp = 0, o_inact = 0, back_words = 0;
+};
+size_t pad4(size_t x) { return (x + 3) & ~(size_t)3; }
+// the plan: the classes, the lowered programs, the layout
+int batch_plan(zkhip_ctx* ctx, const std::string& who, const BatchShape& T, bool with_bus, BatchPlan* Q) {
     const Shape& S = T.S;
-    for (size_t a : S.cached_airs) {
-        const zkhip_cached_main* c = cached[a];
-        if (!c || !c->sc || c->air != a || c->m != S.plans[a].m || c->cw != S.cw[a] || memcmp(&c->params, prm, sizeof(*prm)) != 0)
-            return set_error(ctx, ZKHIP_ERR_INVALID, who + "a cached partition's handle is null or was made for another AIR, height or width");
-    }
-    const size_t pre = S.pre;
-    if (cap < T.total) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, who + "proof buffer too small");
-    size_t n_pv = 0, inact_words = 0;
-    for (size_t a = 0; a < n_airs; a++) {
-        if (!d_traces[a] || (airs[a].n_pvs && !pvs[a])) return set_error(ctx, ZKHIP_ERR_INVALID, who + "null trace or public values");
-        for (size_t i = 0; i < airs[a].n_pvs; i++)
-            if (pvs[a][i] >= P) return set_error(ctx, ZKHIP_ERR_INVALID, who + "public value not canonical");
-        n_pv += airs[a].n_pvs;
-        if (!S.plans[a].active()) inact_words += 4 * (size_t)S.plans[a].m;
-    }
-    const unsigned M = T.M, D = T.D, M2 = T.M2;
     const size_t n_jobs = T.act.size(), n_red = T.red.size();
-    // the jobs: a (D, BUS, PREP) class is a run of the table, tallest first; the lowered programs
     std::vector<size_t> order(T.act);
     auto cls = [&](size_t a) { return 4 * S.plans[a].D + (with_bus && !S.plans[a].prog.ints.empty() ? 2u : 0u) + (S.plans[a].wp ? 1u : 0u); };
     std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return cls(x) != cls(y) ? cls(x) < cls(y) : S.plans[x].m > S.plans[y].m; });
-    std::vector<CompiledAir> ca(n_jobs);
-    size_t n_cons_max = 1, up_words = 0, tab_words = 0, n_cst = 0, n_ucols = 0, red_vals = 0;
-    auto pad4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    Q->slots.resize(n_jobs);
+    size_t up_words = 0, tab_words = 0;
+    auto take = [](size_t& at, size_t n) { return (at += n) - n; };   // n words at the running total
+    uint64_t wg = 0;
     for (size_t k = 0; k < n_jobs; k++) {
-        const ZcPlan& pl = S.plans[order[k]];
+        ZbSlot& J = Q->slots[k];
+        const ZcPlan& pl = S.plans[J.a = order[k]];
+        J.has_bus = with_bus && !pl.prog.ints.empty();
         std::vector<uint32_t> roots = pl.proven;
         if (with_bus) roots.insert(roots.end(), pl.bus_roots.begin(), pl.bus_roots.end());
         std::string err;
-        if (compile_air(pl.prog, &ca[k], &err, &roots) != 0 || ca[k].n_slots > ZC_MAX_SLOTS)
+        if (compile_air(pl.prog, &J.ca, &err, &roots) != 0 || J.ca.n_slots > ZC_MAX_SLOTS)
             return set_error(ctx, ZKHIP_ERR_INVALID, who + (err.empty() ? "an AIR needs more than 64 live intermediates" : err));
-        n_cons_max = std::max(n_cons_max, pl.proven.size());
-        const size_t n_val = pl.w + pl.rot.size() + pl.wp + pl.rot_p.size();   // [v | v' | v_p | v_p']: wp = 0 and rot_p empty without a key
-        up_words += pad4(2 * ca[k].code.size() + ca[k].consts.size() + pl.prog.n_pvs + pl.rot.size() + pl.rot_p.size());
-        const size_t n = (size_t)1 << pl.m, nt = n_val + (with_bus && !pl.prog.ints.empty() ? 4 : 3);
-        tab_words += 4 * (size_t)pl.D * SC_NB + 4 * nt * (n / 2) + 4 * nt * std::max<size_t>(n / 4, 1);
-        if (pl.reduces()) tab_words += 8 * n + 8 * SC_NB, n_ucols += pl.w + pl.wp, red_vals += n_val;
-        if (with_bus) n_cst += pl.prog.ints.size();
+        if (Q->classes.empty() || cls(order[Q->classes.back().lo]) != cls(J.a)) Q->classes.push_back({k, 0, pl.D, 1, J.has_bus, pl.wp != 0}), wg = 0;
+        Q->classes.back().n++, Q->classes.back().slots = std::max(Q->classes.back().slots, J.ca.n_slots);
+        const size_t n = (size_t)1 << pl.m, n_val = pl.w + pl.rot.size() + pl.wp + pl.rot_p.size();   // wp = 0, rot_p empty without a key
+        const size_t nt = n_val + (J.has_bus ? 4 : 3);
+        J.first_wg = (uint32_t)wg, J.n_wg = grid_w(n / 2), wg += J.n_wg;
+        J.up_at = take(up_words, pad4(2 * J.ca.code.size() + J.ca.consts.size() + pl.prog.n_pvs + pl.rot.size() + pl.rot_p.size()));
+        J.partial = take(tab_words, 4 * (size_t)pl.D * SC_NB);
+        J.tA = take(tab_words, 4 * nt * (n / 2));
+        J.tB = take(tab_words, 4 * nt * std::max<size_t>(n / 4, 1));
+        if (pl.reduces()) J.red = take(tab_words, 8 * n + 8 * SC_NB), Q->n_ucols += pl.w + pl.wp, Q->red_vals += n_val;
+        Q->n_cons_max = std::max(Q->n_cons_max, pl.proven.size());
+        if (J.has_bus) Q->n_cst += pl.prog.ints.size();
     }
-    std::map<unsigned, size_t> eq_at;   // height of an AIR with proven constraints -> its eq table (words from d_ws)
-    // the workspace, laid out once: [upload | challenges | powers | weights, claims, states | eq tables | per job: partial, tA, tB (, F_a, F_b, partial)]
-    const size_t o_lagx = up_words, o_lagw = o_lagx + pad4(ZB_PTS * ZB_PTS * ZB_PTS), o_structs = o_lagw + pad4(ZB_PTS);
-    const size_t job_w = pad4(n_jobs * sizeof(ZbJob) / 4 + 1), cst_w = pad4(n_cst * sizeof(ZbCst) / 4 + 1), rot_w = pad4(n_red * sizeof(ZbRot) / 4 + 1),
-                 col_w = pad4(n_ucols * sizeof(ZbCol) / 4 + 1);
-    const size_t o_job = o_structs, o_cst = o_job + job_w, o_rot = o_cst + cst_w, o_col = o_rot + rot_w, up_total = o_col + col_w;
-    const size_t o_chal = up_total, o_apow = o_chal + 4 * (size_t)M + 12, o_lpow = o_apow + 4 * n_cons_max, o_wgt = o_lpow + 4 * std::max<size_t>(red_vals, 1),
-                 o_claim = o_wgt + 4 * std::max<size_t>(n_jobs, 1), o_state = o_claim + 4 * std::max<size_t>(n_jobs, 1);
-    size_t o_end = o_state + 4 * std::max<size_t>(n_red, 1);
+    size_t at = up_words;   // the rest of the upload, then what the device alone writes
+    Q->o_lagx = take(at, pad4(ZB_PTS * ZB_PTS * ZB_PTS)), Q->o_lagw = take(at, pad4(ZB_PTS));
+    Q->o_job = take(at, pad4(n_jobs * sizeof(ZbJob) / 4 + 1)), Q->o_cst = take(at, pad4(Q->n_cst * sizeof(ZbCst) / 4 + 1));
+    Q->o_rot = take(at, pad4(n_red * sizeof(ZbRot) / 4 + 1)), Q->o_col = take(at, pad4(Q->n_ucols * sizeof(ZbCol) / 4 + 1));
+    Q->up_total = at;
+    Q->o_chal = take(at, 4 * (size_t)T.M + 12), Q->o_apow = take(at, 4 * Q->n_cons_max), Q->o_lpow = take(at, 4 * std::max<size_t>(Q->red_vals, 1));
+    Q->o_wgt = take(at, 4 * std::max<size_t>(n_jobs, 1)), Q->o_claim = take(at, 4 * std::max<size_t>(n_jobs, 1));
+    Q->o_state = take(at, 4 * std::max<size_t>(n_red, 1));
     for (size_t a : T.act)
-        if (!S.plans[a].proven.empty() && !eq_at.count(S.plans[a].m)) eq_at[S.plans[a].m] = o_end, o_end += 4 * ((size_t)1 << S.plans[a].m);
-    const size_t o_tabs = o_end, ws_words = o_tabs + tab_words;
-    // 1. commit: every main column, AIRs in caller order (the cached form: the common columns; the partitions were committed before)
-    std::vector<const uint32_t*> cols;
-    for (size_t a = 0; a < n_airs; a++)
-        for (size_t c = S.cw[a]; c < airs[a].width; c++) cols.push_back(d_traces[a] + (c << airs[a].log_height));
-    struct Com {
-        zkhip_ctx* ctx;
-        zkhip_stack_commitment* sc = nullptr;
-        ~Com() { stack_destroy(ctx, sc); }
-    } com{ctx};
-    uint32_t root[8];
-    ZK_TRY(stack_commit(ctx, prm, cols.data(), S.lh.data(), cols.size(), l, &com.sc, root));
-    DevBufs B(ctx);
-    // device: [the words before the opening | r (4 M) | r' (4 M') | the inactive AIRs' points], all read back at once
-    const size_t o_r = T.head, o_rp = o_r + 4 * (size_t)M, o_inact = o_rp + 4 * (size_t)M2, back_words = o_inact + inact_words;
-    uint32_t *dP = B.get(back_words), *d_obs = B.get((key ? 16 : 8) + pre + n_pv), *d_ws = B.get(ws_words);
-    if (!dP || !d_obs || !d_ws) return set_error(ctx, ZKHIP_ERR_NOMEM, who + "the workspace does not fit");
-    std::vector<uint32_t> obs;
-    if (key) obs.assign(key->root, key->root + 8);   // the key's root is observed, not sent
-    for (size_t a : S.cached_airs) obs.insert(obs.end(), cached[a]->root, cached[a]->root + 8);   // cached..., common
-    obs.insert(obs.end(), root, root + 8);
-    for (size_t a = 0; a < n_airs; a++) obs.insert(obs.end(), pvs[a], pvs[a] + airs[a].n_pvs);
-    ZK_TRY(zkhip_h2d(ctx, d_obs, obs.data(), obs.size() * 4));
-    ZK_TRY(transcript_observe(ctx, d_t, d_obs, (uint32_t)obs.size(), true));
-    // 2. - 5. the bus part
-    std::vector<ZcBus> bus(n_airs);
-    const uint32_t* chal = nullptr;
-    if (with_bus) ZK_TRY(prove_bus(ctx, S, airs, n_airs, d_traces, pvs, d_t, B, dP + pre, &bus, key, &chal));
-    // the one upload: programs, constants, public values, rotation lists, the interpolation weights, the job tables
-    std::vector<uint32_t> up(up_total, 0);
-    std::vector<ZbJob> jobs(n_jobs);
+        if (!S.plans[a].proven.empty() && !Q->eq_at.count(S.plans[a].m)) Q->eq_at[S.plans[a].m] = take(at, 4 * ((size_t)1 << S.plans[a].m));
+    Q->o_tabs = at, Q->ws_words = at + tab_words;
+    at = T.head;   // the read-back
+    Q->o_r = take(at, 4 * (size_t)T.M), Q->o_rp = take(at, 4 * (size_t)T.M2), Q->o_inact = at;
+    for (const ZcPlan& pl : S.plans)
+        if (!pl.active()) at += 4 * (size_t)pl.m;
+    Q->inact_words = at - Q->o_inact, Q->back_words = at;
+    return ZKHIP_OK;
+}
+// s(t), t > d, from s(0..d) at lagx; and 1 / prod_{i != t} (t - i) over 0..D at lagw
+void zb_lagrange(uint32_t* lagx, uint32_t* lagw, unsigned D) {
+    auto small = [](unsigned x) { return to_monty(x); };
+    for (unsigned d = 1; d < ZB_PTS; d++)
+        for (unsigned t = d + 1; t < ZB_PTS; t++)
+            for (unsigned j = 0; j <= d; j++) {
+                uint32_t num = MONTY_ONE, den = MONTY_ONE;
+                for (unsigned i = 0; i <= d; i++)
+                    if (i != j) num = mmul(num, msub(small(t), small(i))), den = mmul(den, msub(small(j), small(i)));
+                lagx[(d * ZB_PTS + t) * ZB_PTS + j] = mmul(num, minv(den));
+            }
+    for (unsigned t = 0; t <= D; t++) {
+        uint32_t den = MONTY_ONE;
+        for (unsigned i = 0; i <= D; i++)
+            if (i != t) den = mmul(den, msub(small(t), small(i)));
+        lagw[t] = minv(den);
+    }
+}
+// the one upload: programs, constants, public values, rotation lists, the interpolation weights, the job tables; jobs: the host's
+// copy of the job table, class order (the round loop reads heights and grids from it)
+void batch_fill(const ProveIn& in, const BatchShape& T, const BatchPlan& Q, const std::vector<ZcBus>& bus, uint32_t* d_ws, std::vector<uint32_t>* up,
+                std::vector<ZbJob>* jobs) {
+    const Shape& S = T.S;
+    const uint32_t *const *d_traces = in.d_traces, *const *pvs = in.pvs;
+    const zkhip_airkey* key = in.key;
+    const size_t n_airs = S.plans.size(), n_jobs = Q.slots.size();
+    up->assign(Q.up_total, 0);
+    jobs->assign(n_jobs, ZbJob{});
     std::vector<ZbCst> cst;
-    std::vector<ZbRot> rots(n_red);
+    std::vector<ZbRot> rots(T.red.size());
     std::vector<ZbCol> ucols;
-    std::vector<size_t> val_at(n_airs, 0), u_at(n_airs, 0), lam_at(n_airs, 0), job_of(n_airs, 0);
-    {
-        size_t v = 0, u = 0, o = 0;
-        for (size_t a : T.act) {
-            const ZcPlan& pl = S.plans[a];
-            const size_t n_val = pl.w + pl.rot.size() + pl.wp + pl.rot_p.size();
-            val_at[a] = v, v += 4 * n_val;
-            if (pl.reduces()) u_at[a] = u, u += 4 * (pl.w + pl.wp), lam_at[a] = o, o += n_val;
+    std::vector<size_t> val_at(n_airs, 0), u_at(n_airs, 0), lam_at(n_airs, 0);   // caller order: the proof's value and u sections, the lambda powers
+    size_t v = 0, u = 0, o = 0;
+    for (size_t a : T.act) {
+        const ZcPlan& pl = S.plans[a];
+        const size_t n_val = pl.w + pl.rot.size() + pl.wp + pl.rot_p.size();
+        val_at[a] = v, v += 4 * n_val;
+        if (pl.reduces()) u_at[a] = u, u += 4 * (pl.w + pl.wp), lam_at[a] = o, o += n_val;
+    }
+    auto eq_of = [&](unsigned m) { return d_ws + Q.eq_at.at(m); };   // of an AIR with proven constraints: batch_plan gave its height a table
+    uint32_t* tabs = d_ws + Q.o_tabs;
+    for (size_t k = 0; k < n_jobs; k++) {
+        const ZbSlot& J = Q.slots[k];
+        const size_t a = J.a;
+        const ZcPlan& pl = S.plans[a];
+        const unsigned w = (unsigned)pl.w, n_rot = (unsigned)pl.rot.size(), wp = (unsigned)pl.wp, n_rot_p = (unsigned)pl.rot_p.size();
+        const size_t n_code = J.ca.code.size(), n_ins = n_code / 3, n = (size_t)1 << pl.m;
+        uint32_t* h = up->data() + J.up_at;
+        std::copy(J.ca.code.begin(), J.ca.code.end(), h);
+        for (size_t i = 0; i < n_ins; i++) {   // the extension passes' copy names tables in its VAR operands (zc_prove_air's remap)
+            uint32_t* x = h + n_code + 3 * i;
+            x[0] = J.ca.code[3 * i];
+            for (int q = 1; q < 3; q++) {
+                const uint32_t op = J.ca.code[3 * i + q];
+                x[q] = (op >> 28) != K_VAR ? op : (K_VAR << 28) | (((op >> 27) & 1u) ? w + (uint32_t)pl.rot_of[op & 0x07ffffffu] : (op & 0x07ffffffu));
+                if (wp && (op >> 28) == K_PREP)   // the preprocessed tables follow the main ones
+                    x[q] = (K_VAR << 28) | (w + n_rot + (((op >> 27) & 1u) ? wp + (uint32_t)pl.rot_p_of[op & 0x07ffffffu] : (op & 0x07ffffffu)));
+            }
+        }
+        uint32_t* hp = h + 2 * n_code;
+        hp = std::copy(J.ca.consts.begin(), J.ca.consts.end(), hp);
+        for (uint32_t i = 0; i < pl.prog.n_pvs; i++) *hp++ = to_monty(pvs[a][i]);
+        hp = std::copy(pl.rot.begin(), pl.rot.end(), hp);
+        std::copy(pl.rot_p.begin(), pl.rot_p.end(), hp);
+        const uint32_t* d = d_ws + J.up_at;
+        ZbJob& jb = (*jobs)[k];
+        jb.pg = ZcProg{d, (unsigned)n_ins, d + 2 * n_code, d + 2 * n_code + J.ca.consts.size(), d_ws + Q.o_apow, bus[a].coef, (unsigned)pl.proven.size()};
+        jb.xcode = d + n_code, jb.trace = d_traces[a], jb.rot = d + 2 * n_code + J.ca.consts.size() + pl.prog.n_pvs;
+        if (wp) jb.pp = ZcPrep{key->d_prep + key->prep_at[a], jb.rot + n_rot, wp, n_rot_p};   // the key's columns of this AIR
+        jb.E2 = bus[a].E2, jb.E = pl.proven.empty() ? bus[a].E2 : eq_of(pl.m);
+        jb.partial = tabs + J.partial, jb.tA = tabs + J.tA, jb.tB = tabs + J.tB;
+        jb.m = pl.m, jb.w = w, jb.n_rot = n_rot, jb.D = pl.D;
+        jb.j = (uint32_t)(std::find(T.act.begin(), T.act.end(), a) - T.act.begin());
+        jb.first_wg = J.first_wg, jb.n_wg = J.n_wg;
+        jb.val_at = (uint32_t)val_at[a];
+        if (J.has_bus) {
+            jb.cst_at = (uint32_t)cst.size(), jb.cst_n = (uint32_t)pl.prog.ints.size(), jb.b_at = (uint32_t)S.b_at[a];
+            uint32_t root_at = 0;   // pl.bus_roots: per interaction its count, then its fields
+            for (const Interaction& it : pl.prog.ints) cst.push_back({root_at, to_monty(it.bus + 1), it.sign}), root_at += 1 + it.n_fields;
+        }
+        if (pl.reduces()) {
+            ZbRot& rj = rots[std::find(T.red.begin(), T.red.end(), a) - T.red.begin()];
+            rj = ZbRot{};
+            rj.trace = d_traces[a], rj.rot = jb.rot, rj.lpow = d_ws + Q.o_lpow + 4 * lam_at[a], rj.E = eq_of(pl.m);
+            rj.fa = tabs + J.red, rj.fb = rj.fa + 4 * n, rj.partial = rj.fb + 4 * n;   // ZbSlot::red's layout
+            rj.tA = jb.tA, rj.tB = jb.tB, rj.m = pl.m, rj.w = w, rj.n_rot = n_rot, rj.pp = jb.pp;
+            rj.wgt = mpow(to_monty(2), T.M2 - pl.m), rj.u_at = (uint32_t)u_at[a];
         }
     }
-    uint32_t *tau = d_ws + o_chal, *alpha = tau + 4 * M, *mu = alpha + 4, *lambda = mu + 4;
-    uint32_t *d_r = dP + o_r, *d_rp = dP + o_rp;
-    struct Cls {
-        size_t lo, n;
-        unsigned D, slots;
-        bool bus, prep;
-    };
-    std::vector<Cls> classes;
-    {
-        size_t at = 0, tabs = o_tabs;
-        uint64_t wg = 0;
-        for (size_t k = 0; k < n_jobs; k++) {
-            const size_t a = order[k];
-            const ZcPlan& pl = S.plans[a];
-            const bool has_bus = with_bus && !pl.prog.ints.empty();
-            const unsigned w = (unsigned)pl.w, n_rot = (unsigned)pl.rot.size(), wp = (unsigned)pl.wp, n_rot_p = (unsigned)pl.rot_p.size();
-            if (classes.empty() || cls(order[classes.back().lo]) != cls(a)) classes.push_back({k, 0, pl.D, 1, has_bus, wp != 0}), wg = 0;
-            classes.back().n++, classes.back().slots = std::max(classes.back().slots, ca[k].n_slots);
-            const size_t n_code = ca[k].code.size(), n_ins = n_code / 3;
-            uint32_t* h = up.data() + at;
-            std::copy(ca[k].code.begin(), ca[k].code.end(), h);
-            for (size_t i = 0; i < n_ins; i++) {   // the extension passes' copy names tables in its VAR operands (zc_prove_air's remap)
-                uint32_t* x = h + n_code + 3 * i;
-                x[0] = ca[k].code[3 * i];
-                for (int q = 1; q < 3; q++) {
-                    const uint32_t o = ca[k].code[3 * i + q];
-                    x[q] = (o >> 28) != K_VAR ? o : (K_VAR << 28) | (((o >> 27) & 1u) ? w + (uint32_t)pl.rot_of[o & 0x07ffffffu] : (o & 0x07ffffffu));
-                    if (wp && (o >> 28) == K_PREP)   // the preprocessed tables follow the main ones
-                        x[q] = (K_VAR << 28) | (w + n_rot + (((o >> 27) & 1u) ? wp + (uint32_t)pl.rot_p_of[o & 0x07ffffffu] : (o & 0x07ffffffu)));
-                }
-            }
-            uint32_t* hp = h + 2 * n_code;
-            hp = std::copy(ca[k].consts.begin(), ca[k].consts.end(), hp);
-            for (uint32_t i = 0; i < pl.prog.n_pvs; i++) *hp++ = to_monty(pvs[a][i]);
-            hp = std::copy(pl.rot.begin(), pl.rot.end(), hp);
-            std::copy(pl.rot_p.begin(), pl.rot_p.end(), hp);
-            const uint32_t* d = d_ws + at;
-            const size_t n = (size_t)1 << pl.m, nt = w + n_rot + wp + n_rot_p + (has_bus ? 4 : 3);
-            ZbJob& jb = jobs[k];
-            jb = ZbJob{};
-            jb.pg = ZcProg{d, (unsigned)n_ins, d + 2 * n_code, d + 2 * n_code + ca[k].consts.size(), d_ws + o_apow, bus[a].coef, (unsigned)pl.proven.size()};
-            jb.xcode = d + n_code, jb.trace = d_traces[a], jb.rot = d + 2 * n_code + ca[k].consts.size() + pl.prog.n_pvs;
-            if (wp) jb.pp = ZcPrep{key->d_prep + key->prep_at[a], jb.rot + n_rot, wp, n_rot_p};   // the key's columns of this AIR
-            jb.E2 = bus[a].E2, jb.E = pl.proven.empty() ? bus[a].E2 : d_ws + eq_at[pl.m];
-            jb.partial = d_ws + tabs, tabs += 4 * (size_t)pl.D * SC_NB;
-            jb.tA = d_ws + tabs, tabs += 4 * nt * (n / 2);
-            jb.tB = d_ws + tabs, tabs += 4 * nt * std::max<size_t>(n / 4, 1);
-            jb.m = pl.m, jb.w = w, jb.n_rot = n_rot, jb.D = pl.D;
-            jb.j = (uint32_t)(std::find(T.act.begin(), T.act.end(), a) - T.act.begin());
-            jb.first_wg = (uint32_t)wg, jb.n_wg = grid_w(n / 2), wg += jb.n_wg;
-            jb.val_at = (uint32_t)val_at[a];
-            if (has_bus) {
-                jb.cst_at = (uint32_t)cst.size(), jb.cst_n = (uint32_t)pl.prog.ints.size(), jb.b_at = (uint32_t)S.b_at[a];
-                uint32_t root_at = 0;   // pl.bus_roots: per interaction its count, then its fields
-                for (const Interaction& it : pl.prog.ints) cst.push_back({root_at, to_monty(it.bus + 1), it.sign}), root_at += 1 + it.n_fields;
-            }
-            job_of[a] = k;
-            at += pad4(2 * n_code + ca[k].consts.size() + pl.prog.n_pvs + n_rot + n_rot_p);
-            if (pl.reduces()) {   // its reduction buffers follow its tables
-                ZbRot& rj = rots[std::find(T.red.begin(), T.red.end(), a) - T.red.begin()];
-                rj = ZbRot{};
-                rj.trace = d_traces[a], rj.rot = jb.rot, rj.lpow = d_ws + o_lpow + 4 * lam_at[a], rj.E = d_ws + eq_at[pl.m];
-                rj.fa = d_ws + tabs, rj.fb = rj.fa + 4 * n, tabs += 8 * n;
-                rj.partial = d_ws + tabs, tabs += 8 * SC_NB;
-                rj.tA = jb.tA, rj.tB = jb.tB, rj.m = pl.m, rj.w = w, rj.n_rot = n_rot, rj.pp = jb.pp;
-                rj.wgt = mpow(to_monty(2), M2 - pl.m), rj.u_at = (uint32_t)u_at[a];
-            }
-        }
-        for (size_t a : T.red) {   // u, then u_p from the key's columns
-            const ZcPlan& pl = S.plans[a];
-            for (size_t c = 0; c < pl.w; c++) ucols.push_back({d_traces[a] + (c << pl.m), d_ws + eq_at[pl.m], pl.m, (uint32_t)(u_at[a] + 4 * c)});
-            for (size_t c = 0; c < pl.wp; c++)
-                ucols.push_back({key->d_prep + key->prep_at[a] + (c << pl.m), d_ws + eq_at[pl.m], pl.m, (uint32_t)(u_at[a] + 4 * (pl.w + c))});
-        }
-        // s(t), t > d, from s(0..d); and 1 / prod_{i != t} (t - i) over 0..D
-        auto small = [](unsigned x) { return to_monty(x); };
-        for (unsigned d = 1; d < ZB_PTS; d++)
-            for (unsigned t = d + 1; t < ZB_PTS; t++)
-                for (unsigned j = 0; j <= d; j++) {
-                    uint32_t num = MONTY_ONE, den = MONTY_ONE;
-                    for (unsigned i = 0; i <= d; i++)
-                        if (i != j) num = mmul(num, msub(small(t), small(i))), den = mmul(den, msub(small(j), small(i)));
-                    up[o_lagx + (d * ZB_PTS + t) * ZB_PTS + j] = mmul(num, minv(den));
-                }
-        for (unsigned t = 0; t <= D; t++) {
-            uint32_t den = MONTY_ONE;
-            for (unsigned i = 0; i <= D; i++)
-                if (i != t) den = mmul(den, msub(small(t), small(i)));
-            up[o_lagw + t] = minv(den);
-        }
-        if (n_jobs) memcpy(up.data() + o_job, jobs.data(), n_jobs * sizeof(ZbJob));
-        if (!cst.empty()) memcpy(up.data() + o_cst, cst.data(), cst.size() * sizeof(ZbCst));
-        if (n_red) memcpy(up.data() + o_rot, rots.data(), n_red * sizeof(ZbRot));
-        if (!ucols.empty()) memcpy(up.data() + o_col, ucols.data(), ucols.size() * sizeof(ZbCol));
+    for (size_t a : T.red) {   // u, then u_p from the key's columns
+        const ZcPlan& pl = S.plans[a];
+        for (size_t c = 0; c < pl.w; c++) ucols.push_back({d_traces[a] + (c << pl.m), eq_of(pl.m), pl.m, (uint32_t)(u_at[a] + 4 * c)});
+        for (size_t c = 0; c < pl.wp; c++)
+            ucols.push_back({key->d_prep + key->prep_at[a] + (c << pl.m), eq_of(pl.m), pl.m, (uint32_t)(u_at[a] + 4 * (pl.w + c))});
     }
-    ZK_TRY(zkhip_h2d(ctx, d_ws, up.data(), up.size() * 4));
-    const ZbJob* d_jobs = (const ZbJob*)(d_ws + o_job);
-    const ZbRot* d_rots = (const ZbRot*)(d_ws + o_rot);
-    // 6. the batched sum-check: tau and alpha (if some AIR has proven constraints), then mu
+    zb_lagrange(up->data() + Q.o_lagx, up->data() + Q.o_lagw, T.D);
+    if (n_jobs) memcpy(up->data() + Q.o_job, jobs->data(), n_jobs * sizeof(ZbJob));
+    if (!cst.empty()) memcpy(up->data() + Q.o_cst, cst.data(), cst.size() * sizeof(ZbCst));
+    if (!rots.empty()) memcpy(up->data() + Q.o_rot, rots.data(), rots.size() * sizeof(ZbRot));
+    if (!ucols.empty()) memcpy(up->data() + Q.o_col, ucols.data(), ucols.size() * sizeof(ZbCol));
+}
+// 6. the batched sum-check: tau and alpha (if some AIR has proven constraints), then mu; M rounds and the tallest AIRs' last fold
+// 7. the values of every active AIR at its prefix of r
+// chal: prove_bus's [gamma | beta | kappa] (null without with_bus)
+int batch_rounds(const ProveIn& in, const BatchShape& T, const BatchPlan& Q, const std::vector<ZbJob>& jobs, uint32_t* d_ws, uint32_t* dP,
+                 const uint32_t* chal) {
+    zkhip_ctx* ctx = in.ctx;
+    DevTranscript* d_t = in.d_t;
+    hipStream_t st = ctx->stream;
+    const unsigned M = T.M;
+    const size_t n_jobs = jobs.size();
+    uint32_t *tau = d_ws + Q.o_chal, *alpha = tau + 4 * M, *mu = alpha + 4, *d_r = dP + Q.o_r;
+    const ZbJob* d_jobs = (const ZbJob*)(d_ws + Q.o_job);
     if (T.any_cons) ZK_TRY(transcript_sample(ctx, d_t, tau, nullptr, 4 * M + 8));
     else ZK_TRY(transcript_sample(ctx, d_t, mu, nullptr, 4));
-    for (auto& e : eq_at) {
+    for (auto& e : Q.eq_at) {
         KernelScope ks(ctx, "zb_eq");
         whir_eq_launch(st, d_ws + e.second, e.first, tau);
     }
     if (T.any_cons) {
         KernelScope ks(ctx, "zb_pows");
-        hipLaunchKernelGGL(k_zc_pows, dim3(1), dim3(256), 0, st, (const uint32_t*)alpha, (unsigned)n_cons_max, d_ws + o_apow);
+        hipLaunchKernelGGL(k_zc_pows, dim3(1), dim3(256), 0, st, (const uint32_t*)alpha, (unsigned)Q.n_cons_max, d_ws + Q.o_apow);
     }
     ZK_HIP_CHECK(ctx, hipGetLastError());
     ZbTr ztr{};
-    ztr.mu = mu, ztr.lagx = d_ws + o_lagx, ztr.lagw = d_ws + o_lagw, ztr.cst = (const ZbCst*)(d_ws + o_cst), ztr.chal = chal;
-    ztr.dB = dP + pre + 8 + S.gkr_words, ztr.wgt = d_ws + o_wgt, ztr.claim = d_ws + o_claim, ztr.proof = dP + T.o_rounds, ztr.r = d_r;
+    ztr.mu = mu, ztr.lagx = d_ws + Q.o_lagx, ztr.lagw = d_ws + Q.o_lagw, ztr.cst = (const ZbCst*)(d_ws + Q.o_cst), ztr.chal = chal;
+    ztr.dB = dP + T.S.pre + 8 + T.S.gkr_words, ztr.wgt = d_ws + Q.o_wgt, ztr.claim = d_ws + Q.o_claim, ztr.proof = dP + T.o_rounds, ztr.r = d_r;
     for (unsigned i = 0; i <= M; i++) {   // round i; i = M: the tallest AIRs' last fold only
-        for (const Cls& c : classes) {
+        for (const ZbCls& c : Q.classes) {
             size_t alive = 0;   // the class's jobs are sorted tallest first: the ones with m >= i are a prefix
             while (alive < c.n && jobs[c.lo + alive].m >= i) alive++;
             if (!alive) continue;
@@ -982,11 +1085,10 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
         }
         if (i < M) {
             KernelScope ks(ctx, "zb_round_tr");
-            hipLaunchKernelGGL(k_zb_round_tr, dim3(1), dim3(ZB_TR), 0, st, d_t, d_jobs, (unsigned)n_jobs, i, M, D, ztr);
+            hipLaunchKernelGGL(k_zb_round_tr, dim3(1), dim3(ZB_TR), 0, st, d_t, d_jobs, (unsigned)n_jobs, i, M, T.D, ztr);
         }
         ZK_HIP_CHECK(ctx, hipGetLastError());
     }
-    // 7. the values of every active AIR at its prefix of r
     if (n_jobs) {
         {
             KernelScope ks(ctx, "zb_emit");
@@ -995,147 +1097,128 @@ int prove_batch(zkhip_ctx* ctx, const zkhip_whir_params* prm, const zkhip_air* a
         ZK_HIP_CHECK(ctx, hipGetLastError());
         ZK_TRY(transcript_observe(ctx, d_t, dP + T.o_vals, (uint32_t)(T.o_red - T.o_vals), true));
     }
-    // 8. the batched rotation reduction
-    if (n_red) {
-        std::map<unsigned, size_t> heights;   // the reducing AIRs' distinct heights
-        unsigned m_min = M2;
-        for (size_t a : T.red) heights[S.plans[a].m] = eq_at[S.plans[a].m], m_min = std::min(m_min, S.plans[a].m);
-        ZK_TRY(transcript_sample(ctx, d_t, lambda, nullptr, 4));
-        {
-            KernelScope ks(ctx, "zb_pows");
-            hipLaunchKernelGGL(k_zc_pows, dim3(1), dim3(256), 0, st, (const uint32_t*)lambda, (unsigned)red_vals, d_ws + o_lpow);
-        }
-        for (auto& e : heights) {
-            KernelScope ks(ctx, "zb_eq");
-            whir_eq_launch(st, d_ws + e.second, e.first, d_r);
-        }
-        {
-            KernelScope ks(ctx, "zb_combine");
-            if (key) hipLaunchKernelGGL(k_zb_combine_p, dim3(grid_of((size_t)1 << M2), (unsigned)n_red), dim3(256), 0, st, d_rots);
-            else hipLaunchKernelGGL(k_zb_combine, dim3(grid_of((size_t)1 << M2), (unsigned)n_red), dim3(256), 0, st, d_rots);
-        }
-        ZK_HIP_CHECK(ctx, hipGetLastError());
-        const ZbRotTr rtr{d_ws + o_state, dP + T.o_red, d_rp};
-        for (unsigned t = 0; t < M2; t++) {
-            {
-                KernelScope ks(ctx, "zb_rot_pass");
-                hipLaunchKernelGGL(k_zb_rot_pass, dim3(grid_of(((size_t)1 << (M2 - t)) >> 1), (unsigned)n_red), dim3(256), 0, st, d_rots, t,
-                                   t ? (const uint32_t*)(d_rp + 4 * (t - 1)) : nullptr);
-            }
-            {
-                KernelScope ks(ctx, "zb_round_tr");
-                hipLaunchKernelGGL(k_zb_rot_tr, dim3(1), dim3(ZB_TR), 0, st, d_t, d_rots, (unsigned)n_red, t, rtr);
-            }
-            ZK_HIP_CHECK(ctx, hipGetLastError());
-        }
-        for (auto& e : heights) {
-            KernelScope ks(ctx, "zb_eq");
-            whir_eq_launch(st, d_ws + e.second, e.first, d_rp);
-        }
-        {
-            KernelScope ks(ctx, "zb_dot");
-            hipLaunchKernelGGL(k_zb_dot, dim3((unsigned)n_ucols), dim3(256), 0, st, (const ZbCol*)(d_ws + o_col), dP + T.o_u);
-        }
-        ZK_HIP_CHECK(ctx, hipGetLastError());
-        ZK_TRY(transcript_observe(ctx, d_t, dP + T.o_u, (uint32_t)(T.head - T.o_u), true));
-    }
-    // 9. the points: an inactive AIR samples its own, all of them in one launch
-    if (inact_words) ZK_TRY(transcript_sample(ctx, d_t, dP + o_inact, nullptr, (uint32_t)inact_words));
-    std::vector<uint32_t> h(back_words);
-    ZK_TRY(zkhip_d2h(ctx, h.data(), dP, h.size() * 4));
-    for (size_t i = T.head; i < h.size(); i++) h[i] = from_monty(h[i]);
-    std::vector<uint32_t> points, points_p;   // points_p: of the AIRs that have preprocessed columns, for the key's opening
-    std::vector<size_t> pt_at(n_airs);        // AIR -> its point in h
-    size_t in_at = o_inact;
-    for (size_t a = 0; a < n_airs; a++) {
-        const ZcPlan& pl = S.plans[a];
-        const size_t from = pt_at[a] = !pl.active() ? in_at : pl.reduces() ? o_rp : o_r;
-        points.insert(points.end(), h.begin() + from, h.begin() + from + 4 * (size_t)pl.m);
-        if (key && pl.wp) points_p.insert(points_p.end(), h.begin() + from, h.begin() + from + 4 * (size_t)pl.m);
-        if (!pl.active()) in_at += 4 * (size_t)pl.m;
-    }
-    // 10. the one stacked opening (keyed: then the key's commitment, on the same transcript)
-    ZK_TRY(stack_open(ctx, com.sc, d_t, points.data(), S.dims.data(), n_airs, S.col_point.data(), nullptr, proof_out + T.head, cap - T.head));
-    if (key) {
-        const size_t o = T.head + S.main_words;
-        ZK_TRY(stack_open(ctx, key->sc, d_t, points_p.data(), S.dims_p.data(), S.dims_p.size(), S.col_point_p.data(), nullptr, proof_out + o, cap - o));
-    }
-    size_t o = T.head + S.main_words + S.prep_words;
-    for (size_t k = 0; k < S.cached_airs.size(); o += S.cached_words[k], k++) {   // each partition's commitment at its AIR's point
-        const size_t a = S.cached_airs[k];
-        const std::vector<unsigned> zero(S.cw[a], 0);
-        ZK_TRY(stack_open(ctx, cached[a]->sc, d_t, h.data() + pt_at[a], &S.dims[a], 1, zero.data(), nullptr, proof_out + o, cap - o));
-        memcpy(proof_out + 8 * k, cached[a]->root, 32);
-    }
-    memcpy(proof_out + pre, root, 32);
-    memcpy(proof_out + pre + 8, h.data() + pre + 8, (T.head - pre - 8) * 4);
-    if (root_out) memcpy(root_out, root, 32);
     return ZKHIP_OK;
 }
-
-// the host verifier of the batched proof; pq_out: with_bus only
-// prep_root: the keyed form, checked against the key's root at l_prep (never reads prep_trace)
-int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs, const uint32_t* const* pvs,
-                 unsigned l, const uint32_t* proof, size_t words, bool with_bus, uint32_t* root_out, uint32_t* pq_out,
-                 const uint32_t* prep_root = nullptr, unsigned l_prep = 0, const unsigned* l_cached = nullptr,
-                 uint32_t* cached_roots_out = nullptr) {
-    BatchShape T;
-    if (!batch_shape(prm, airs, n_airs, l, with_bus, &T, prep_root ? (int)l_prep : -1, l_cached)) return ZKHIP_ERR_INVALID;
-    const Shape& S = T.S;
-    const size_t pre = S.pre;   // the cached form: the partitions' roots, sent before the main root
-    const uint32_t* root = proof + pre;
-    for (size_t i = 0; prep_root && i < 8; i++)
-        if (prep_root[i] >= P) return ZKHIP_ERR_INVALID;
-    for (size_t a = 0; a < n_airs; a++) {
-        if (airs[a].n_pvs && !pvs[a]) return ZKHIP_ERR_INVALID;
-        for (size_t i = 0; i < airs[a].n_pvs; i++)
-            if (pvs[a][i] >= P) return ZKHIP_ERR_INVALID;
+// 8. the batched rotation reduction (some AIR reduces); the keyed form's combine reads the key's columns too
+int batch_reduce(const ProveIn& in, const BatchShape& T, const BatchPlan& Q, uint32_t* d_ws, uint32_t* dP) {
+    zkhip_ctx* ctx = in.ctx;
+    DevTranscript* d_t = in.d_t;
+    hipStream_t st = ctx->stream;
+    const unsigned M2 = T.M2, n_red = (unsigned)T.red.size();
+    uint32_t *lambda = d_ws + Q.o_chal + 4 * T.M + 8, *d_r = dP + Q.o_r, *d_rp = dP + Q.o_rp;
+    const ZbRot* d_rots = (const ZbRot*)(d_ws + Q.o_rot);
+    // the reducing AIRs' distinct heights -> their eq tables: zc_plan takes rot and rot_p from the proven constraints, so a reducing
+    // AIR has some and batch_plan gave its height a table
+    std::map<unsigned, size_t> heights;
+    for (size_t a : T.red) heights[T.S.plans[a].m] = Q.eq_at.at(T.S.plans[a].m);
+    ZK_TRY(transcript_sample(ctx, d_t, lambda, nullptr, 4));
+    {
+        KernelScope ks(ctx, "zb_pows");
+        hipLaunchKernelGGL(k_zc_pows, dim3(1), dim3(256), 0, st, (const uint32_t*)lambda, (unsigned)Q.red_vals, d_ws + Q.o_lpow);
     }
-    for (size_t i = 0; i < n_prefix; i++)
-        if (prefix[i] >= P) return ZKHIP_ERR_INVALID;
-    if (words != T.total) return ZKHIP_ERR_VERIFY;
-    for (size_t i = 0; i < T.head; i++)
-        if (proof[i] >= P) return ZKHIP_ERR_VERIFY;
-    HostChallenger ch;
-    ch.observe_canon(prefix, n_prefix);
-    if (prep_root) ch.observe_canon(prep_root, 8);
-    ch.observe_canon(proof, pre + 8);   // the cached roots (if any), then the main root
-    for (size_t a = 0; a < n_airs; a++) ch.observe_canon(pvs[a], airs[a].n_pvs);
-    const Ext one = ext_one();
-    const size_t n_blk = S.blocks.size();
-    const uint32_t* qB = nullptr;
-    Ext gamma = ext_zero(), kappa = ext_zero();
-    std::vector<Ext> rho(S.L), eb(n_blk), bpow(LOGUP_MAX_FIELDS + 1, one);
-    std::vector<std::vector<size_t>> blk_of(n_airs);
-    if (with_bus) {   // steps 2 - 5, as in verify()
-        gamma = ch.sample_ext();
-        const Ext beta = ch.sample_ext();
-        std::vector<uint32_t> pt(4 * (size_t)S.L);
-        uint32_t cl8[8];
-        Ext pq[2];
-        ZK_TRY(gkr_verify_host(ch, root + 8, S.gkr_words, S.L, pt.data(), cl8, pq));
-        if (!ext_eq(pq[0], ext_zero()) || ext_eq(pq[1], ext_zero())) return ZKHIP_ERR_VERIFY;
-        for (unsigned j = 0; j < S.L; j++) rho[j] = ext_from_canon(pt.data() + 4 * j);
-        const Ext pstar = ext_from_canon(cl8), qstar = ext_from_canon(cl8 + 4);
-        Ext pad = one;
-        for (size_t b = 0; b < n_blk; b++) {
-            const AsBlk& k = S.blocks[b];
-            Ext e = one;
-            for (unsigned t = 0; k.m + t < S.L; t++) e = ext_mul(e, ((k.off >> k.m) >> t) & 1u ? rho[k.m + t] : ext_sub(one, rho[k.m + t]));
-            eb[b] = e, pad = ext_sub(pad, e);
+    for (auto& e : heights) {
+        KernelScope ks(ctx, "zb_eq");
+        whir_eq_launch(st, d_ws + e.second, e.first, d_r);
+    }
+    {
+        KernelScope ks(ctx, "zb_combine");
+        if (in.key) hipLaunchKernelGGL(k_zb_combine_p, dim3(grid_of((size_t)1 << M2), n_red), dim3(256), 0, st, d_rots);
+        else hipLaunchKernelGGL(k_zb_combine, dim3(grid_of((size_t)1 << M2), n_red), dim3(256), 0, st, d_rots);
+    }
+    ZK_HIP_CHECK(ctx, hipGetLastError());
+    const ZbRotTr rtr{d_ws + Q.o_state, dP + T.o_red, d_rp};
+    for (unsigned t = 0; t < M2; t++) {
+        {
+            KernelScope ks(ctx, "zb_rot_pass");
+            hipLaunchKernelGGL(k_zb_rot_pass, dim3(grid_of(((size_t)1 << (M2 - t)) >> 1), n_red), dim3(256), 0, st, d_rots, t,
+                               t ? (const uint32_t*)(d_rp + 4 * (t - 1)) : nullptr);
         }
-        kappa = ch.sample_ext();
-        qB = root + 8 + S.gkr_words;
-        Ext lhs = ext_mul(kappa, pad);
-        for (size_t i = 0; i < S.n_bus; i++) lhs = ext_add(lhs, ext_from_canon(qB + 4 * i));
-        ch.observe_canon(qB, 4 * S.n_bus);
-        if (!ext_eq(lhs, ext_add(pstar, ext_mul(kappa, qstar)))) return ZKHIP_ERR_VERIFY;
-        for (unsigned i = 1; i <= LOGUP_MAX_FIELDS; i++) bpow[i] = ext_mul(bpow[i - 1], beta);
-        for (size_t a = 0; a < n_airs; a++) blk_of[a].resize(S.plans[a].prog.ints.size());
-        for (size_t b = 0; b < n_blk; b++) blk_of[S.blocks[b].a][S.blocks[b].j] = b;
+        {
+            KernelScope ks(ctx, "zb_round_tr");
+            hipLaunchKernelGGL(k_zb_rot_tr, dim3(1), dim3(ZB_TR), 0, st, d_t, d_rots, n_red, t, rtr);
+        }
+        ZK_HIP_CHECK(ctx, hipGetLastError());
     }
-    // 6. the batched sum-check
-    const unsigned M = T.M, D = T.D, M2 = T.M2;
+    for (auto& e : heights) {
+        KernelScope ks(ctx, "zb_eq");
+        whir_eq_launch(st, d_ws + e.second, e.first, d_rp);
+    }
+    {
+        KernelScope ks(ctx, "zb_dot");
+        hipLaunchKernelGGL(k_zb_dot, dim3((unsigned)Q.n_ucols), dim3(256), 0, st, (const ZbCol*)(d_ws + Q.o_col), dP + T.o_u);
+    }
+    ZK_HIP_CHECK(ctx, hipGetLastError());
+    return transcript_observe(ctx, d_t, dP + T.o_u, (uint32_t)(T.head - T.o_u), true);
+}
+// the batched proof (docs/airbatch.md's step numbers); in.cached: per AIR, null where the AIR has no CACHED section
+int prove_batch(const ProveIn& in) {
+    zkhip_ctx* ctx = in.ctx;
+    const size_t n_airs = in.n_airs;
+    const std::string who = in.cached ? "airkey cached: " : in.key ? "airkey batch: " : "airbatch: ";
+    BatchShape T;
+    std::vector<unsigned> l_cached;
+    for (size_t a = 0; in.cached && a < n_airs; a++) l_cached.push_back(in.cached[a] ? in.cached[a]->l : 0);
+    if (!batch_shape(in.prm, in.airs, n_airs, in.l, in.with_bus, &T, in.key ? (int)in.key->l_prep : -1, in.cached ? l_cached.data() : nullptr))
+        return set_error(ctx, ZKHIP_ERR_INVALID, who + "the shape does not fit the limits");
+    const Shape& S = T.S;
+    for (size_t a : S.cached_airs) {
+        const zkhip_cached_main* c = in.cached[a];
+        if (!c || !c->sc || c->air != a || c->m != S.plans[a].m || c->cw != S.cw[a] || memcmp(&c->params, in.prm, sizeof(*in.prm)) != 0)
+            return set_error(ctx, ZKHIP_ERR_INVALID, who + "a cached partition's handle is null or was made for another AIR, height or width");
+    }
+    if (in.cap < T.total) return set_error(ctx, ZKHIP_ERR_SMALL_BUFFER, who + "proof buffer too small");
+    size_t n_pv = 0;
+    ZK_TRY(check_inputs(in, who, &n_pv));
+    BatchPlan Q;
+    ZK_TRY(batch_plan(ctx, who, T, in.with_bus, &Q));
+    MainCom com{ctx};
+    ZK_TRY(commit_main(in, S, &com));   // 1.
+    DevBufs B(ctx);
+    uint32_t *dP = B.get(Q.back_words), *d_obs = B.get(obs_words(in, S, n_pv)), *d_ws = B.get(Q.ws_words);
+    if (!dP || !d_obs || !d_ws) return set_error(ctx, ZKHIP_ERR_NOMEM, who + "the workspace does not fit");
+    ZK_TRY(observe_start(in, S, d_obs, com.root));
+    // 2. - 5. the bus part
+    std::vector<ZcBus> bus(n_airs);
+    const uint32_t* chal = nullptr;
+    if (in.with_bus) ZK_TRY(prove_bus(ctx, S, in.airs, n_airs, in.d_traces, in.pvs, in.d_t, B, dP + S.pre, &bus, in.key, &chal));
+    std::vector<uint32_t> up;
+    std::vector<ZbJob> jobs;
+    batch_fill(in, T, Q, bus, d_ws, &up, &jobs);
+    ZK_TRY(zkhip_h2d(ctx, d_ws, up.data(), up.size() * 4));
+    ZK_TRY(batch_rounds(in, T, Q, jobs, d_ws, dP, chal));               // 6., 7.
+    if (!T.red.empty()) ZK_TRY(batch_reduce(in, T, Q, d_ws, dP));       // 8.
+    // 9. the points: an inactive AIR samples its own, all of them in one launch; then the one read-back
+    if (Q.inact_words) ZK_TRY(transcript_sample(ctx, in.d_t, dP + Q.o_inact, nullptr, (uint32_t)Q.inact_words));
+    std::vector<uint32_t> h(Q.back_words);
+    ZK_TRY(zkhip_d2h(ctx, h.data(), dP, h.size() * 4));
+    for (size_t i = T.head; i < h.size(); i++) h[i] = from_monty(h[i]);
+    std::vector<size_t> pt_at(n_airs);   // AIR -> its point in h: its own if inactive, else its prefix of r' if it reduces, of r if not
+    size_t in_at = Q.o_inact;
+    for (size_t a = 0; a < n_airs; a++) {
+        const ZcPlan& pl = S.plans[a];
+        pt_at[a] = !pl.active() ? in_at : pl.reduces() ? Q.o_rp : Q.o_r;
+        if (!pl.active()) in_at += 4 * (size_t)pl.m;
+    }
+    // 10. the openings
+    return open_and_finish(in, S, com, h, pt_at, T.head);
+}
+// the host verifier of the batched proof
+// pq_out: written under with_bus only: these entry points hand the caller's pointer through in either form (verify()'s callers
+// pass null without with_bus instead)
+int verify_batch(const VerIn& in, uint32_t* root_out, uint32_t* pq_out, uint32_t* cached_roots_out = nullptr) {
+    const size_t n_airs = in.n_airs;
+    const uint32_t *const *pvs = in.pvs, *proof = in.proof;
+    BatchShape T;
+    if (!batch_shape(in.prm, in.airs, n_airs, in.l, in.with_bus, &T, in.prep_root ? (int)in.l_prep : -1, in.l_cached)) return ZKHIP_ERR_INVALID;
+    const Shape& S = T.S;
+    const uint32_t* root = proof + S.pre;   // the cached form: the partitions' roots are sent before the main root
+    HostChallenger ch;
+    ZK_TRY(verify_start(ch, in, S, T.head, T.total));   // 1.
+    const Ext one = ext_one();
+    BusV V;
+    if (in.with_bus) ZK_TRY(verify_bus(ch, S, root + 8, &V));   // 2. - 5.
+    // 6. the batched sum-check: the claim is sum_j mu^j 2^(M - m_a) (AIR a's bus claim), j over the active AIRs
+    const unsigned M = T.M, M2 = T.M2;
     std::vector<Ext> tau(M), r(M), rp(M2);
     Ext alpha = ext_zero();
     if (T.any_cons) {
@@ -1148,102 +1231,46 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
     Ext claim = ext_zero(), mup = one;
     for (size_t a : T.act) {
         const ZcPlan& pl = S.plans[a];
-        if (!pl.bus_roots.empty()) {
-            Ext cst = ext_zero();   // sum_j e_{a,j} (gamma + bus_j + 1)
-            for (size_t j = 0; j < blk_of[a].size(); j++) {
-                const Interaction& it = pl.prog.ints[j];
-                const Ext e = eb[blk_of[a][j]], ke = ext_mul(kappa, e);
-                Ext g1 = gamma;
-                g1.c[0] = madd(g1.c[0], to_monty(it.bus + 1));
-                cst = ext_add(cst, ext_mul(e, g1));
-                coef[a].push_back(it.sign ? ext_neg(e) : e);
-                for (uint32_t i = 0; i < it.n_fields; i++) coef[a].push_back(ext_mul(ke, bpow[i + 1]));
-            }
-            const Ext c = ext_sub(ext_from_canon(qB + 4 * S.b_at[a]), ext_mul(kappa, cst));
-            claim = ext_add(claim, ext_mul(ext_mul(mup, ext_pow(two, M - pl.m)), c));   // mu^j 2^(M - m_a) c_a
-        }
+        if (!pl.bus_roots.empty()) claim = ext_add(claim, ext_mul(ext_mul(mup, ext_pow(two, M - pl.m)), bus_claim(S, V, a, &coef[a])));
         mup = ext_mul(mup, mu);
     }
     const uint32_t* q = proof + T.o_rounds;
-    for (unsigned i = 0; i < M; i++, q += 4 * D) {
-        Ext s[ZKHIP_ZEROCHECK_MAX_DEGREE + 1];
-        s[0] = ext_from_canon(q), s[1] = ext_sub(claim, s[0]);
-        for (unsigned e = 1; e < D; e++) s[e + 1] = ext_from_canon(q + 4 * e);
-        ch.observe_canon(q, 4 * D);
-        r[i] = ch.sample_ext();
-        claim = poly_at(s, D, r[i]);
-    }
-    // 7. the values: sum_j mu^j [eq(tau_a, r_a) sum_k alpha^k C_k + eq(rho_a, r_a) (the bus part)] = the last claim
+    claim = rounds_host(ch, q, M, T.D, claim, r.data());
+    // 7. the values: sum_j mu^j (AIR a's summand at its prefix of r) = the last claim
     ch.observe_canon(q, T.o_red - T.o_vals);
-    std::vector<const uint32_t*> vals(n_airs, nullptr), claimed(n_airs, nullptr);
-    std::vector<const uint32_t*> claimed_p(n_airs, nullptr);   // keyed: the w_p values the key's opening must show
+    std::vector<const uint32_t*> vals(n_airs, nullptr);
     Ext rhs = ext_zero();
     mup = one;
     for (size_t a : T.act) {
         const ZcPlan& pl = S.plans[a];
-        const unsigned m = pl.m;
-        const size_t w = pl.w, n_rot = pl.rot.size(), wp = pl.wp, n_rot_p = pl.rot_p.size();
-        std::vector<Ext> v(w), vn(n_rot), vp(wp), vpn(n_rot_p);   // v, v', v_p, v_p'
-        for (size_t j = 0; j < w; j++) v[j] = ext_from_canon(q + 4 * j);
-        for (size_t t = 0; t < n_rot; t++) vn[t] = ext_from_canon(q + 4 * (w + t));
-        for (size_t j = 0; j < wp; j++) vp[j] = ext_from_canon(q + 4 * (w + n_rot + j));
-        for (size_t t = 0; t < n_rot_p; t++) vpn[t] = ext_from_canon(q + 4 * (w + n_rot + wp + t));
-        vals[a] = q, q += 4 * (w + n_rot + wp + n_rot_p);
-        Ext first = one, last = one, g = ext_zero();
-        for (unsigned j = 0; j < m; j++) first = ext_mul(first, ext_sub(one, r[j])), last = ext_mul(last, r[j]);
-        if (!pl.proven.empty()) {
-            const std::vector<Ext> val = zc_eval_host(pl, pl.reach, v.data(), vn.data(), first, last, pvs[a], vp.data(), vpn.data());
-            Ext c = ext_zero(), ap = one;
-            for (uint32_t k : pl.proven) c = ext_add(c, ext_mul(ap, val[k])), ap = ext_mul(ap, alpha);
-            g = ext_mul(eq_eval(tau.data(), r.data(), m), c);
-        }
-        if (!pl.bus_roots.empty()) {
-            const std::vector<Ext> val = zc_eval_host(pl, pl.bus_reach, v.data(), vn.data(), first, last, pvs[a], vp.data(), vpn.data());
-            Ext c = ext_zero();
-            for (size_t k = 0; k < coef[a].size(); k++) c = ext_add(c, ext_mul(coef[a][k], val[pl.bus_roots[k]]));
-            g = ext_add(g, ext_mul(eq_eval(rho.data(), r.data(), m), c));
-        }
-        rhs = ext_add(rhs, ext_mul(mup, g));
+        vals[a] = q, q += 4 * (pl.w + pl.rot.size() + pl.wp + pl.rot_p.size());
+        rhs = ext_add(rhs, ext_mul(mup, air_summand(pl, vals[a], pvs[a], tau.data(), alpha, V.rho.data(), coef[a], r.data())));
         mup = ext_mul(mup, mu);
     }
     if (!ext_eq(rhs, claim)) return ZKHIP_ERR_VERIFY;
-    // 8. the batched rotation reduction
+    // 8. the batched rotation reduction: one lambda, its powers running through the reducing AIRs' values, weights 2^(M' - m_a)
+    std::vector<const uint32_t*> claimed(n_airs, nullptr), claimed_p(n_airs, nullptr);   // as in verify()
     if (!T.red.empty()) {
         const Ext lambda = ch.sample_ext();
-        std::vector<std::vector<Ext>> lp(n_airs);   // lambda^(o_a + k) over the AIR's [v | v' | v_p | v_p']
+        std::vector<std::vector<Ext>> lp(n_airs);
         Ext x = one;
         claim = ext_zero();
         for (size_t a : T.red) {
             const ZcPlan& pl = S.plans[a];
-            Ext acc = ext_zero();
-            const size_t n_val = pl.w + pl.rot.size() + pl.wp + pl.rot_p.size();
-            for (size_t k = 0; k < n_val; k++) lp[a].push_back(x), acc = ext_add(acc, ext_mul(x, ext_from_canon(vals[a] + 4 * k))), x = ext_mul(x, lambda);
+            const Ext acc = lambda_comb(vals[a], pl.w + pl.rot.size() + pl.wp + pl.rot_p.size(), lambda, &x, &lp[a]);
             claim = ext_add(claim, ext_mul(ext_pow(two, M2 - pl.m), acc));
         }
-        for (unsigned i = 0; i < M2; i++, q += 8) {
-            const Ext s0 = ext_from_canon(q), s2 = ext_from_canon(q + 4);
-            ch.observe_canon(q, 8);
-            rp[i] = ch.sample_ext();
-            const Ext sv[3] = {s0, ext_sub(claim, s0), s2};
-            claim = poly_at(sv, 2, rp[i]);
-        }
+        claim = rounds_host(ch, q, M2, 2, claim, rp.data());
         ch.observe_canon(q, T.head - T.o_u);
         Ext want = ext_zero();
         for (size_t a : T.red) {
             const ZcPlan& pl = S.plans[a];
-            Ext ua = ext_zero(), ub = ext_zero();
-            for (size_t j = 0; j < pl.w; j++) ua = ext_add(ua, ext_mul(lp[a][j], ext_from_canon(q + 4 * j)));
-            for (size_t t = 0; t < pl.rot.size(); t++) ub = ext_add(ub, ext_mul(lp[a][pl.w + t], ext_from_canon(q + 4 * pl.rot[t])));
-            const uint32_t* qp = q + 4 * pl.w;   // u_p
-            const size_t o = pl.w + pl.rot.size();
-            for (size_t j = 0; j < pl.wp; j++) ua = ext_add(ua, ext_mul(lp[a][o + j], ext_from_canon(qp + 4 * j)));
-            for (size_t t = 0; t < pl.rot_p.size(); t++) ub = ext_add(ub, ext_mul(lp[a][o + pl.wp + t], ext_from_canon(qp + 4 * pl.rot_p[t])));
-            claimed[a] = q, claimed_p[a] = pl.wp ? qp : nullptr, q += 4 * (pl.w + pl.wp);
-            want = ext_add(want, ext_add(ext_mul(ua, eq_eval(r.data(), rp.data(), pl.m)), ext_mul(ub, zc_rot_eval(r.data(), rp.data(), pl.m))));
+            want = ext_add(want, u_term(pl, lp[a].data(), q, r.data(), rp.data()));
+            claimed[a] = q, claimed_p[a] = pl.wp ? q + 4 * pl.w : nullptr, q += 4 * (pl.w + pl.wp);
         }
         if (!ext_eq(want, claim)) return ZKHIP_ERR_VERIFY;
     }
-    // 9. the points, 10. the stacked opening
+    // 9. the points: an inactive AIR samples its own; the others take their prefix of r' if they reduce, of r if not
     std::vector<uint32_t> points;
     for (size_t a = 0; a < n_airs; a++) {
         const ZcPlan& pl = S.plans[a];
@@ -1254,38 +1281,11 @@ int verify_batch(const zkhip_whir_params* prm, const uint32_t* prefix, size_t n_
             points.insert(points.end(), c4, c4 + 4);
         }
     }
-    const uint32_t* op = proof + T.head;
-    ZK_TRY(stack_verify_host(ch, prm, root, S.lh.data(), S.lh.size(), l, points.data(), S.dims.data(), n_airs, S.col_point.data(), op, S.main_words));
-    size_t col = 0;   // the main opening shows the common columns: all of them where there is no cached partition
-    for (size_t a = 0; a < n_airs; col += airs[a].width - S.cw[a], a++)
-        if (claimed[a] && memcmp(claimed[a] + 4 * S.cw[a], op + 4 * col, 16 * (airs[a].width - S.cw[a])) != 0) return ZKHIP_ERR_VERIFY;
-    if (prep_root) {   // the key's opening, against the verifier's own root: an inactive AIR with preprocessed columns is in it too
-        std::vector<uint32_t> pts;
-        size_t at = 0;
-        for (size_t a = 0; a < n_airs; at += 4 * (size_t)S.plans[a].m, a++)
-            if (S.plans[a].wp) pts.insert(pts.end(), points.begin() + at, points.begin() + at + 4 * (size_t)S.plans[a].m);
-        const uint32_t* op2 = op + S.main_words;
-        ZK_TRY(stack_verify_host(ch, prm, prep_root, S.lh_p.data(), S.lh_p.size(), l_prep, pts.data(), S.dims_p.data(), S.dims_p.size(),
-                                 S.col_point_p.data(), op2, S.prep_words));
-        col = 0;
-        for (size_t a = 0; a < n_airs; col += S.plans[a].wp, a++)
-            if (claimed_p[a] && memcmp(claimed_p[a], op2 + 4 * col, 16 * S.plans[a].wp) != 0) return ZKHIP_ERR_VERIFY;
-    }
-    // each cached partition's opening, against the root the proof sent, at its AIR's point: it shows the first cw entries of u (of v
-    // where the AIR does not reduce); an inactive AIR's values stand
-    const uint32_t* op3 = op + S.main_words + S.prep_words;
-    size_t at = 0;
-    for (size_t a = 0, k = 0; a < n_airs; at += 4 * (size_t)S.plans[a].m, a++) {
-        if (!S.cw[a]) continue;
-        const std::vector<unsigned> lhc(S.cw[a], S.plans[a].m), zero(S.cw[a], 0);
-        ZK_TRY(stack_verify_host(ch, prm, proof + 8 * k, lhc.data(), lhc.size(), l_cached[a], points.data() + at, &S.dims[a], 1, zero.data(), op3,
-                                 S.cached_words[k]));
-        if (claimed[a] && memcmp(claimed[a], op3, 16 * S.cw[a]) != 0) return ZKHIP_ERR_VERIFY;
-        op3 += S.cached_words[k++];
-    }
-    if (cached_roots_out) memcpy(cached_roots_out, proof, 4 * pre);
+    // 10. the openings: main, the key's, the partitions'
+    ZK_TRY(verify_openings(ch, in, S, T.head, points, claimed, claimed_p));
+    if (cached_roots_out) memcpy(cached_roots_out, proof, 4 * S.pre);
     if (root_out) memcpy(root_out, root, 32);
-    if (pq_out && with_bus) memcpy(pq_out, root + 8, 32);
+    if (pq_out && in.with_bus) memcpy(pq_out, root + 8, 32);
     return ZKHIP_OK;
 }
 
@@ -1392,7 +1392,7 @@ int zkhip_zerocheck_prove(zkhip_ctx* ctx, const zkhip_whir_params* params, const
                           uint32_t* root_out) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !params || !airs || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
-    return prove(ctx, params, airs, n_airs, d_traces, pvs, log_stack, false, transcript->d, proof_out, cap, root_out);
+    return prove({ctx, params, airs, n_airs, d_traces, pvs, log_stack, false, transcript->d, proof_out, cap, root_out});
 }
 
 int zkhip_airset_prove(zkhip_ctx* ctx, const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, const uint32_t* const* d_traces,
@@ -1400,7 +1400,7 @@ int zkhip_airset_prove(zkhip_ctx* ctx, const zkhip_whir_params* params, const zk
                        uint32_t* root_out) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !params || !airs || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
-    return prove(ctx, params, airs, n_airs, d_traces, pvs, log_stack, true, transcript->d, proof_out, cap, root_out);
+    return prove({ctx, params, airs, n_airs, d_traces, pvs, log_stack, true, transcript->d, proof_out, cap, root_out});
 }
 
 int zkhip_airkey_create(zkhip_ctx* ctx, const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, unsigned log_stack_prep,
@@ -1425,16 +1425,16 @@ int zkhip_airkey_prove(zkhip_ctx* ctx, zkhip_airkey* key, int with_bus, const ui
                        unsigned log_stack, zkhip_transcript* transcript, uint32_t* proof_out, size_t cap, uint32_t* root_out) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !key || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
-    return prove(ctx, &key->params, key->airs.data(), key->airs.size(), d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out, cap,
-                 root_out, key);
+    return prove({ctx, &key->params, key->airs.data(), key->airs.size(), d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out, cap,
+                  root_out, key});
 }
 
 int zkhip_airkey_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
                         const uint32_t* prep_root, unsigned log_stack_prep, const uint32_t* const* pvs, unsigned log_stack, int with_bus,
                         const uint32_t* proof, size_t words, uint32_t* root_out, uint32_t* pq_out) {
     if (!params || (n_prefix && !prefix) || !airs || !prep_root || !pvs || !proof || log_stack_prep > ZKHIP_WHIR_MAX_LOG_N) return ZKHIP_ERR_INVALID;
-    return verify(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, root_out, with_bus ? pq_out : nullptr, prep_root,
-                  log_stack_prep);
+    return verify({params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, prep_root, log_stack_prep}, root_out,
+                  with_bus ? pq_out : nullptr);
 }
 
 size_t zkhip_airkey_batch_proof_words(const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, unsigned log_stack,
@@ -1448,16 +1448,16 @@ int zkhip_airkey_batch_prove(zkhip_ctx* ctx, zkhip_airkey* key, int with_bus, co
                              unsigned log_stack, zkhip_transcript* transcript, uint32_t* proof_out, size_t cap, uint32_t* root_out) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !key || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
-    return prove_batch(ctx, &key->params, key->airs.data(), key->airs.size(), d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out,
-                       cap, root_out, key);
+    return prove_batch({ctx, &key->params, key->airs.data(), key->airs.size(), d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out,
+                        cap, root_out, key});
 }
 
 int zkhip_airkey_batch_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
                               const uint32_t* prep_root, unsigned log_stack_prep, const uint32_t* const* pvs, unsigned log_stack, int with_bus,
                               const uint32_t* proof, size_t words, uint32_t* root_out, uint32_t* pq_out) {
     if (!params || (n_prefix && !prefix) || !airs || !prep_root || !pvs || !proof || log_stack_prep > ZKHIP_WHIR_MAX_LOG_N) return ZKHIP_ERR_INVALID;
-    return verify_batch(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, root_out, pq_out, prep_root,
-                        log_stack_prep);
+    return verify_batch({params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, prep_root, log_stack_prep}, root_out,
+                        pq_out);
 }
 
 int zkhip_airkey_commit_cached(zkhip_ctx* ctx, zkhip_airkey* key, size_t air, const uint32_t* d_cols, unsigned log_stack_cached,
@@ -1484,8 +1484,8 @@ int zkhip_airkey_cached_prove(zkhip_ctx* ctx, zkhip_airkey* key, int with_bus, c
                               size_t cap, uint32_t* root_out) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !key || !d_traces || !pvs || !cached || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
-    return prove_batch(ctx, &key->params, key->airs.data(), key->airs.size(), d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out,
-                       cap, root_out, key, cached);
+    return prove_batch({ctx, &key->params, key->airs.data(), key->airs.size(), d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out,
+                        cap, root_out, key, cached});
 }
 
 int zkhip_airkey_cached_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
@@ -1494,21 +1494,21 @@ int zkhip_airkey_cached_verify(const zkhip_whir_params* params, const uint32_t* 
                                uint32_t* cached_roots_out) {
     if (!params || (n_prefix && !prefix) || !airs || !prep_root || !log_stack_cached || !pvs || !proof || log_stack_prep > ZKHIP_WHIR_MAX_LOG_N)
         return ZKHIP_ERR_INVALID;
-    return verify_batch(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, root_out, pq_out, prep_root,
-                        log_stack_prep, log_stack_cached, cached_roots_out);
+    return verify_batch({params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, prep_root, log_stack_prep,
+                         log_stack_cached}, root_out, pq_out, cached_roots_out);
 }
 
 int zkhip_zerocheck_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
                            const uint32_t* const* pvs, unsigned log_stack, const uint32_t* proof, size_t words, uint32_t* root_out) {
     if (!params || (n_prefix && !prefix) || !airs || !pvs || !proof) return ZKHIP_ERR_INVALID;
-    return verify(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, false, root_out, nullptr);
+    return verify({params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, false}, root_out, nullptr);
 }
 
 int zkhip_airset_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
                         const uint32_t* const* pvs, unsigned log_stack, const uint32_t* proof, size_t words, uint32_t* root_out,
                         uint32_t* pq_out) {
     if (!params || (n_prefix && !prefix) || !airs || !pvs || !proof) return ZKHIP_ERR_INVALID;
-    return verify(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, true, root_out, pq_out);
+    return verify({params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, true}, root_out, pq_out);
 }
 
 size_t zkhip_airbatch_proof_words(const zkhip_whir_params* params, const zkhip_air* airs, size_t n_airs, unsigned log_stack, int with_bus) {
@@ -1521,14 +1521,14 @@ int zkhip_airbatch_prove(zkhip_ctx* ctx, const zkhip_whir_params* params, const 
                          uint32_t* root_out) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !params || !airs || !d_traces || !pvs || !transcript || !proof_out) return ZKHIP_ERR_INVALID;
-    return prove_batch(ctx, params, airs, n_airs, d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out, cap, root_out);
+    return prove_batch({ctx, params, airs, n_airs, d_traces, pvs, log_stack, with_bus != 0, transcript->d, proof_out, cap, root_out});
 }
 
 int zkhip_airbatch_verify(const zkhip_whir_params* params, const uint32_t* prefix, size_t n_prefix, const zkhip_air* airs, size_t n_airs,
                           const uint32_t* const* pvs, unsigned log_stack, int with_bus, const uint32_t* proof, size_t words, uint32_t* root_out,
                           uint32_t* pq_out) {
     if (!params || (n_prefix && !prefix) || !airs || !pvs || !proof) return ZKHIP_ERR_INVALID;
-    return verify_batch(params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0, root_out, pq_out);
+    return verify_batch({params, prefix, n_prefix, airs, n_airs, pvs, log_stack, proof, words, with_bus != 0}, root_out, pq_out);
 }
 
 }  // extern "C"
