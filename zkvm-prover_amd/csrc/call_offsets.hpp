@@ -92,5 +92,23 @@ inline void launch_call_offsets(zkhip_ctx* ctx, const uint32_t* d_len, size_t n_
     hipLaunchKernelGGL(k_ro_offsets, dim3(blocks), dim3(RO_W), 0, ctx->stream, d_len, n_calls, n_elems, per_block, shift, exact ? 1 : 0, (const uint64_t*)sums, off, bad);
 }
 
+// The scratch of such a generator (slot 3): n_off arrays of n_calls + 1 offsets, each rounded up to four words | sums[RO_MAX_BLOCKS] (64
+// bits) | `extra_words` words of the generator's own
+struct CallScratch {
+    uint32_t* off[2];
+    uint64_t* sums;
+    uint32_t* extra;
+};
+inline int call_scratch(zkhip_ctx* ctx, size_t n_calls, unsigned n_off, size_t extra_words, CallScratch* s) {
+    const size_t off_words = (n_calls + 1 + 3) / 4 * 4;
+    void* buf = nullptr;
+    ZK_TRY(get_scratch(ctx, 3, (n_off * off_words + 2 * (size_t)RO_MAX_BLOCKS + extra_words) * 4, &buf));
+    uint32_t* p = (uint32_t*)buf;
+    s->off[0] = p, s->off[1] = n_off > 1 ? p + off_words : nullptr;
+    p += n_off * off_words;
+    s->sums = (uint64_t*)p, s->extra = p + 2 * RO_MAX_BLOCKS;
+    return ZKHIP_OK;
+}
+
 }  // namespace
 }  // namespace zk

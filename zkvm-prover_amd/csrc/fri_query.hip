@@ -7,15 +7,14 @@
 //   k_fri_query_rows              one lane per ROW: finds its call in roff, redoes the row's own fold from the pair (everything else in a row
 //                                 is a function of the row's records), permutes e0 | e1 | 0^8 and stores the 61 cells
 // One lane per row keeps the stores along rows with no staging: consecutive lanes hold consecutive rows of every column.  The padding rows
-// are written as zeros by k_fri_query_rows itself, so the trace needs no memset.  The other form of the row kernel, k_fri_query_rows16
-// (16 lanes per row on coop_permute_regs, staged through LDS), was measured against it and lost at both workloads (docs/fri_query.md).
+// are written as zeros by k_fri_query_rows itself, so the trace needs no memset.  A second form of the row kernel (16 lanes per row on
+// coop_permute_regs, staged through LDS) was measured against it, lost at both workloads and was removed (docs/fri_query.md "Measured").
 #include <algorithm>
 
 #include "../../include/zkhip.h"
 #include "babybear.hpp"
 #include "call_offsets.hpp"
 #include "fri_query_host.hpp"
-#include "lds_barrier.hpp"
 #include "poseidon2_coop.hpp"
 #include "tracegen_common.hpp"
 
@@ -24,11 +23,6 @@ namespace {
 
 constexpr unsigned FQ_COLS = ZKHIP_FRI_QUERY_WIDTH;
 static_assert(FQ_COLS == 61, "e0 e1 beta bsq [4] | x_inv | folded ro eval [4] | st_out[16] | root[8] | bit has_ro k lvl is_first is_last is_real call");
-// the form of the row kernel, chosen by measurement (docs/fri_query.md "Measured"); the other one stays for A/B builds: -DZK_FQ_LANES_PER_ROW=1 or 16
-#ifndef ZK_FQ_LANES_PER_ROW
-#define ZK_FQ_LANES_PER_ROW 1
-#endif
-static_assert(ZK_FQ_LANES_PER_ROW == 1 || ZK_FQ_LANES_PER_ROW == 16, "one lane per row or sixteen");
 constexpr unsigned FQ_MAX_LAYERS = 26;   // rows of a call: lvl = log_max - 1 - t >= 1 with log_max <= 27
 
 // W_j^-1 in Montgomery form, W_j the generator of the subgroup of order 2^(j + 2) (air.domain_point_inverse_roots): bit j of a pair index k
@@ -55,12 +49,7 @@ __device__ __forceinline__ uint32_t fq_x_inv(uint32_t k) {
     for (unsigned j = 0; j < FQ_MAX_LAYERS && (k >> j); j++) acc = mmul(acc, (k >> j) & 1u ? FQ_WINV.v[j] : MONTY_ONE);
     return acc;
 }
-// a record word: refused (counted, read as 0) unless it is a field element; returns Montgomery form
-__device__ __forceinline__ uint32_t fq_word(uint32_t v, uint32_t* bad) {
-    if (v >= P) atomicAdd(bad, 1u), v = 0;
-    return to_monty(v);
-}
-__device__ __forceinline__ Ext fq_ext(const uint32_t* p, uint32_t* bad) { return Ext{{fq_word(p[0], bad), fq_word(p[1], bad), fq_word(p[2], bad), fq_word(p[3], bad)}}; }
+__device__ __forceinline__ Ext fq_ext(const uint32_t* p, uint32_t* bad) { return Ext{{field_word(p[0], bad), field_word(p[1], bad), field_word(p[2], bad), field_word(p[3], bad)}}; }
 // folded = ((e0 + e1) + x_inv (beta (e0 - e1))) / 2: the line of air.fri_fold_air
 __device__ __forceinline__ Ext fq_fold(const Ext& e0, const Ext& e1, const Ext& beta, uint32_t xinv) {
     return ext_mul_base(ext_add(ext_add(e0, e1), ext_mul_base(ext_mul(beta, ext_sub(e0, e1)), xinv)), to_monty((P + 1) / 2));
@@ -115,7 +104,7 @@ __global__ __launch_bounds__(256) void k_fri_query_chain(FqIn in, size_t N, uint
     }
 }
 
-// ---- the rows: both forms take a row's call from the offsets and its cells from the row's own records and the pair the chain left ----
+// ---- the rows: a row's call comes from the offsets, its cells from the row's own records and the pair the chain left ----
 // the last call whose first row is not behind r (roff is non-decreasing), and whether r is a row of it
 __device__ __forceinline__ bool fq_find(const FqIn& in, size_t r, uint32_t* c, uint32_t* t, uint32_t* len, uint32_t* lm, uint32_t* idx) {
     uint32_t lo = 0, hi = in.n_calls, r0;
@@ -166,8 +155,8 @@ __device__ __forceinline__ void fq_cells(const FqIn& in, size_t r, uint32_t c, u
     put(60, to_monty(c));
 }
 
-// Form A, one lane per ROW on the batch permutation's device function: consecutive lanes hold consecutive rows of every column, so the
-// stores run along rows with no staging.
+// One lane per ROW on the batch permutation's device function: consecutive lanes hold consecutive rows of every column, so the stores run
+// along rows with no staging.
 __global__ __launch_bounds__(256) void k_fri_query_rows(FqIn in, size_t N, uint32_t* __restrict__ trace, const uint32_t* __restrict__ hash_inputs,
                                                         uint32_t* __restrict__ leaf, uint32_t* __restrict__ bad) {
     const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -180,7 +169,7 @@ __global__ __launch_bounds__(256) void k_fri_query_rows(FqIn in, size_t N, uint3
 #pragma unroll
         for (int i = 0; i < 8; i++) st[i] = hash_inputs[16 * r + i], st[8 + i] = 0;
 #pragma unroll
-        for (int i = 0; i < 8; i++) trace[(size_t)(45 + i) * N + r] = fq_word(in.root[8 * r + i], bad);
+        for (int i = 0; i < 8; i++) trace[(size_t)(45 + i) * N + r] = field_word(in.root[8 * r + i], bad);
         poseidon2_permute_rolled(st);                      // (only the state is live across it: the other cells are out)
 #pragma unroll
         for (int i = 0; i < 16; i++) trace[(size_t)(29 + i) * N + r] = st[i];
@@ -196,52 +185,6 @@ __global__ __launch_bounds__(256) void k_fri_query_rows(FqIn in, size_t N, uint3
             for (int i = 0; i < 8; i++) leaf[8 * r + i] = 0u;
         }
     }
-}
-
-// Form B, 16 lanes per ROW on coop_permute_regs: lane i of a group holds state word i.  A workgroup takes FQ16_ROWS consecutive rows, a
-// group of 16 lanes one of them in each of four passes; the group's first lane computes the row's fold cells, lanes 8..15 fetch the root,
-// every lane keeps its state word, and all of it is staged in LDS so that the 61 columns leave along rows, 256 bytes a wave and column.
-constexpr unsigned FQ16_ROWS = 64;
-constexpr unsigned FQ16_STRIDE = FQ16_ROWS + 4;   // (the 16 state words of the four rows a wave stages at a time fall into 64 banks)
-__global__ __launch_bounds__(256) void k_fri_query_rows16(FqIn in, size_t N, uint32_t* __restrict__ trace, const uint32_t* __restrict__ hash_inputs,
-                                                          uint32_t* __restrict__ leaf, uint32_t* __restrict__ bad) {
-    __shared__ uint32_t tile[FQ_COLS * FQ16_STRIDE];
-    const unsigned lane = threadIdx.x & 15u, g = threadIdx.x >> 4, w = threadIdx.x & 63u;
-    const size_t base = (size_t)blockIdx.x * FQ16_ROWS;
-    if (base >= N) return;
-    if (base >= in.n_rows || in.n_calls == 0) {            // (the same for the whole workgroup) nothing but padding
-        if (base + w < N)
-            for (unsigned q = threadIdx.x >> 6; q < FQ_COLS; q += 4) trace[(size_t)q * N + base + w] = 0u;
-        return;
-    }
-    const CoopConsts cc = coop_load_consts(lane);
-#pragma unroll 1
-    for (unsigned p = 0; p < FQ16_ROWS / 16; p++) {
-        const unsigned slot = p * 16 + g;
-        const size_t r = base + slot;
-        uint32_t c = 0, t = 0, len = 0, lm = 0, idx = 0;   // (the same for the 16 lanes of a group)
-        const bool real = r < N && r < in.n_rows && fq_find(in, r, &c, &t, &len, &lm, &idx);
-        uint32_t x = real && lane < 8 ? hash_inputs[16 * r + lane] : 0u;
-        if (lane == 0) {
-            if (real) {
-                fq_cells(in, r, c, t, len, lm, idx, hash_inputs, [&](unsigned q, uint32_t v) { tile[q * FQ16_STRIDE + slot] = v; });
-            } else {
-#pragma unroll 1
-                for (unsigned q = 0; q < 29; q++) tile[q * FQ16_STRIDE + slot] = 0u;
-#pragma unroll 1
-                for (unsigned q = 53; q < FQ_COLS; q++) tile[q * FQ16_STRIDE + slot] = 0u;
-            }
-        } else if (lane >= 8) {
-            tile[(45 + lane - 8) * FQ16_STRIDE + slot] = real ? fq_word(in.root[8 * r + (lane - 8)], bad) : 0u;
-        }
-        x = coop_permute_regs(x, lane, cc);                // (all 16 lanes of every group, real or not: DPP needs them active)
-        if (!real) x = 0u;
-        tile[(29 + lane) * FQ16_STRIDE + slot] = x;
-        if (leaf && lane < 8 && r < N && r < in.n_rows) leaf[8 * r + lane] = from_monty(x);
-    }
-    zk_syncthreads();
-    if (base + w < N)
-        for (unsigned q = threadIdx.x >> 6; q < FQ_COLS; q += 4) trace[(size_t)q * N + base + w] = tile[q * FQ16_STRIDE + w];
 }
 
 }  // namespace
@@ -267,30 +210,23 @@ int zkhip_fri_query_tracegen(zkhip_ctx* ctx, const uint32_t* d_n_layers, const u
     if (n_calls > n_rows) return set_error(ctx, ZKHIP_ERR_INVALID, "fri_query_tracegen: more calls than rows (a call has at least one)");
     // (what keeps the offsets inside 32 bits; a call has at most 26 rows, so the device's checks would refuse it as well)
     if (n_rows > ((size_t)1 << 31)) return set_error(ctx, ZKHIP_ERR_INVALID, "fri_query_tracegen: more rows than any trace has");
-    // scratch: roff[n_calls + 1] | sums[RO_MAX_BLOCKS] (64 bits)
-    const size_t off_words = (n_calls + 1 + 3) / 4 * 4;
-    void* buf = nullptr;
-    ZK_TRY(get_scratch(ctx, 3, (off_words + 2 * (size_t)RO_MAX_BLOCKS) * 4, &buf));
-    uint32_t* roff = (uint32_t*)buf;
-    uint64_t* sums = (uint64_t*)(roff + off_words);
+    // scratch: roff[n_calls + 1] | sums
+    CallScratch s;
+    ZK_TRY(call_scratch(ctx, n_calls, 1, 0, &s));
+    uint32_t* roff = s.off[0];
     const FqIn in{d_log_max, d_index, d_ro_top, d_beta, d_root, d_sibling, d_has_ro, d_ro, roff, (uint32_t)n_calls, (uint32_t)n_rows};
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    uint32_t* bad = (uint32_t*)flag;
-    KernelScope ks(ctx, "fri_query_tracegen");
-    ZK_HIP_CHECK(ctx, hipMemsetAsync(d_hash_inputs, 0, 16 * N * 4, ctx->stream));
-    if (n_calls) launch_call_offsets(ctx, d_n_layers, n_calls, n_rows, 0, true, sums, roff, bad);
-    // (with no call the chain kernel still runs its one check: rows without calls are refused there)
-    hipLaunchKernelGGL(k_fri_query_chain, dim3((unsigned)((std::max<size_t>(n_calls, 1) + 255) / 256)), dim3(256), 0, ctx->stream, in, N, d_hash_inputs, d_final, bad);
-#if ZK_FQ_LANES_PER_ROW == 16
-    hipLaunchKernelGGL(k_fri_query_rows16, dim3((unsigned)((N + FQ16_ROWS - 1) / FQ16_ROWS)), dim3(256), 0, ctx->stream, in, N, d_trace, (const uint32_t*)d_hash_inputs, d_leaf_digest, bad);
-#else
-    hipLaunchKernelGGL(k_fri_query_rows, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, in, N, d_trace, (const uint32_t*)d_hash_inputs, d_leaf_digest, bad);
-#endif
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return tracegen_finish(ctx, flag,
-                           "fri_query_tracegen (a call of 0 or more than log_max - 1 layers, log_max > 27, an index outside 2^log_max, lengths that do not sum to n_rows, "
-                           "more rows than the trace has, has_ro outside {0, 1}, a non-zero ro under has_ro = 0, or a word that is not a field element)");
+    return tracegen_frame(
+        ctx, "fri_query_tracegen", {},
+        [&](uint32_t* bad) -> int {
+            ZK_HIP_CHECK(ctx, hipMemsetAsync(d_hash_inputs, 0, 16 * N * 4, ctx->stream));
+            if (n_calls) launch_call_offsets(ctx, d_n_layers, n_calls, n_rows, 0, true, s.sums, roff, bad);
+            // (with no call the chain kernel still runs its one check: rows without calls are refused there)
+            hipLaunchKernelGGL(k_fri_query_chain, dim3((unsigned)((std::max<size_t>(n_calls, 1) + 255) / 256)), dim3(256), 0, ctx->stream, in, N, d_hash_inputs, d_final, bad);
+            hipLaunchKernelGGL(k_fri_query_rows, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, in, N, d_trace, (const uint32_t*)d_hash_inputs, d_leaf_digest, bad);
+            return ZKHIP_OK;
+        },
+        "fri_query_tracegen (a call of 0 or more than log_max - 1 layers, log_max > 27, an index outside 2^log_max, lengths that do not sum to n_rows, "
+        "more rows than the trace has, has_ro outside {0, 1}, a non-zero ro under has_ro = 0, or a word that is not a field element)");
 }
 
 }  // extern "C"

@@ -70,8 +70,7 @@ __global__ __launch_bounds__(64) void k_mmcs_rows(MrIn in, size_t N, uint32_t* _
                 else if (lane == 12) v = in.idx[c];
                 else if (lane == 13) v = in.mult[c];
                 else if (lane == 14) v = c;
-                if (v >= P) atomicAdd(bad, 1u), v = 0;
-                cell = to_monty(v);
+                cell = field_word(v, bad);
             }
         }
         const bool all_done = __all(done);
@@ -80,9 +79,7 @@ __global__ __launch_bounds__(64) void k_mmcs_rows(MrIn in, size_t N, uint32_t* _
             const uint32_t k = act ? std::min(8u, L - 8u * t) : 0u;   // words of this block
             if (lane < k) {
                 const uint32_t e = w0 + 8u * t + lane;
-                uint32_t v = e < in.n_words ? in.values[e] : 0u;
-                if (v >= P) atomicAdd(bad, 1u), v = 0;
-                x = to_monty(v);
+                x = field_word(e < in.n_words ? in.values[e] : 0u, bad);
             }
             const uint32_t st_in = x;
             x = coop_permute_regs(x, lane, cc);
@@ -145,31 +142,27 @@ int zkhip_mmcs_rows_tracegen(zkhip_ctx* ctx, const uint32_t* d_len, const uint32
     if (n_words > 8 * N) return set_error(ctx, ZKHIP_ERR_INVALID, "mmcs_rows_tracegen: more rows than the trace has");
     if (n_calls > n_words) return set_error(ctx, ZKHIP_ERR_INVALID, "mmcs_rows_tracegen: more calls than words (a call has at least one)");
     if (n_calls == 0 && n_words != 0) return set_error(ctx, ZKHIP_ERR_INVALID, "mmcs_rows_tracegen: words but no call (the lengths must sum to n_words)");
-    // scratch: woff[n_calls + 1] | roff[n_calls + 1] | sums[RO_MAX_BLOCKS] (64 bits) | the call counter
-    const size_t off_words = (n_calls + 1 + 3) / 4 * 4;
-    void* buf = nullptr;
-    ZK_TRY(get_scratch(ctx, 3, (2 * off_words + 2 * (size_t)RO_MAX_BLOCKS + 4) * 4, &buf));
-    uint32_t *woff = (uint32_t*)buf, *roff = woff + off_words;
-    uint64_t* sums = (uint64_t*)(roff + off_words);
-    uint32_t* next_call = roff + off_words + 2 * RO_MAX_BLOCKS;
+    // scratch: woff[n_calls + 1] | roff[n_calls + 1] | sums | the call counter
+    CallScratch s;
+    ZK_TRY(call_scratch(ctx, n_calls, 2, 4, &s));
+    uint32_t *woff = s.off[0], *roff = s.off[1], *next_call = s.extra;
+    uint64_t* sums = s.sums;
     const MrIn in{d_len, d_root, d_lvl, d_idx, d_mult, d_values, woff, roff, (uint32_t)n_calls, (uint32_t)n_words};
     // as many groups as calls, up to the 10 one-wave workgroups whose staging fits a CU's LDS: the counter balances the rest
     const size_t waves = std::min<size_t>((n_calls + 3) / 4, (size_t)std::max(ctx->cu_count, 1) * 10);
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    uint32_t* bad = (uint32_t*)flag;
-    KernelScope ks(ctx, "mmcs_rows_tracegen");
-    ZK_HIP_CHECK(ctx, hipMemsetAsync(d_trace, 0, (size_t)ZKHIP_MMCS_ROWS_WIDTH * N * 4, ctx->stream));
-    ZK_HIP_CHECK(ctx, hipMemsetAsync(d_hash_inputs, 0, 16 * N * 4, ctx->stream));
-    if (n_calls) {
-        ZK_HIP_CHECK(ctx, hipMemsetAsync(next_call, 0, 4, ctx->stream));
-        launch_call_offsets(ctx, d_len, n_calls, n_words, 0, true, sums, woff, bad);
-        launch_call_offsets(ctx, d_len, n_calls, N, 3, false, sums, roff, bad);
-        hipLaunchKernelGGL(k_mmcs_rows, dim3((unsigned)waves), dim3(64), 0, ctx->stream, in, N, next_call, d_trace, d_hash_inputs, d_digest, bad);
-    }
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return tracegen_finish(ctx, flag,
-                           "mmcs_rows_tracegen (a length of 0, lengths that do not sum to n_words, more rows than the trace has, or a word that is not a field element)");
+    return tracegen_frame(
+        ctx, "mmcs_rows_tracegen", {},
+        [&](uint32_t* bad) -> int {
+            ZK_HIP_CHECK(ctx, hipMemsetAsync(d_trace, 0, (size_t)ZKHIP_MMCS_ROWS_WIDTH * N * 4, ctx->stream));
+            ZK_HIP_CHECK(ctx, hipMemsetAsync(d_hash_inputs, 0, 16 * N * 4, ctx->stream));
+            if (!n_calls) return ZKHIP_OK;
+            ZK_HIP_CHECK(ctx, hipMemsetAsync(next_call, 0, 4, ctx->stream));
+            launch_call_offsets(ctx, d_len, n_calls, n_words, 0, true, sums, woff, bad);
+            launch_call_offsets(ctx, d_len, n_calls, N, 3, false, sums, roff, bad);
+            hipLaunchKernelGGL(k_mmcs_rows, dim3((unsigned)waves), dim3(64), 0, ctx->stream, in, N, next_call, d_trace, d_hash_inputs, d_digest, bad);
+            return ZKHIP_OK;
+        },
+        "mmcs_rows_tracegen (a length of 0, lengths that do not sum to n_words, more rows than the trace has, or a word that is not a field element)");
 }
 
 }  // extern "C"

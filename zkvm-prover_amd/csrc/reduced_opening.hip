@@ -220,13 +220,11 @@ int zkhip_reduced_opening_tracegen(zkhip_ctx* ctx, const uint32_t* d_alpha, cons
     const auto whole = [](size_t x) { return (x + RO_W - 1) / RO_W * RO_W; };
     const size_t rows_per_block = std::max<size_t>(whole((N + RO_MAX_BLOCKS - 1) / RO_MAX_BLOCKS), 2 * RO_W);
     const unsigned row_blocks = (unsigned)((N + rows_per_block - 1) / rows_per_block);
-    // scratch: off[n_calls + 1] | sums[RO_MAX_BLOCKS] (64 bits) | maps[row_blocks][8] | carry[row_blocks][4]
-    const size_t off_words = (n_calls + 1 + 3) / 4 * 4;
-    void* buf = nullptr;
-    ZK_TRY(get_scratch(ctx, 3, (off_words + 2 * (size_t)RO_MAX_BLOCKS + 12 * (size_t)RO_MAX_BLOCKS) * 4, &buf));
-    uint32_t* off = (uint32_t*)buf;
-    uint64_t* sums = (uint64_t*)(off + off_words);
-    uint32_t *maps = off + off_words + 2 * RO_MAX_BLOCKS, *carry = maps + 8 * RO_MAX_BLOCKS;
+    // scratch: off[n_calls + 1] | sums | maps[row_blocks][8] | carry[row_blocks][4]
+    CallScratch s;
+    ZK_TRY(call_scratch(ctx, n_calls, 1, 12 * (size_t)RO_MAX_BLOCKS, &s));
+    uint32_t *off = s.off[0], *maps = s.extra, *carry = maps + 8 * RO_MAX_BLOCKS;
+    uint64_t* sums = s.sums;
     const RoIn in{d_alpha, d_a, d_b, off, (uint32_t)n_calls, (uint32_t)n_elems};
     return tracegen_frame(
         ctx, "reduced_opening_tracegen", {},

@@ -82,6 +82,7 @@ int poseidon2_air_tracegen(zkhip_ctx* ctx, const uint32_t* d_inputs, size_t n_pe
     const size_t N = (size_t)1 << log_height;
     if (n_perms > N) return set_error(ctx, ZKHIP_ERR_INVALID, "poseidon2_air_tracegen: more permutations than rows");
     if (n_perms && !d_inputs) return set_error(ctx, ZKHIP_ERR_INVALID, "poseidon2_air_tracegen: null inputs");
+    // (outside tracegen_frame: the kernel refuses nothing, and a counter would cost a memset launch)
     KernelScope ks(ctx, "poseidon2_air_tracegen");
     hipLaunchKernelGGL(k_poseidon2_air_trace, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_inputs, n_perms, N,
                        d_trace);
@@ -135,18 +136,14 @@ void table_repr(zkhip_ctx* ctx, uint32_t* d, size_t words, bool to_m) {
 int range_counts_tracegen(zkhip_ctx* ctx, const uint32_t* d_values, size_t n, unsigned log_table, uint32_t* d_counts, int accumulate) {
     if (log_table > 27) return set_error(ctx, ZKHIP_ERR_INVALID, "range_counts_tracegen: log_table > 27");
     const size_t T = (size_t)1 << log_table;
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "range_counts_tracegen");
-    if (!accumulate) ZK_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, T * 4, ctx->stream));
-    else tables_repr(ctx, {{d_counts, T}}, false);
-    if (n) {
-        const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 32 - 1) / (256 * 32), 1024);
-        hipLaunchKernelGGL(k_range_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_values, n, log_table, d_counts, (uint32_t*)flag);
-    }
-    tables_repr(ctx, {{d_counts, T}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return tracegen_finish(ctx, flag, "range_counts_tracegen (values outside the table)");
+    return tracegen_count_frame(
+        ctx, "range_counts_tracegen", {d_counts, T}, accumulate,
+        [&](uint32_t* bad) {
+            if (!n) return;
+            const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 32 - 1) / (256 * 32), 1024);
+            hipLaunchKernelGGL(k_range_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_values, n, log_table, d_counts, bad);
+        },
+        "range_counts_tracegen (values outside the table)");
 }
 
 // ---- MMCS path chip: in-circuit verification of mixed-height Merkle openings (air.py mmcs_path_air) ------------------------------
@@ -246,6 +243,7 @@ extern "C" int zkhip_duplex_tracegen(zkhip_ctx* ctx, const uint32_t* d_n_observe
     if (!ctx || !d_trace || !d_hash_inputs || log_height > 27 || (n && (!d_n_observed || !d_observed || !d_n_sampled))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
     if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "duplex_tracegen: more duplexings than rows");
+    // (outside tracegen_frame: it reads its counter back itself, at once in either mode, for a message of its own -- docs/gaps.md)
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "duplex_tracegen");
@@ -266,6 +264,7 @@ extern "C" int zkhip_mmcs_path_tracegen(zkhip_ctx* ctx, const uint32_t* d_leaf, 
     if (!ctx || !d_trace || !d_hash_inputs || log_height > 27 || (n_paths && (!d_leaf || !d_index || !d_path_start || !d_step_kind || !d_step_digest)))
         return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
+    // (outside tracegen_frame: it reads its counter back itself, at once in either mode, for a message of its own -- docs/gaps.md)
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "mmcs_path_tracegen");

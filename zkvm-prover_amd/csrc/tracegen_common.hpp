@@ -1,13 +1,16 @@
 // tracegen_common.hpp -- what the trace generators' host sides share: the conversion of count tables out of Montgomery form and back
-// around a generator's increments, the launch frame of the limb chips, and the per-chip cache of AIR programs.
+// around a generator's increments, the kernels' check of a record word, the launch frame every generator with a device counter runs in, and
+// the per-chip cache of AIR programs.
 #pragma once
 #include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/zkhip_air.hpp"
+#include "babybear.hpp"
 #include "zkhip_internal.hpp"
 
 namespace zk {
@@ -25,6 +28,12 @@ inline void tables_repr(zkhip_ctx* ctx, std::initializer_list<TableRef> tabs, bo
     for (const TableRef& t : tabs) table_repr(ctx, t.d, t.words, to_monty);
 }
 
+// a record word on the device: refused (counted, and read as 0) unless it is a field element; returns Montgomery form
+__device__ __forceinline__ uint32_t field_word(uint32_t v, uint32_t* bad) {
+    if (v >= P) atomicAdd(bad, 1u), v = 0;
+    return to_monty(v);
+}
+
 // the range (or, one column further, XOR) multiplicities of the 8-bit table
 constexpr size_t BITWISE_WORDS = (size_t)1 << 16;
 
@@ -36,18 +45,46 @@ inline int tracegen_shape(zkhip_ctx* ctx, const std::string& name, size_t n, siz
     return ZKHIP_OK;
 }
 
-// One generator call under the profile scope `name`: the tables out of Montgomery form, launch(bad) for the trace kernel with the device
-// counter of refused records, the tables back, and the verdict (`refusal` names what the kernel refuses).
+// a launch callback's status: one that returns nothing has issued kernels only, and those are checked by the frame
+template <class Launch>
+int tracegen_launch(Launch& launch, uint32_t* bad) {
+    if constexpr (std::is_void_v<decltype(launch(bad))>) {
+        launch(bad);
+        return ZKHIP_OK;
+    } else {
+        return launch(bad);
+    }
+}
+
+// One generator call under the profile scope `name`: the device counter of refused records, the tables out of Montgomery form,
+// launch(bad) for the generator's kernels (and memsets: a callback that can fail returns its status), the tables back, and the verdict
+// (`refusal` names what the kernels refuse).  The order is what the deferred checks rely on: the counter before the scope, the tables
+// back before the error check, the verdict last.
 template <class Launch>
 int tracegen_frame(zkhip_ctx* ctx, const char* name, std::initializer_list<TableRef> tabs, Launch&& launch, const std::string& refusal) {
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, name);
     tables_repr(ctx, tabs, false);
-    launch((uint32_t*)flag);
+    ZK_TRY(tracegen_launch(launch, (uint32_t*)flag));
     tables_repr(ctx, tabs, true);
     ZK_HIP_CHECK(ctx, hipGetLastError());
     return tracegen_finish(ctx, flag, refusal);
+}
+
+// The frame of a generator whose whole trace is the count table: counted from zero, or (accumulate) on top of what the table holds
+template <class Launch>
+int tracegen_count_frame(zkhip_ctx* ctx, const char* name, TableRef tab, int accumulate, Launch&& launch, const std::string& refusal) {
+    return tracegen_frame(
+        ctx, name, {},
+        [&](uint32_t* bad) -> int {
+            if (!accumulate) ZK_HIP_CHECK(ctx, hipMemsetAsync(tab.d, 0, tab.words * 4, ctx->stream));
+            else tables_repr(ctx, {tab}, false);
+            ZK_TRY(tracegen_launch(launch, bad));
+            tables_repr(ctx, {tab}, true);
+            return ZKHIP_OK;
+        },
+        refusal);
 }
 
 // AIR programs of one chip by key (modulus, buses, ...), built at first use and kept for the life of the process: the zkhip_air handed

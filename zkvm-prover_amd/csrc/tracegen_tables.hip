@@ -106,8 +106,6 @@ __global__ __launch_bounds__(256) void k_boundary_fill(const uint64_t* __restric
     for (int q = 0; q < ZKHIP_MEMORY_BOUNDARY_WIDTH; q++) trace[(size_t)q * N + r] = c[q];
 }
 
-int finish_counts(zkhip_ctx* ctx, void* flag, const char* what) { return tracegen_finish(ctx, flag, std::string(what) + " (requests outside the table)"); }
-
 }  // namespace
 }  // namespace zk
 
@@ -119,18 +117,14 @@ extern "C" int zkhip_range_tuple_counts_tracegen(zkhip_ctx* ctx, const uint32_t*
     if (!ctx || !d_counts || (n && (!d_x || !d_y)) || size_x == 0 || size_y == 0) return ZKHIP_ERR_INVALID;
     const size_t T = (size_t)size_x * size_y;
     if (T > ((size_t)1 << 27) || (T & (T - 1))) return set_error(ctx, ZKHIP_ERR_INVALID, "range tuple table: size_x * size_y must be a power of two <= 2^27");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "range_tuple_tracegen");
-    if (!accumulate) ZK_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, T * 4, ctx->stream));
-    else tables_repr(ctx, {{d_counts, T}}, false);
-    if (n) {
-        const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
-        hipLaunchKernelGGL(k_tuple_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_x, d_y, n, size_x, size_y, d_counts, (uint32_t*)flag);
-    }
-    tables_repr(ctx, {{d_counts, T}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "range_tuple_counts_tracegen");
+    return tracegen_count_frame(
+        ctx, "range_tuple_tracegen", {d_counts, T}, accumulate,
+        [&](uint32_t* bad) {
+            if (!n) return;
+            const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
+            hipLaunchKernelGGL(k_tuple_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_x, d_y, n, size_x, size_y, d_counts, bad);
+        },
+        "range_tuple_counts_tracegen (requests outside the table)");
 }
 
 extern "C" int zkhip_bitwise_lookup_tracegen(zkhip_ctx* ctx, const uint32_t* d_x, const uint32_t* d_y, const uint32_t* d_op, size_t n,
@@ -138,18 +132,14 @@ extern "C" int zkhip_bitwise_lookup_tracegen(zkhip_ctx* ctx, const uint32_t* d_x
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || (n && (!d_x || !d_y || !d_op)) || num_bits == 0 || num_bits > 12) return ZKHIP_ERR_INVALID;
     const size_t T = (size_t)2 << (2 * num_bits);  // two columns
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "bitwise_lookup_tracegen");
-    if (!accumulate) ZK_HIP_CHECK(ctx, hipMemsetAsync(d_trace, 0, T * 4, ctx->stream));
-    else tables_repr(ctx, {{d_trace, T}}, false);
-    if (n) {
-        const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
-        hipLaunchKernelGGL(k_bitwise_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_x, d_y, d_op, n, num_bits, d_trace, (uint32_t*)flag);
-    }
-    tables_repr(ctx, {{d_trace, T}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "bitwise_lookup_tracegen");
+    return tracegen_count_frame(
+        ctx, "bitwise_lookup_tracegen", {d_trace, T}, accumulate,
+        [&](uint32_t* bad) {
+            if (!n) return;
+            const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
+            hipLaunchKernelGGL(k_bitwise_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_x, d_y, d_op, n, num_bits, d_trace, bad);
+        },
+        "bitwise_lookup_tracegen (requests outside the table)");
 }
 
 extern "C" int zkhip_memory_boundary_tracegen(zkhip_ctx* ctx, const uint32_t* d_addr_space, const uint32_t* d_pointer,
@@ -161,6 +151,7 @@ extern "C" int zkhip_memory_boundary_tracegen(zkhip_ctx* ctx, const uint32_t* d_
     const size_t N = (size_t)1 << log_height;
     if (n > N || (n && (!d_addr_space || !d_pointer || !d_initial || !d_final || !d_timestamp)))
         return set_error(ctx, ZKHIP_ERR_INVALID, "memory_boundary_tracegen: more records than rows");
+    // (outside tracegen_frame: it reads its counter back itself, for a message of its own -- docs/gaps.md)
     void* flag = nullptr;
     ZK_TRY(tracegen_flag(ctx, &flag));
     KernelScope ks(ctx, "memory_boundary_tracegen");
@@ -239,18 +230,15 @@ extern "C" int zkhip_rv32_alu_tracegen(zkhip_ctx* ctx, const uint32_t* d_opcode,
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_bitwise_trace || log_height > 27 || (n && (!d_opcode || !d_b || !d_c))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_alu_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "rv32_alu_tracegen");
+    ZK_TRY(tracegen_shape(ctx, "rv32_alu_tracegen", n, N, 0, 0, 0));
     // the XOR multiplicity column of the 8-bit bitwise lookup table (column 1 of its 2 x 2^16 trace): Montgomery -> counts -> Montgomery
     uint32_t* xor_col = d_bitwise_trace + (1u << 16);
-    tables_repr(ctx, {{xor_col, (size_t)1 << 16}}, false);
-    hipLaunchKernelGGL(k_rv32_alu, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, xor_col,
-                       (uint32_t*)flag);
-    tables_repr(ctx, {{xor_col, (size_t)1 << 16}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "rv32_alu_tracegen (opcode > 4)");
+    return tracegen_frame(
+        ctx, "rv32_alu_tracegen", {{xor_col, BITWISE_WORDS}},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_rv32_alu, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, xor_col, bad);
+        },
+        "rv32_alu_tracegen (opcode > 4) (requests outside the table)");
 }
 
 // ---- RV32 multiplication core (OpenVM rv32im MultiplicationCoreAir: MUL on 4 x 8-bit limbs) ----------------------------------------
@@ -301,8 +289,9 @@ extern "C" int zkhip_rv32_mul_tracegen(zkhip_ctx* ctx, const uint32_t* d_b, cons
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_tuple_counts || log_height > 27 || (n && (!d_b || !d_c))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height, T = (size_t)size_x * size_y;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_mul_tracegen: more records than rows");
+    ZK_TRY(tracegen_shape(ctx, "rv32_mul_tracegen", n, N, 0, 0, 0));
     if (size_x < 256 || size_y < 1024 || T > ((size_t)1 << 27)) return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_mul_tracegen: the tuple table must cover (limb < 256, carry < 1024)");
+    // (outside tracegen_frame: the kernel refuses nothing, and a counter would cost a memset launch)
     KernelScope ks(ctx, "rv32_mul_tracegen");
     tables_repr(ctx, {{d_tuple_counts, T}}, false);
     hipLaunchKernelGGL(k_rv32_mul, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_b, d_c, n, N, d_trace, d_tuple_counts, size_y);
@@ -358,16 +347,17 @@ extern "C" int zkhip_program_freq_tracegen(zkhip_ctx* ctx, const uint32_t* d_pc_
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_freq || log_height > 27 || (n && !d_pc_index)) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "program_freq_tracegen");
-    ZK_HIP_CHECK(ctx, hipMemsetAsync(d_freq, 0, N * 4, ctx->stream));
-    if (n)
-        hipLaunchKernelGGL(k_program_freq, dim3((unsigned)std::min<size_t>((n + 256 * 32 - 1) / (256 * 32), 1024)), dim3(256), 0, ctx->stream, d_pc_index, n, N,
-                           d_freq, (uint32_t*)flag);
-    table_repr(ctx, d_freq, N, true);   // (counted from zero: converted in either table mode)
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "program_freq_tracegen (instruction index beyond the program)");
+    return tracegen_frame(
+        ctx, "program_freq_tracegen", {},
+        [&](uint32_t* bad) -> int {
+            ZK_HIP_CHECK(ctx, hipMemsetAsync(d_freq, 0, N * 4, ctx->stream));
+            if (n)
+                hipLaunchKernelGGL(k_program_freq, dim3((unsigned)std::min<size_t>((n + 256 * 32 - 1) / (256 * 32), 1024)), dim3(256), 0, ctx->stream, d_pc_index, n, N,
+                                   d_freq, bad);
+            table_repr(ctx, d_freq, N, true);   // (counted from zero: converted in either table mode)
+            return ZKHIP_OK;
+        },
+        "program_freq_tracegen (instruction index beyond the program) (requests outside the table)");
 }
 
 extern "C" int zkhip_exec_frame_tracegen(zkhip_ctx* ctx, const uint32_t* d_pc_index, size_t n, const uint32_t* d_program, size_t n_program,
@@ -375,14 +365,13 @@ extern "C" int zkhip_exec_frame_tracegen(zkhip_ctx* ctx, const uint32_t* d_pc_in
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_program || log_height > 27 || (n && !d_pc_index)) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "exec_frame_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "exec_frame_tracegen");
-    hipLaunchKernelGGL(k_exec_frames, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_pc_index, n, d_program, n_program, N, d_trace,
-                       (uint32_t*)flag);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "exec_frame_tracegen (instruction index beyond the program)");
+    ZK_TRY(tracegen_shape(ctx, "exec_frame_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "exec_frame_tracegen", {},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_exec_frames, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_pc_index, n, d_program, n_program, N, d_trace, bad);
+        },
+        "exec_frame_tracegen (instruction index beyond the program) (requests outside the table)");
 }
 
 // ---- RV32 less-than core (OpenVM rv32im LessThanCoreAir<4, 8>: SLT / SLTU) -------------------------------------------------------
@@ -445,17 +434,14 @@ extern "C" int zkhip_rv32_lt_tracegen(zkhip_ctx* ctx, const uint32_t* d_opcode, 
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_bitwise_trace || log_height > 27 || (n && (!d_opcode || !d_b || !d_c))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_lt_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "rv32_lt_tracegen");
+    ZK_TRY(tracegen_shape(ctx, "rv32_lt_tracegen", n, N, 0, 0, 0));
     // the RANGE multiplicity column of the 8-bit bitwise lookup table (column 0 of its 2 x 2^16 trace)
-    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, false);
-    hipLaunchKernelGGL(k_rv32_lt, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, d_bitwise_trace,
-                       (uint32_t*)flag);
-    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "rv32_lt_tracegen (opcode > 1)");
+    return tracegen_frame(
+        ctx, "rv32_lt_tracegen", {{d_bitwise_trace, BITWISE_WORDS}},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_rv32_lt, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, d_bitwise_trace, bad);
+        },
+        "rv32_lt_tracegen (opcode > 1) (requests outside the table)");
 }
 
 // ---- memory access chip: the offline memory-checking argument's per-access rows ---------------------------------------------------
@@ -498,14 +484,14 @@ extern "C" int zkhip_memory_access_tracegen(zkhip_ctx* ctx, const uint32_t* d_ad
     if (!ctx || !d_trace || log_height > 27 || (n && (!d_addr_space || !d_pointer || !d_prev_data || !d_prev_ts || !d_data || !d_ts || !d_is_read)))
         return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "memory_access_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "memory_access_tracegen");
-    hipLaunchKernelGGL(k_memory_access, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_addr_space, d_pointer, d_prev_data, d_prev_ts,
-                       d_data, d_ts, d_is_read, n, N, d_trace, (uint32_t*)flag);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "memory_access_tracegen (value above 16 bits, time not moving forward, or a read that changes its cell)");
+    ZK_TRY(tracegen_shape(ctx, "memory_access_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "memory_access_tracegen", {},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_memory_access, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_addr_space, d_pointer, d_prev_data, d_prev_ts, d_data, d_ts,
+                               d_is_read, n, N, d_trace, bad);
+        },
+        "memory_access_tracegen (value above 16 bits, time not moving forward, or a read that changes its cell) (requests outside the table)");
 }
 
 // ---- RV32 shift core (OpenVM rv32im ShiftCoreAir<4, 8>: SLL / SRL / SRA) -----------------------------------------------------------
@@ -573,16 +559,14 @@ extern "C" int zkhip_rv32_shift_tracegen(zkhip_ctx* ctx, const uint32_t* d_opcod
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_bitwise_trace || log_height > 27 || (n && (!d_opcode || !d_b || !d_c))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_shift_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "rv32_shift_tracegen");
-    tables_repr(ctx, {{d_bitwise_trace, (size_t)2 << 16}}, false);  // both columns
-    hipLaunchKernelGGL(k_rv32_shift, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace,
-                       d_bitwise_trace, d_bitwise_trace + (1u << 16), (uint32_t*)flag);
-    tables_repr(ctx, {{d_bitwise_trace, (size_t)2 << 16}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "rv32_shift_tracegen (opcode > 2)");
+    ZK_TRY(tracegen_shape(ctx, "rv32_shift_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "rv32_shift_tracegen", {{d_bitwise_trace, 2 * BITWISE_WORDS}},   // both columns
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_rv32_shift, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace,
+                               d_bitwise_trace, d_bitwise_trace + (1u << 16), bad);
+        },
+        "rv32_shift_tracegen (opcode > 2) (requests outside the table)");
 }
 
 // ---- RV32 branch-equal core (OpenVM rv32im BranchEqualCoreAir<4>: BEQ / BNE) ------------------------------------------------------
@@ -631,14 +615,13 @@ extern "C" int zkhip_rv32_branch_eq_tracegen(zkhip_ctx* ctx, const uint32_t* d_o
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || log_height > 27 || (n && (!d_opcode || !d_a || !d_b || !d_imm))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_branch_eq_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "rv32_branch_eq_tracegen");
-    hipLaunchKernelGGL(k_rv32_branch_eq, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_opcode, d_a, d_b, d_imm, n, N, d_trace,
-                       (uint32_t*)flag);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "rv32_branch_eq_tracegen (opcode > 1 or offset not a field element)");
+    ZK_TRY(tracegen_shape(ctx, "rv32_branch_eq_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "rv32_branch_eq_tracegen", {},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_rv32_branch_eq, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_opcode, d_a, d_b, d_imm, n, N, d_trace, bad);
+        },
+        "rv32_branch_eq_tracegen (opcode > 1 or offset not a field element) (requests outside the table)");
 }
 
 // ---- RV32 branch-less-than core (OpenVM rv32im BranchLessThanCoreAir<4, 8>: BLT / BLTU / BGE / BGEU) -------------------------------
@@ -698,16 +681,14 @@ extern "C" int zkhip_rv32_branch_lt_tracegen(zkhip_ctx* ctx, const uint32_t* d_o
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_bitwise_trace || log_height > 27 || (n && (!d_opcode || !d_a || !d_b || !d_imm))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_branch_lt_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "rv32_branch_lt_tracegen");
-    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, false);
-    hipLaunchKernelGGL(k_rv32_branch_lt, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_a, d_b, d_imm, n, N, d_trace,
-                       d_bitwise_trace, (uint32_t*)flag);
-    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "rv32_branch_lt_tracegen (opcode > 3 or offset not a field element)");
+    ZK_TRY(tracegen_shape(ctx, "rv32_branch_lt_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "rv32_branch_lt_tracegen", {{d_bitwise_trace, BITWISE_WORDS}},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_rv32_branch_lt, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_a, d_b, d_imm, n, N, d_trace,
+                               d_bitwise_trace, bad);
+        },
+        "rv32_branch_lt_tracegen (opcode > 3 or offset not a field element) (requests outside the table)");
 }
 
 // ---- RV32 JAL / LUI, AUIPC and JALR cores (OpenVM rv32im Rv32JalLuiCoreAir, Rv32AuipcCoreAir, Rv32JalrCoreAir) ---------------------
@@ -816,20 +797,6 @@ __global__ __launch_bounds__(256) void k_rv32_jalr(const uint32_t* __restrict__ 
     hot_flush(hk_r, hc_r, range_counts);
 }
 
-// shared launch frame of the three: flag, table to counts, the chip's kernel, table back to Montgomery form
-template <typename Launch>
-int jump_chip_tracegen(zkhip_ctx* ctx, const char* name, size_t n, unsigned log_height, uint32_t* d_bitwise_trace, Launch&& launch) {
-    const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, name);
-    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, false);
-    launch(dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), N, (uint32_t*)flag);
-    tables_repr(ctx, {{d_bitwise_trace, (size_t)1 << 16}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, name);
-}
 }  // namespace
 }  // namespace zk
 
@@ -837,27 +804,44 @@ extern "C" int zkhip_rv32_jal_lui_tracegen(zkhip_ctx* ctx, const uint32_t* d_opc
                                            unsigned log_height, uint32_t* d_trace, uint32_t* d_bitwise_trace) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_bitwise_trace || log_height > 27 || (n && (!d_opcode || !d_pc || !d_imm))) return ZKHIP_ERR_INVALID;
-    return jump_chip_tracegen(ctx, "rv32_jal_lui_tracegen", n, log_height, d_bitwise_trace, [&](dim3 grid, size_t N, uint32_t* flag) {
-        hipLaunchKernelGGL(k_rv32_jal_lui, grid, dim3(256), 0, ctx->stream, d_opcode, d_pc, d_imm, n, N, d_trace, d_bitwise_trace, flag);
-    });
+    const size_t N = (size_t)1 << log_height;
+    ZK_TRY(tracegen_shape(ctx, "rv32_jal_lui_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "rv32_jal_lui_tracegen", {{d_bitwise_trace, BITWISE_WORDS}},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_rv32_jal_lui, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_pc, d_imm, n, N, d_trace,
+                               d_bitwise_trace, bad);
+        },
+        "rv32_jal_lui_tracegen (requests outside the table)");
 }
 
 extern "C" int zkhip_rv32_auipc_tracegen(zkhip_ctx* ctx, const uint32_t* d_pc, const uint32_t* d_imm, size_t n, unsigned log_height, uint32_t* d_trace,
                                          uint32_t* d_bitwise_trace) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_bitwise_trace || log_height > 27 || (n && (!d_pc || !d_imm))) return ZKHIP_ERR_INVALID;
-    return jump_chip_tracegen(ctx, "rv32_auipc_tracegen", n, log_height, d_bitwise_trace, [&](dim3 grid, size_t N, uint32_t* flag) {
-        hipLaunchKernelGGL(k_rv32_auipc, grid, dim3(256), 0, ctx->stream, d_pc, d_imm, n, N, d_trace, d_bitwise_trace, flag);
-    });
+    const size_t N = (size_t)1 << log_height;
+    ZK_TRY(tracegen_shape(ctx, "rv32_auipc_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "rv32_auipc_tracegen", {{d_bitwise_trace, BITWISE_WORDS}},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_rv32_auipc, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_pc, d_imm, n, N, d_trace, d_bitwise_trace, bad);
+        },
+        "rv32_auipc_tracegen (requests outside the table)");
 }
 
 extern "C" int zkhip_rv32_jalr_tracegen(zkhip_ctx* ctx, const uint32_t* d_pc, const uint32_t* d_rs1, const uint32_t* d_imm, size_t n,
                                         unsigned log_height, uint32_t* d_trace, uint32_t* d_bitwise_trace) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_bitwise_trace || log_height > 27 || (n && (!d_pc || !d_rs1 || !d_imm))) return ZKHIP_ERR_INVALID;
-    return jump_chip_tracegen(ctx, "rv32_jalr_tracegen", n, log_height, d_bitwise_trace, [&](dim3 grid, size_t N, uint32_t* flag) {
-        hipLaunchKernelGGL(k_rv32_jalr, grid, dim3(256), 0, ctx->stream, d_pc, d_rs1, d_imm, n, N, d_trace, d_bitwise_trace, flag);
-    });
+    const size_t N = (size_t)1 << log_height;
+    ZK_TRY(tracegen_shape(ctx, "rv32_jalr_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "rv32_jalr_tracegen", {{d_bitwise_trace, BITWISE_WORDS}},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_rv32_jalr, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_pc, d_rs1, d_imm, n, N, d_trace,
+                               d_bitwise_trace, bad);
+        },
+        "rv32_jalr_tracegen (requests outside the table)");
 }
 
 // ---- RV32 high-multiplication core (OpenVM rv32im MulHCoreAir<4, 8>: MULH / MULHSU / MULHU) ------------------------------------------
@@ -923,18 +907,16 @@ extern "C" int zkhip_rv32_mulh_tracegen(zkhip_ctx* ctx, const uint32_t* d_opcode
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_tuple_counts || !d_bitwise_trace || log_height > 27 || (n && (!d_opcode || !d_b || !d_c))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height, T = (size_t)size_x * size_y;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_mulh_tracegen: more records than rows");
+    ZK_TRY(tracegen_shape(ctx, "rv32_mulh_tracegen", n, N, 0, 0, 0));
     if (size_x < 256 || size_y < 2048 || T > ((size_t)1 << 27))
         return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_mulh_tracegen: the tuple table must cover (limb < 256, carry < 2048)");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "rv32_mulh_tracegen");
-    tables_repr(ctx, {{d_tuple_counts, T}, {d_bitwise_trace, (size_t)1 << 16}}, false);
-    hipLaunchKernelGGL(k_rv32_mulh, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, d_tuple_counts, size_y,
-                       d_bitwise_trace, (uint32_t*)flag);
-    tables_repr(ctx, {{d_tuple_counts, T}, {d_bitwise_trace, (size_t)1 << 16}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "rv32_mulh_tracegen (opcode > 2)");
+    return tracegen_frame(
+        ctx, "rv32_mulh_tracegen", {{d_tuple_counts, T}, {d_bitwise_trace, BITWISE_WORDS}},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_rv32_mulh, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, d_tuple_counts,
+                               size_y, d_bitwise_trace, bad);
+        },
+        "rv32_mulh_tracegen (opcode > 2) (requests outside the table)");
 }
 
 // ---- RV32 load/store cores (OpenVM rv32im LoadStoreCoreAir<4> + LoadSignExtendCoreAir<4, 8>) in one chip -------------------------------
@@ -993,9 +975,15 @@ extern "C" int zkhip_rv32_loadstore_tracegen(zkhip_ctx* ctx, const uint32_t* d_c
                                              unsigned log_height, uint32_t* d_trace, uint32_t* d_bitwise_trace) {
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_bitwise_trace || log_height > 27 || (n && (!d_case || !d_read || !d_prev))) return ZKHIP_ERR_INVALID;
-    return jump_chip_tracegen(ctx, "rv32_loadstore_tracegen", n, log_height, d_bitwise_trace, [&](dim3 grid, size_t N, uint32_t* flag) {
-        hipLaunchKernelGGL(k_rv32_loadstore, grid, dim3(256), 0, ctx->stream, d_case, d_read, d_prev, n, N, d_trace, d_bitwise_trace, flag);
-    });
+    const size_t N = (size_t)1 << log_height;
+    ZK_TRY(tracegen_shape(ctx, "rv32_loadstore_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "rv32_loadstore_tracegen", {{d_bitwise_trace, BITWISE_WORDS}},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_rv32_loadstore, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_case, d_read, d_prev, n, N, d_trace,
+                               d_bitwise_trace, bad);
+        },
+        "rv32_loadstore_tracegen (requests outside the table)");
 }
 
 // ---- RV32 division core (the job of OpenVM rv32im DivRemCoreAir<4, 8>: DIV / DIVU / REM / REMU) ---------------------------------------
@@ -1088,18 +1076,16 @@ extern "C" int zkhip_rv32_divrem_tracegen(zkhip_ctx* ctx, const uint32_t* d_opco
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_tuple_counts || !d_bitwise_trace || log_height > 27 || (n && (!d_opcode || !d_b || !d_c))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height, T = (size_t)size_x * size_y;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_divrem_tracegen: more records than rows");
+    ZK_TRY(tracegen_shape(ctx, "rv32_divrem_tracegen", n, N, 0, 0, 0));
     if (size_x < 256 || size_y < 2048 || T > ((size_t)1 << 27))
         return set_error(ctx, ZKHIP_ERR_INVALID, "rv32_divrem_tracegen: the tuple table must cover (limb < 256, carry < 2048)");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "rv32_divrem_tracegen");
-    tables_repr(ctx, {{d_tuple_counts, T}, {d_bitwise_trace, (size_t)1 << 16}}, false);
-    hipLaunchKernelGGL(k_rv32_divrem, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, d_tuple_counts,
-                       size_y, d_bitwise_trace, (uint32_t*)flag);
-    tables_repr(ctx, {{d_tuple_counts, T}, {d_bitwise_trace, (size_t)1 << 16}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "rv32_divrem_tracegen (opcode > 3)");
+    return tracegen_frame(
+        ctx, "rv32_divrem_tracegen", {{d_tuple_counts, T}, {d_bitwise_trace, BITWISE_WORDS}},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_rv32_divrem, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace,
+                               d_tuple_counts, size_y, d_bitwise_trace, bad);
+        },
+        "rv32_divrem_tracegen (opcode > 3) (requests outside the table)");
 }
 
 // ---- NATIVE chips: base-field and extension-field arithmetic (OpenVM native FieldArithmeticCoreAir / FieldExtensionCoreAir) -----------
@@ -1166,13 +1152,11 @@ extern "C" int zkhip_field_arith_tracegen(zkhip_ctx* ctx, const uint32_t* d_opco
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || log_height > 27 || (n && (!d_opcode || !d_b || !d_c))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "field_arith_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "field_arith_tracegen");
-    hipLaunchKernelGGL(k_field_arith, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, (uint32_t*)flag);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "field_arith_tracegen (opcode > 3, operand not a field element, or division by zero)");
+    ZK_TRY(tracegen_shape(ctx, "field_arith_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "field_arith_tracegen", {},
+        [&](uint32_t* bad) { hipLaunchKernelGGL(k_field_arith, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_opcode, d_b, d_c, n, N, d_trace, bad); },
+        "field_arith_tracegen (opcode > 3, operand not a field element, or division by zero) (requests outside the table)");
 }
 
 extern "C" int zkhip_field_ext_tracegen(zkhip_ctx* ctx, const uint32_t* d_opcode, const uint32_t* d_x, const uint32_t* d_y, size_t n, unsigned log_height,
@@ -1180,14 +1164,12 @@ extern "C" int zkhip_field_ext_tracegen(zkhip_ctx* ctx, const uint32_t* d_opcode
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || log_height > 27 || (n && (!d_opcode || !d_x || !d_y))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "field_ext_tracegen: more records than rows");
+    ZK_TRY(tracegen_shape(ctx, "field_ext_tracegen", n, N, 0, 0, 0));
     if (((uintptr_t)d_x | (uintptr_t)d_y) & 15u) return set_error(ctx, ZKHIP_ERR_INVALID, "field_ext_tracegen: operands must be 16-byte aligned");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "field_ext_tracegen");
-    hipLaunchKernelGGL(k_field_ext, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_opcode, d_x, d_y, n, N, d_trace, (uint32_t*)flag);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "field_ext_tracegen (opcode > 3, operand not a field element, or division by zero)");
+    return tracegen_frame(
+        ctx, "field_ext_tracegen", {},
+        [&](uint32_t* bad) { hipLaunchKernelGGL(k_field_ext, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_opcode, d_x, d_y, n, N, d_trace, bad); },
+        "field_ext_tracegen (opcode > 3, operand not a field element, or division by zero) (requests outside the table)");
 }
 
 // ---- variable range checker (OpenVM VariableRangeCheckerChip): one table for x < 2^bits, bits <= max_bits ------------------------------
@@ -1218,18 +1200,14 @@ extern "C" int zkhip_var_range_counts_tracegen(zkhip_ctx* ctx, const uint32_t* d
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_counts || (n && !d_values) || max_bits > 26) return ZKHIP_ERR_INVALID;
     const size_t T = (size_t)1 << (max_bits + 1);
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "var_range_counts_tracegen");
-    if (!accumulate) ZK_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, T * 4, ctx->stream));
-    else tables_repr(ctx, {{d_counts, T}}, false);
-    if (n) {
-        const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
-        hipLaunchKernelGGL(k_var_range_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_values, d_bits, const_bits, n, max_bits, d_counts, (uint32_t*)flag);
-    }
-    tables_repr(ctx, {{d_counts, T}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "var_range_counts_tracegen (bits > max_bits or value >= 2^bits)");
+    return tracegen_count_frame(
+        ctx, "var_range_counts_tracegen", {d_counts, T}, accumulate,
+        [&](uint32_t* bad) {
+            if (!n) return;
+            const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
+            hipLaunchKernelGGL(k_var_range_counts, dim3(blocks), dim3(256), 0, ctx->stream, d_values, d_bits, const_bits, n, max_bits, d_counts, bad);
+        },
+        "var_range_counts_tracegen (bits > max_bits or value >= 2^bits) (requests outside the table)");
 }
 
 // ---- native CASTF core (OpenVM native CastFCoreAir): a field element below 2^30 to limbs of 8, 8, 8, 6 bits -----------------------------
@@ -1268,15 +1246,13 @@ extern "C" int zkhip_castf_tracegen(zkhip_ctx* ctx, const uint32_t* d_x, size_t 
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || !d_var_range_counts || log_height > 27 || max_bits < 8 || max_bits > 26 || (n && !d_x)) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height, T = (size_t)1 << (max_bits + 1);
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "castf_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "castf_tracegen");
-    tables_repr(ctx, {{d_var_range_counts, T}}, false);
-    hipLaunchKernelGGL(k_castf, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_x, n, N, d_trace, d_var_range_counts, (uint32_t*)flag);
-    tables_repr(ctx, {{d_var_range_counts, T}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "castf_tracegen (value >= 2^30)");
+    ZK_TRY(tracegen_shape(ctx, "castf_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "castf_tracegen", {{d_var_range_counts, T}},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_castf, dim3((unsigned)std::min<size_t>((N + 255) / 256, HOT_MAX_BLOCKS)), dim3(256), 0, ctx->stream, d_x, n, N, d_trace, d_var_range_counts, bad);
+        },
+        "castf_tracegen (value >= 2^30) (requests outside the table)");
 }
 
 // ---- FRI fold chip (air.py fri_fold_air): one arity-2 folding step per row, generated from the step's data -----------------------------
@@ -1323,14 +1299,13 @@ extern "C" int zkhip_fri_fold_chip_tracegen(zkhip_ctx* ctx, const uint32_t* d_e0
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || log_height > 27 || (n && (!d_e0 || !d_e1 || !d_beta || !d_k || !d_log_n_out))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "fri_fold_chip_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "fri_fold_chip_tracegen");
-    hipLaunchKernelGGL(k_fri_fold_chip, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_e0, d_e1, d_beta, d_k, d_log_n_out, n, N, d_trace,
-                       (uint32_t*)flag);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "fri_fold_chip_tracegen (a value that is not a field element, or an index outside its layer)");
+    ZK_TRY(tracegen_shape(ctx, "fri_fold_chip_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "fri_fold_chip_tracegen", {},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_fri_fold_chip, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_e0, d_e1, d_beta, d_k, d_log_n_out, n, N, d_trace, bad);
+        },
+        "fri_fold_chip_tracegen (a value that is not a field element, or an index outside its layer) (requests outside the table)");
 }
 
 // ---- domain-point chip (air.py domain_point_air): x^-1 of a FRI pair from the bits of its index ------------------------------------------
@@ -1363,11 +1338,9 @@ extern "C" int zkhip_domain_point_tracegen(zkhip_ctx* ctx, const uint32_t* d_k, 
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || log_height > 27 || (n && (!d_k || !d_mult))) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "domain_point_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "domain_point_tracegen");
-    hipLaunchKernelGGL(k_domain_point, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_k, d_mult, n, N, d_trace, (uint32_t*)flag);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return finish_counts(ctx, flag, "domain_point_tracegen (a pair index of more than 26 bits or a multiplicity that is not a field element)");
+    ZK_TRY(tracegen_shape(ctx, "domain_point_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "domain_point_tracegen", {},
+        [&](uint32_t* bad) { hipLaunchKernelGGL(k_domain_point, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_k, d_mult, n, N, d_trace, bad); },
+        "domain_point_tracegen (a pair index of more than 26 bits or a multiplicity that is not a field element) (requests outside the table)");
 }

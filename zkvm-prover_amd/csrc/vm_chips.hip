@@ -261,8 +261,6 @@ __global__ __launch_bounds__(256) void k_vm_castf(const uint32_t* __restrict__ r
     for (unsigned q = 0; q < vmc::CASTF_WIDTH; q++) trace[(size_t)q * N + r] = col[q];
 }
 
-int check_flag(zkhip_ctx* ctx, void* flag, const char* what) { return tracegen_finish(ctx, flag, what); }
-
 }  // namespace
 }  // namespace zk
 
@@ -374,14 +372,14 @@ int zkhip_vm_frame_tracegen(zkhip_ctx* ctx, const uint32_t* d_pc_index, const ui
         (n && (!d_pc_index || !d_x || !d_y || !d_z || !d_rd_prev || !d_pc_inc || !d_prev_ts_rs1 || !d_prev_ts_rs2 || !d_prev_ts_rd)))
         return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "vm_frame_tracegen: more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "vm_frame_tracegen");
-    hipLaunchKernelGGL(k_vm_frame, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_pc_index, d_x, d_y, d_z, d_rd_prev, d_pc_inc,
-                       d_prev_ts_rs1, d_prev_ts_rs2, d_prev_ts_rd, n, d_program, n_program, N, d_trace, (uint32_t*)flag);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return check_flag(ctx, flag, "vm_frame_tracegen (instruction index beyond the program, a pc step that is not a field element, or a timestamp gap out of range)");
+    ZK_TRY(tracegen_shape(ctx, "vm_frame_tracegen", n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, "vm_frame_tracegen", {},
+        [&](uint32_t* bad) {
+            hipLaunchKernelGGL(k_vm_frame, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_pc_index, d_x, d_y, d_z, d_rd_prev, d_pc_inc, d_prev_ts_rs1,
+                               d_prev_ts_rs2, d_prev_ts_rd, n, d_program, n_program, N, d_trace, bad);
+        },
+        "vm_frame_tracegen (instruction index beyond the program, a pc step that is not a field element, or a timestamp gap out of range)");
 }
 
 int zkhip_vm_loadstore_tracegen(zkhip_ctx* ctx, const uint32_t* d_case, const uint32_t* d_read, const uint32_t* d_prev, const uint32_t* d_ts,
@@ -393,12 +391,10 @@ int zkhip_vm_loadstore_tracegen(zkhip_ctx* ctx, const uint32_t* d_case, const ui
     // the core's 33 columns (same stride: they are the first 33 columns of this chip), then the adapter's
     ZK_TRY(zkhip_rv32_loadstore_tracegen(ctx, d_case, d_read, d_prev, n, log_height, d_trace, d_bitwise_trace));
     const size_t N = (size_t)1 << log_height;
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "vm_loadstore_adapter_tracegen");
-    hipLaunchKernelGGL(k_vm_ls_adapter, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_ts, d_base, d_imm, d_prev_ts, n, N, d_trace, (uint32_t*)flag);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return check_flag(ctx, flag, "vm_loadstore_tracegen (a timestamp gap out of range)");
+    return tracegen_frame(
+        ctx, "vm_loadstore_adapter_tracegen", {},
+        [&](uint32_t* bad) { hipLaunchKernelGGL(k_vm_ls_adapter, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_ts, d_base, d_imm, d_prev_ts, n, N, d_trace, bad); },
+        "vm_loadstore_tracegen (a timestamp gap out of range)");
 }
 
 int zkhip_vm_poseidon2_tracegen(zkhip_ctx* ctx, const uint32_t* d_inputs, size_t n, unsigned log_height, uint32_t* d_trace) {
@@ -406,6 +402,7 @@ int zkhip_vm_poseidon2_tracegen(zkhip_ctx* ctx, const uint32_t* d_inputs, size_t
     if (!ctx || !d_trace || log_height > 27) return ZKHIP_ERR_INVALID;
     ZK_TRY(poseidon2_air_tracegen(ctx, d_inputs, n, log_height, d_trace));
     const size_t N = (size_t)1 << log_height;
+    // (outside tracegen_frame: the fill refuses nothing, and a counter would cost a memset launch)
     KernelScope ks(ctx, "vm_poseidon2_multiplicities");
     hipLaunchKernelGGL(k_fill_prefix, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_trace + (size_t)ZKHIP_POSEIDON2_AIR_WIDTH * N, n, N);
     ZK_HIP_CHECK(ctx, hipGetLastError());
@@ -417,16 +414,16 @@ static int native_rows(zkhip_ctx* ctx, const uint32_t* d_records, size_t n, unsi
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_trace || log_height > 27 || (n && !d_records)) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
-    if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, std::string(name) + ": more records than rows");
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, name);
-    const dim3 grid((unsigned)((N + 255) / 256)), block(256);
-    if (which == 0) hipLaunchKernelGGL(k_vm_native_arith, grid, block, 0, ctx->stream, d_records, n, N, d_trace, (uint32_t*)flag);
-    else if (which == 1) hipLaunchKernelGGL(k_vm_native_ext, grid, block, 0, ctx->stream, d_records, n, N, d_trace, (uint32_t*)flag);
-    else hipLaunchKernelGGL(k_vm_castf, grid, block, 0, ctx->stream, d_records, n, N, d_trace, (uint32_t*)flag);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return check_flag(ctx, flag, (std::string(name) + " (an unknown operation, a division by zero, a castf operand of 2^30 or more, or a timestamp gap out of range)").c_str());
+    ZK_TRY(tracegen_shape(ctx, name, n, N, 0, 0, 0));
+    return tracegen_frame(
+        ctx, name, {},
+        [&](uint32_t* bad) {
+            const dim3 grid((unsigned)((N + 255) / 256)), block(256);
+            if (which == 0) hipLaunchKernelGGL(k_vm_native_arith, grid, block, 0, ctx->stream, d_records, n, N, d_trace, bad);
+            else if (which == 1) hipLaunchKernelGGL(k_vm_native_ext, grid, block, 0, ctx->stream, d_records, n, N, d_trace, bad);
+            else hipLaunchKernelGGL(k_vm_castf, grid, block, 0, ctx->stream, d_records, n, N, d_trace, bad);
+        },
+        std::string(name) + " (an unknown operation, a division by zero, a castf operand of 2^30 or more, or a timestamp gap out of range)");
 }
 int zkhip_vm_native_arith_tracegen(zkhip_ctx* ctx, const uint32_t* d_records, size_t n, unsigned log_height, uint32_t* d_trace) {
     return native_rows(ctx, d_records, n, log_height, d_trace, 0, "vm_native_arith_tracegen");
@@ -443,6 +440,7 @@ int zkhip_rows_tracegen(zkhip_ctx* ctx, const uint32_t* d_rows, size_t n, size_t
     if (!ctx || !d_trace || width == 0 || width > 4096 || log_height > 27 || (n && !d_rows)) return ZKHIP_ERR_INVALID;
     const size_t N = (size_t)1 << log_height;
     if (n > N) return set_error(ctx, ZKHIP_ERR_INVALID, "rows_tracegen: more rows than the trace height");
+    // (outside tracegen_frame: the counter shares a scratch block with the padding row, and the call synchronises for the caller's temporary)
     void *flag = nullptr, *scratch = nullptr;
     ZK_TRY(get_scratch(ctx, 2, 16 + 4 * 4096, &scratch));   // [error flag | the padding row]
     uint32_t* d_pad = nullptr;
@@ -461,7 +459,7 @@ int zkhip_rows_tracegen(zkhip_ctx* ctx, const uint32_t* d_rows, size_t n, size_t
     hipLaunchKernelGGL(k_rows_to_trace, dim3((unsigned)((N * width + 255) / 256)), dim3(256), 0, ctx->stream, d_rows, n, (uint32_t)width, N, d_pad, d_trace,
                        (uint32_t*)flag);
     ZK_HIP_CHECK(ctx, hipGetLastError());
-    return check_flag(ctx, flag, "rows_tracegen (a word is not a canonical field element)");
+    return tracegen_finish(ctx, flag, "rows_tracegen (a word is not a canonical field element)");
 }
 
 int zkhip_range_counts_scaled_tracegen(zkhip_ctx* ctx, const uint32_t* d_values, size_t n, uint32_t scale, unsigned log_table, uint32_t* d_counts,
@@ -469,18 +467,14 @@ int zkhip_range_counts_scaled_tracegen(zkhip_ctx* ctx, const uint32_t* d_values,
     ZK_BIND_DEVICE(ctx);
     if (!ctx || !d_counts || log_table > 27 || scale == 0 || (n && !d_values)) return ZKHIP_ERR_INVALID;
     const size_t T = (size_t)1 << log_table;
-    void* flag = nullptr;
-    ZK_TRY(tracegen_flag(ctx, &flag));
-    KernelScope ks(ctx, "range_counts_scaled_tracegen");
-    if (!accumulate) ZK_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, T * 4, ctx->stream));
-    else tables_repr(ctx, {{d_counts, T}}, false);
-    if (n) {
-        const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
-        hipLaunchKernelGGL(k_range_counts_scaled, dim3(blocks), dim3(256), 0, ctx->stream, d_values, n, scale, (uint32_t)T, d_counts, (uint32_t*)flag);
-    }
-    tables_repr(ctx, {{d_counts, T}}, true);
-    ZK_HIP_CHECK(ctx, hipGetLastError());
-    return check_flag(ctx, flag, "range_counts_scaled_tracegen (scaled value outside the table)");
+    return tracegen_count_frame(
+        ctx, "range_counts_scaled_tracegen", {d_counts, T}, accumulate,
+        [&](uint32_t* bad) {
+            if (!n) return;
+            const unsigned blocks = (unsigned)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), HOT_MAX_BLOCKS);
+            hipLaunchKernelGGL(k_range_counts_scaled, dim3(blocks), dim3(256), 0, ctx->stream, d_values, n, scale, (uint32_t)T, d_counts, bad);
+        },
+        "range_counts_scaled_tracegen (scaled value outside the table)");
 }
 
 }  // extern "C"
