@@ -126,18 +126,27 @@ def prove(ch, params, airs, traces, pvs, l, with_bus=True, weighted=True, leaf_h
     claim = ZERO
     for j, a in enumerate(act):
         claim = ext_add(claim, ext_mul(wgt[a], c.get(a, ZERO)))
-    info.update(tau=tau, alpha=alpha, mu=mu, claim0=claim, rounds=[], c=c)
+    info.update(tau=tau, alpha=alpha, mu=mu, claim0=claim, rounds=[], c=c, sa={})
     r = []
+    ca = {a: c.get(a, ZERO) for a in act}   # every AIR's running claim
     for i in range(M):
         s = [ZERO] * (D + 1)
         for j, a in enumerate(act):
             pl = plans[a]
             if pl.m > i:
-                for t in range(D + 1):
-                    sa = ZERO
+                sa = []
+                for t in range(pl.D + 1):
+                    x = ZERO
                     for y in range(len(tabs[a][0]) // 2):
-                        sa = ext_add(sa, summand(pl, [zm._at(tb[2 * y], tb[2 * y + 1], t) for tb in tabs[a]], pvs[a], apow[a], coef[a]))
-                    s[t] = ext_add(s[t], ext_mul(wgt[a], sa))
+                        x = ext_add(x, summand(pl, [zm._at(tb[2 * y], tb[2 * y + 1], t) for tb in tabs[a]], pvs[a], apow[a], coef[a]))
+                    sa.append(x)
+                # the round polynomial the AIR would have sent alone is s_a(0), s_a(2), .., s_a(D_a): s_a(1) is what its running claim
+                # leaves and the points above D_a follow from those D_a + 1.  On a true statement these are the sums themselves
+                sa[1] = wm.ext_sub(ca[a], sa[0])
+                sa += [zm.interp(sa[:pl.D + 1], gm.ext_c(t)) for t in range(pl.D + 1, D + 1)]
+                info["sa"][(i, a)] = sa   # s_a(0..D) of round i, before its weight
+                for t in range(D + 1):
+                    s[t] = ext_add(s[t], ext_mul(wgt[a], sa[t]))
             else:   # used up: the constant mu^j 2^(M - 1 - i) g_a(r_a)
                 k = ext_mul(ext_mul(mup[j], pow2(M - 1 - i) if weighted else ONE), g_end[a])
                 s = [ext_add(x, k) for x in s]
@@ -148,8 +157,9 @@ def prove(ch, params, airs, traces, pvs, l, with_bus=True, weighted=True, leaf_h
         for a in act:
             if plans[a].m > i:
                 tabs[a] = zm._fold_all(tabs[a], ri)
-                if plans[a].m == i + 1:
-                    g_end[a] = summand(plans[a], [tb[0] for tb in tabs[a]], pvs[a], apow[a], coef[a])
+                ca[a] = zm.interp(info["sa"][(i, a)], ri)
+                if plans[a].m == i + 1:   # g_a(r_a), as the last claim gives it (the summand on the folded tables, if the statement is true)
+                    g_end[a] = ca[a]
     # 7. the values
     vals = {a: [tabs[a][k][0] for k in range(plans[a].w + len(plans[a].rot))] for a in act}
     wm._observe(ch, [x for a in act for e in vals[a] for x in e], words)

@@ -110,9 +110,9 @@ def proof_words(params, airs, l, l_prep, l_cached, with_bus=True):
             + sum(S.cached_words(params, a) for a in S.cached_airs))
 
 
-def prove(ch, params, airs, traces, preps, pvs, l, key, cached, with_bus=True):
+def prove(ch, params, airs, traces, preps, pvs, l, key, cached, with_bus=True, leaf_hook=None):
     """The proof, continuing `ch` (after the caller's prefix): (root, words, info).  The prover reads the cached columns from `traces`
-    (the whole traces, cached columns first) and opens the handles' own copies.  info: as keyed_batch_model.prove's, plus the offsets
+    (the whole traces, cached columns first) and opens the handles' own copies.  leaf_hook: as airset_model.prove's.  info: as keyed_batch_model.prove's, plus the offsets
     of the three kinds of opening (open_at, open2_at, open3_at: AIR -> offset) and the opened cached values."""
     S = Shape(params, airs, l, key.l_prep, [c.l if c else 0 for c in cached], with_bus)
     plans, n_airs = S.plans, len(airs)
@@ -132,6 +132,8 @@ def prove(ch, params, airs, traces, preps, pvs, l, key, cached, with_bus=True):
     if with_bus:   # steps 2 - 5 of the keyed AIR-set proof
         gamma, beta = gm.bus_challenges(ch)
         num, den = km.leaves(S, traces, preps, pvs, gamma, beta)
+        if leaf_hook:
+            leaf_hook(num, den)
         gw, rho, _ = gm.prove(ch, num, den)
         words += gw
         eb = am.block_eq(S.blocks, rho)
@@ -157,18 +159,27 @@ def prove(ch, params, airs, traces, preps, pvs, l, key, cached, with_bus=True):
     claim = ZERO
     for a in act:
         claim = ext_add(claim, ext_mul(wgt[a], c.get(a, ZERO)))
-    info.update(tau=tau, alpha=alpha, mu=mu, claim0=claim, rounds=[], c=c)
+    info.update(tau=tau, alpha=alpha, mu=mu, claim0=claim, rounds=[], c=c, sa={})
     r = []
+    ca = {a: c.get(a, ZERO) for a in act}   # every AIR's running claim
     for i in range(M):
         s = [ZERO] * (D + 1)
         for j, a in enumerate(act):
             pl = plans[a]
             if pl.m > i:
-                for t in range(D + 1):
-                    sa = ZERO
+                sa = []
+                for t in range(pl.D + 1):
+                    x = ZERO
                     for y in range(len(tabs[a][0]) // 2):
-                        sa = ext_add(sa, summand(pl, [zm._at(tb[2 * y], tb[2 * y + 1], t) for tb in tabs[a]], pvs[a], apow[a], coef[a]))
-                    s[t] = ext_add(s[t], ext_mul(wgt[a], sa))
+                        x = ext_add(x, summand(pl, [zm._at(tb[2 * y], tb[2 * y + 1], t) for tb in tabs[a]], pvs[a], apow[a], coef[a]))
+                    sa.append(x)
+                # the round polynomial the AIR would have sent alone is s_a(0), s_a(2), .., s_a(D_a): s_a(1) is what its running claim
+                # leaves and the points above D_a follow from those D_a + 1.  On a true statement these are the sums themselves
+                sa[1] = wm.ext_sub(ca[a], sa[0])
+                sa += [zm.interp(sa[:pl.D + 1], gm.ext_c(t)) for t in range(pl.D + 1, D + 1)]
+                info["sa"][(i, a)] = sa   # s_a(0..D) of round i, before its weight
+                for t in range(D + 1):
+                    s[t] = ext_add(s[t], ext_mul(wgt[a], sa[t]))
             else:   # used up: the constant mu^j 2^(M - 1 - i) g_a(r_a)
                 k = ext_mul(ext_mul(mup[j], pow2(M - 1 - i)), g_end[a])
                 s = [ext_add(x, k) for x in s]
@@ -179,8 +190,9 @@ def prove(ch, params, airs, traces, preps, pvs, l, key, cached, with_bus=True):
         for a in act:
             if plans[a].m > i:
                 tabs[a] = zm._fold_all(tabs[a], ri)
-                if plans[a].m == i + 1:
-                    g_end[a] = summand(plans[a], [tb[0] for tb in tabs[a]], pvs[a], apow[a], coef[a])
+                ca[a] = zm.interp(info["sa"][(i, a)], ri)
+                if plans[a].m == i + 1:   # g_a(r_a), as the last claim gives it (the summand on the folded tables, if the statement is true)
+                    g_end[a] = ca[a]
     # 7. the values [v | v' | v_p | v_p'] of every active AIR
     vals = {a: [tabs[a][k][0] for k in range(plans[a].n_val)] for a in act}
     wm._observe(ch, [x for a in act for e in vals[a] for x in e], words)

@@ -113,14 +113,25 @@ def test_boundary_count_columns(zk, kind):
         pytest.fail("proof differs from the model at word %d of %d" % (int(np.nonzero(proof != np.array(words))[0][0]), len(words)))
 
 
-def _replay(prm, prefix, airs, pvs, l, proof, with_bus):
-    """(plans, r, r', offsets) by replaying the transcript up to the points with the model's challenger"""
+def _replay(prm, prefix, airs, pvs, l, proof, with_bus, keyed=None):
+    """(plans, r, r', offsets) by replaying the transcript up to the points with the model's challenger.  keyed = (the key's root,
+    log_stack_prep): the keyed batched form, whose transcript takes the key's root first and whose values are [v | v' | v_p | v_p']"""
     import gkr_model as gm
 
-    plans, _, _, blocks, L = bm.shape(prm, airs, l, with_bus)
-    act, M, D, red, M2 = bm.dims(plans)
     ch = Challenger()
     ch.observe(prefix)
+    if keyed:
+        import keyed_batch_model as kb
+
+        S = kb.Shape(prm, airs, l, keyed[1], with_bus)
+        plans, L = S.plans, S.L
+        act, M, D, red, M2 = kb.dims(plans)
+        n_val = lambda a: plans[a].n_val
+        ch.observe([int(x) for x in keyed[0]])
+    else:
+        plans, _, _, blocks, L = bm.shape(prm, airs, l, with_bus)
+        act, M, D, red, M2 = bm.dims(plans)
+        n_val = lambda a: plans[a].w + len(plans[a].rot)
     ch.observe(proof[:8].tolist())
     for pv in pvs:
         ch.observe([int(x) for x in pv])
@@ -142,7 +153,7 @@ def _replay(prm, prefix, airs, pvs, l, proof, with_bus):
         r.append(ch.sample_ext())
         q += 4 * D
     o_vals = q
-    nv = sum(4 * (plans[a].w + len(plans[a].rot)) for a in act)
+    nv = sum(4 * n_val(a) for a in act)
     ch.observe(proof[q:q + nv].tolist())
     q += nv
     if red:
