@@ -79,6 +79,13 @@ struct Gate {
     uint8_t hmask = 0;  // K_HSTEP: bit j = coordinate j of slot b is taken
     Src src[4];  // K_INPUT: where each defined slot's value comes from
 };
+inline Src make_src(uint8_t kind, uint32_t child = 0, uint32_t a = 0, uint32_t b = 0) {
+    Src s;
+    s.kind = kind, s.child = child, s.a = a, s.b = b;
+    return s;
+}
+// the defining row of a constant wire (Builder::use): evaluated once, before the sections of a witness run side by side
+inline bool is_const_row(const Gate& G) { return G.kind == K_LIN && !G.role[0] && !G.role[1] && !G.role[3]; }
 struct Perm {
     uint32_t in[4], out[4];
 };
@@ -596,22 +603,23 @@ static V bit_product(Builder& b, const std::vector<V>& bits, const std::vector<u
     return acc;
 }
 
-// The symbolic twin of zkhip_verify (verifier.hip:218-576) for child `ci`.
+// The symbolic twin of zkhip_verify (verifier.hip:218-576) for child `ci`, as the steps verify_child_sym calls in order.
 // `prep_sym` (uniform node): the child's preprocessed commitments are VALUES of the circuit (8 base words per AIR, indexed by AIR)
 // instead of constants of the child verifying key -- one circuit then verifies proofs of any key with this AIR set and these heights.
-static ChildValues verify_child_sym(Builder& b, const ChildVk& vk, uint32_t ci, const std::vector<std::array<V, 8>>* prep_sym = nullptr) {
-    const zkhip_params& prm = vk.prm;
-    const unsigned bl = prm.log_blowup, lfp = prm.log_final_poly_len;
-    const size_t n_airs = vk.pg.size(), n_fin = (size_t)1 << lfp;
-    const std::vector<AirProgram>& pg = vk.pg;
-    unsigned hmax = 0;
-    size_t n_lu = 0, n_prep = 0, n_cached = 0;
-    for (size_t a = 0; a < n_airs; a++) {
-        hmax = std::max(hmax, vk.log_heights[a] + bl);
-        if (!pg[a].ints.empty()) n_lu++;
-        if (pg[a].prep_width) n_prep++;
-        if (pg[a].cached_width) n_cached++;
-    }
+// The builder is stateful: the circuit IS the order of the b.* calls (wire ids, constant rows, input-row packing), so the steps run in
+// this order only, and the maps filled on first use (zn_of, chal, x_of, invd) stay filled on first use.
+struct ChildVerifier {
+    Builder& b;
+    const ChildVk& vk;
+    const zkhip_params& prm;
+    const std::vector<AirProgram>& pg;
+    const uint32_t ci;
+    const std::vector<std::array<V, 8>>* const prep_sym;
+    const unsigned bl, lfp;
+    const size_t n_airs, n_fin;
+    const uint32_t gen = to_monty(FIELD_GEN_CANON), half = minv(to_monty(2));
+
+    // the matrix table: main parts, cached partitions, preprocessed, permutation, quotient chunks (verifier.hip's order)
     struct CMat {
         unsigned lh, h;
         size_t width;
@@ -619,211 +627,249 @@ static ChildValues verify_child_sym(Builder& b, const ChildVk& vk, uint32_t ci, 
         size_t open_off;
     };
     std::vector<CMat> cm;
-    for (size_t a = 0; a < n_airs; a++) cm.push_back({vk.log_heights[a], vk.log_heights[a] + bl, vk.widths[a] - pg[a].cached_width, 2, 0});
-    for (size_t a = 0; a < n_airs; a++)
-        if (pg[a].cached_width) cm.push_back({vk.log_heights[a], vk.log_heights[a] + bl, pg[a].cached_width, 2, 0});
-    for (size_t a = 0; a < n_airs; a++)
-        if (pg[a].prep_width) cm.push_back({vk.log_heights[a], vk.log_heights[a] + bl, pg[a].prep_width, 2, 0});
-    for (size_t a = 0; a < n_airs; a++)
-        if (!pg[a].ints.empty()) cm.push_back({vk.log_heights[a], vk.log_heights[a] + bl, pg[a].perm_width(), 2, 0});
-    for (size_t a = 0; a < n_airs; a++)
-        for (unsigned j = 0; j < pg[a].qd(); j++) cm.push_back({vk.log_heights[a], vk.log_heights[a] + bl, 4, 1, 0});
-    const size_t cm_cached0 = n_airs, cm_prep0 = n_airs + n_cached, cm_perm0 = cm_prep0 + n_prep, cm_quot0 = cm_perm0 + n_lu;
-    std::vector<size_t> qoff(n_airs + 1, 0);
-    for (size_t a = 0; a < n_airs; a++) qoff[a + 1] = qoff[a] + pg[a].qd();
-    size_t n_open = 0;
-    for (auto& m : cm) {
-        m.open_off = n_open;
-        n_open += m.width * m.n_pts;
+    unsigned hmax = 0, n_layers = 0;
+    size_t n_lu = 0, n_prep = 0, n_cached = 0, n_open = 0;
+    size_t cm_cached0 = 0, cm_prep0 = 0, cm_perm0 = 0, cm_quot0 = 0;
+    std::vector<size_t> qoff;
+    size_t r = 4;   // the word cursor over the proof
+
+    // the proof's fixed part
+    std::array<V, 2> root_main, root_perm{}, root_quot;
+    std::vector<std::array<V, 2>> roots_cached, fri_roots;
+    std::vector<std::array<V, 4>> exposed_coords;   // per AIR with interactions: the 4 base coordinates
+    std::vector<V> exposed, opened, fri_pow, fin;
+    V qpow;
+    ChildValues out;   // the child's public values
+
+    // the transcript and what it hands out
+    SymChallenger ch;
+    std::vector<V> chal;   // base coordinates, materialised on demand
+    std::vector<char> chal_have;
+    std::vector<V> chal_ext;   // gamma, beta^1 ..
+    V alpha, zeta, alpha_f;
+    std::vector<V> betas, betas_sq;
+
+    struct Batch {
+        size_t first, n;
+        std::array<V, 2> root;
+        std::vector<unsigned> lhs;
+        std::vector<size_t> ws;
+        size_t tw = 0;
+        unsigned bh = 0;
+    };
+    std::vector<Batch> batches;
+    struct RoTerm {
+        V ry[2], off_pow[2];
+    };
+    std::vector<RoTerm> ro_terms;
+    std::vector<char> has;
+    std::map<std::pair<unsigned, unsigned>, V> z_of;   // z per (height, point): a per-proof value
+    std::vector<std::vector<V>> idx_of;
+
+    ChildVerifier(Builder& bb, const ChildVk& k, uint32_t child, const std::vector<std::array<V, 8>>* prep)
+        : b(bb), vk(k), prm(k.prm), pg(k.pg), ci(child), prep_sym(prep), bl(k.prm.log_blowup), lfp(k.prm.log_final_poly_len),
+          n_airs(k.pg.size()), n_fin((size_t)1 << k.prm.log_final_poly_len), ch(bb) {}
+
+    std::array<V, 2> in_digest(size_t off) {
+        std::array<V, 2> d;
+        d[0] = b.in_ext(make_src(S_PROOF_EXT, ci, (uint32_t)off));
+        d[1] = b.in_ext(make_src(S_PROOF_EXT, ci, (uint32_t)off + 4));
+        return d;
     }
-    const unsigned n_layers = hmax - bl - lfp;
+    V in_ext_at(size_t off) { return b.in_ext(make_src(S_PROOF_EXT, ci, (uint32_t)off)); }
+    V in_base_at(size_t off) { return b.in_base(make_src(S_PROOF_BASE, ci, (uint32_t)off)); }
+
+    void layout_matrices() {
+        for (size_t a = 0; a < n_airs; a++) {
+            hmax = std::max(hmax, vk.log_heights[a] + bl);
+            if (!pg[a].ints.empty()) n_lu++;
+            if (pg[a].prep_width) n_prep++;
+            if (pg[a].cached_width) n_cached++;
+        }
+        for (size_t a = 0; a < n_airs; a++) cm.push_back({vk.log_heights[a], vk.log_heights[a] + bl, vk.widths[a] - pg[a].cached_width, 2, 0});
+        for (size_t a = 0; a < n_airs; a++)
+            if (pg[a].cached_width) cm.push_back({vk.log_heights[a], vk.log_heights[a] + bl, pg[a].cached_width, 2, 0});
+        for (size_t a = 0; a < n_airs; a++)
+            if (pg[a].prep_width) cm.push_back({vk.log_heights[a], vk.log_heights[a] + bl, pg[a].prep_width, 2, 0});
+        for (size_t a = 0; a < n_airs; a++)
+            if (!pg[a].ints.empty()) cm.push_back({vk.log_heights[a], vk.log_heights[a] + bl, pg[a].perm_width(), 2, 0});
+        for (size_t a = 0; a < n_airs; a++)
+            for (unsigned j = 0; j < pg[a].qd(); j++) cm.push_back({vk.log_heights[a], vk.log_heights[a] + bl, 4, 1, 0});
+        cm_cached0 = n_airs, cm_prep0 = n_airs + n_cached, cm_perm0 = cm_prep0 + n_prep, cm_quot0 = cm_perm0 + n_lu;
+        qoff.assign(n_airs + 1, 0);
+        for (size_t a = 0; a < n_airs; a++) qoff[a + 1] = qoff[a] + pg[a].qd();
+        for (auto& m : cm) {
+            m.open_off = n_open;
+            n_open += m.width * m.n_pts;
+        }
+        n_layers = hmax - bl - lfp;
+    }
 
     // ---- the proof's fixed part as inputs (word offsets as in verifier.hip) ----
-    b.phase = "proof inputs";
-    size_t r = 4;
-    auto in_digest = [&](size_t off) -> std::array<V, 2> {
-        Src s;
-        s.kind = S_PROOF_EXT, s.child = ci;
-        std::array<V, 2> d;
-        s.a = (uint32_t)off, d[0] = b.in_ext(s);
-        s.a = (uint32_t)off + 4, d[1] = b.in_ext(s);
-        return d;
-    };
-    auto in_ext_at = [&](size_t off) {
-        Src s;
-        s.kind = S_PROOF_EXT, s.child = ci, s.a = (uint32_t)off;
-        return b.in_ext(s);
-    };
-    auto in_base_at = [&](size_t off) {
-        Src s;
-        s.kind = S_PROOF_BASE, s.child = ci, s.a = (uint32_t)off;
-        return b.in_base(s);
-    };
-    const std::array<V, 2> root_main = in_digest(r);
-    r += 8;
-    std::vector<std::array<V, 2>> roots_cached;
-    for (size_t k = 0; k < n_cached; k++) roots_cached.push_back(in_digest(r)), r += 8;
-    std::array<V, 2> root_perm{};
-    std::vector<std::array<V, 4>> exposed_coords;  // per AIR with interactions: the 4 base coordinates
-    std::vector<V> exposed;
-    if (n_lu) {
-        root_perm = in_digest(r);
+    void read_fixed_part() {
+        b.phase = "proof inputs";
+        root_main = in_digest(r);
         r += 8;
-        for (size_t k = 0; k < n_lu; k++) {
-            std::array<V, 4> co;
-            for (int q = 0; q < 4; q++) co[q] = in_base_at(r + q);
-            exposed_coords.push_back(co);
-            exposed.push_back(b.pack(co));
-            r += 4;
+        for (size_t k = 0; k < n_cached; k++) roots_cached.push_back(in_digest(r)), r += 8;
+        if (n_lu) {
+            root_perm = in_digest(r);
+            r += 8;
+            for (size_t k = 0; k < n_lu; k++) {
+                std::array<V, 4> co;
+                for (int q = 0; q < 4; q++) co[q] = in_base_at(r + q);
+                exposed_coords.push_back(co);
+                exposed.push_back(b.pack(co));
+                r += 4;
+            }
         }
-    }
-    const std::array<V, 2> root_quot = in_digest(r);
-    r += 8;
-    std::vector<V> opened(n_open);
-    for (size_t i = 0; i < n_open; i++) opened[i] = in_ext_at(r + 4 * i);
-    r += 4 * n_open;
-    std::vector<std::array<V, 2>> fri_roots(n_layers);
-    std::vector<V> fri_pow(n_layers);
-    for (unsigned l = 0; l < n_layers; l++) {
-        fri_roots[l] = in_digest(r + 9 * (size_t)l);
-        fri_pow[l] = in_base_at(r + 9 * (size_t)l + 8);
-    }
-    r += 9 * (size_t)n_layers;
-    std::vector<V> fin(n_fin);
-    for (size_t j = 0; j < n_fin; j++) fin[j] = in_ext_at(r + 4 * j);
-    r += 4 * n_fin;
-    const V qpow = in_base_at(r++);
-    ChildValues out;
-    out.pvs.resize(n_airs);
-    for (size_t a = 0; a < n_airs; a++)
-        for (size_t i = 0; i < vk.n_pvs[a]; i++) {
-            Src s;
-            s.kind = S_PV, s.child = ci, s.a = (uint32_t)a, s.b = (uint32_t)i;
-            out.pvs[a].push_back(b.in_base(s));
+        root_quot = in_digest(r);
+        r += 8;
+        opened.resize(n_open);
+        for (size_t i = 0; i < n_open; i++) opened[i] = in_ext_at(r + 4 * i);
+        r += 4 * n_open;
+        fri_roots.resize(n_layers), fri_pow.resize(n_layers);
+        for (unsigned l = 0; l < n_layers; l++) {
+            fri_roots[l] = in_digest(r + 9 * (size_t)l);
+            fri_pow[l] = in_base_at(r + 9 * (size_t)l + 8);
         }
+        r += 9 * (size_t)n_layers;
+        fin.resize(n_fin);
+        for (size_t j = 0; j < n_fin; j++) fin[j] = in_ext_at(r + 4 * j);
+        r += 4 * n_fin;
+        qpow = in_base_at(r++);
+        out.pvs.resize(n_airs);
+        for (size_t a = 0; a < n_airs; a++)
+            for (size_t i = 0; i < vk.n_pvs[a]; i++) out.pvs[a].push_back(b.in_base(make_src(S_PV, ci, (uint32_t)a, (uint32_t)i)));
+    }
 
     // ---- transcript ----
-    b.phase = "transcript";
-    SymChallenger ch(b);
-    {
-        const uint32_t hdr[7] = {PROTO_TAG, (uint32_t)n_airs, prm.log_blowup, prm.log_final_poly_len, prm.num_queries, prm.commit_pow_bits, prm.query_pow_bits};
-        for (uint32_t w : hdr) ch.observe_const(w);
-        for (size_t a = 0; a < n_airs; a++) {
-            std::vector<uint32_t> pm(vk.programs[a].size());
-            for (size_t i = 0; i < pm.size(); i++) pm[i] = to_monty(vk.programs[a][i]);
-            uint32_t dg[8];
-            p2_hash_slice(pm.data(), pm.size(), dg);
-            ch.observe_const(vk.log_heights[a]), ch.observe_const((uint32_t)vk.widths[a]), ch.observe_const((uint32_t)vk.n_pvs[a]);
-            for (int i = 0; i < 8; i++) ch.observe(Lane{cst_base(dg[i]), -1});
-            if (pg[a].prep_width)
-                for (int i = 0; i < 8; i++) {
-                    if (prep_sym) ch.observe_base((*prep_sym)[a][i]);
-                    else ch.observe_const(vk.prep_commit[a][i]);
-                }
-            for (size_t i = 0; i < vk.n_pvs[a]; i++) ch.observe_base(out.pvs[a][i]);
+    void run_transcript() {
+        b.phase = "transcript";
+        {
+            const uint32_t hdr[7] = {PROTO_TAG, (uint32_t)n_airs, prm.log_blowup, prm.log_final_poly_len, prm.num_queries, prm.commit_pow_bits, prm.query_pow_bits};
+            for (uint32_t w : hdr) ch.observe_const(w);
+            for (size_t a = 0; a < n_airs; a++) {
+                std::vector<uint32_t> pm(vk.programs[a].size());
+                for (size_t i = 0; i < pm.size(); i++) pm[i] = to_monty(vk.programs[a][i]);
+                uint32_t dg[8];
+                p2_hash_slice(pm.data(), pm.size(), dg);
+                ch.observe_const(vk.log_heights[a]), ch.observe_const((uint32_t)vk.widths[a]), ch.observe_const((uint32_t)vk.n_pvs[a]);
+                for (int i = 0; i < 8; i++) ch.observe(Lane{cst_base(dg[i]), -1});
+                if (pg[a].prep_width)
+                    for (int i = 0; i < 8; i++) {
+                        if (prep_sym) ch.observe_base((*prep_sym)[a][i]);
+                        else ch.observe_const(vk.prep_commit[a][i]);
+                    }
+                for (size_t i = 0; i < vk.n_pvs[a]; i++) ch.observe_base(out.pvs[a][i]);
+            }
         }
-    }
-    for (size_t k = 0; k < n_cached; k++) ch.observe_ext(roots_cached[k][0]), ch.observe_ext(roots_cached[k][1]);
-    ch.observe_ext(root_main[0]), ch.observe_ext(root_main[1]);
-    std::vector<V> chal(N_CHAL);  // base coordinates, materialised on demand
-    std::vector<char> chal_have(N_CHAL, 0);
-    std::vector<V> chal_ext;  // gamma, beta^1 ..
-    if (n_lu) {
-        const V gamma = ch.sample_ext(), beta = ch.sample_ext();
-        unsigned max_f = 0;
-        for (size_t a = 0; a < n_airs; a++)
-            for (uint32_t i = 0; i < pg[a].n_nodes; i++)
-                if (pg[a].nodes[3 * i] == A_CHAL) max_f = std::max(max_f, pg[a].nodes[3 * i + 1] / 4);
-        chal_ext.push_back(gamma);
-        V cur = beta;
-        for (unsigned i = 1; i <= max_f; i++) {
-            chal_ext.push_back(cur);
-            if (i < max_f) cur = b.mul(cur, beta);
+        for (size_t k = 0; k < n_cached; k++) ch.observe_ext(roots_cached[k][0]), ch.observe_ext(roots_cached[k][1]);
+        ch.observe_ext(root_main[0]), ch.observe_ext(root_main[1]);
+        chal.resize(N_CHAL), chal_have.assign(N_CHAL, 0);
+        if (n_lu) {
+            const V gamma = ch.sample_ext(), beta = ch.sample_ext();
+            unsigned max_f = 0;
+            for (size_t a = 0; a < n_airs; a++)
+                for (uint32_t i = 0; i < pg[a].n_nodes; i++)
+                    if (pg[a].nodes[3 * i] == A_CHAL) max_f = std::max(max_f, pg[a].nodes[3 * i + 1] / 4);
+            chal_ext.push_back(gamma);
+            V cur = beta;
+            for (unsigned i = 1; i <= max_f; i++) {
+                chal_ext.push_back(cur);
+                if (i < max_f) cur = b.mul(cur, beta);
+            }
+            ch.observe_ext(root_perm[0]), ch.observe_ext(root_perm[1]);
+            for (size_t k = 0; k < n_lu; k++)
+                for (int q = 0; q < 4; q++) ch.observe_base(exposed_coords[k][q]);
+            V tot = exposed[0];
+            for (size_t k = 1; k < n_lu; k++) tot = b.add(tot, exposed[k]);
+            b.assert_zero(tot);
         }
-        ch.observe_ext(root_perm[0]), ch.observe_ext(root_perm[1]);
-        for (size_t k = 0; k < n_lu; k++)
-            for (int q = 0; q < 4; q++) ch.observe_base(exposed_coords[k][q]);
-        V tot = exposed[0];
-        for (size_t k = 1; k < n_lu; k++) tot = b.add(tot, exposed[k]);
-        b.assert_zero(tot);
+        alpha = ch.sample_ext();
+        ch.observe_ext(root_quot[0]), ch.observe_ext(root_quot[1]);
+        zeta = ch.sample_ext();
+        for (size_t i = 0; i < n_open; i++) ch.observe_ext(opened[i]);
+        alpha_f = ch.sample_ext();
     }
-    auto chal_at = [&](uint32_t x) -> V {
+    // base coordinate x of the LogUp challenges, unpacked when a constraint first asks for it
+    V chal_at(uint32_t x) {
         if (!chal_have[x]) {
             if (x / 4 >= chal_ext.size()) throw BuildError{"challenge index out of range"};
             const std::array<V, 4> co = b.unpack(chal_ext[x / 4]);
             for (int q = 0; q < 4; q++) chal[4 * (x / 4) + q] = co[q], chal_have[4 * (x / 4) + q] = 1;
         }
         return chal[x];
-    };
-    const V alpha = ch.sample_ext();
-    ch.observe_ext(root_quot[0]), ch.observe_ext(root_quot[1]);
-    const V zeta = ch.sample_ext();
-    for (size_t i = 0; i < n_open; i++) ch.observe_ext(opened[i]);
-    const V alpha_f = ch.sample_ext();
-    const uint32_t gen = to_monty(FIELD_GEN_CANON);
+    }
 
     // ---- constraints at zeta ----
-    b.phase = "constraints at zeta";
-    size_t k_lu = 0, k_prep = 0, k_cached = 0;
-    std::map<unsigned, V> zn_of;  // zeta^(2^lh)
-    for (size_t a = 0; a < n_airs; a++) {
-        const unsigned lh = vk.log_heights[a], h = lh + bl;
-        const size_t W = vk.widths[a], CW = pg[a].cached_width;
-        if (!zn_of.count(lh)) {
-            V zn = zeta;
-            for (unsigned k = 0; k < lh; k++) zn = b.mul(zn, zn);
-            zn_of[lh] = zn;
-        }
-        const V zn = zn_of[lh];
-        const V zh = b.add_const(zn, ext_from_base(mneg(MONTY_ONE)));
-        const V d1 = b.add_const(zeta, ext_from_base(mneg(MONTY_ONE)));
-        const V is_first = b.div(zh, d1);
-        const V is_trans = b.add_const(zeta, ext_from_base(mneg(minv(two_adic_generator(lh)))));
-        const V is_last = b.div(zh, is_trans);
-        const V inv_zh = b.inv(zh);
-        std::vector<V> mrow(2 * W);
-        if (CW) {
-            const V* co = &opened[cm[cm_cached0 + k_cached++].open_off];
-            for (size_t k = 0; k < CW; k++) mrow[k] = co[k], mrow[W + k] = co[CW + k];
-        }
-        for (size_t k = 0; k < W - CW; k++) mrow[CW + k] = opened[cm[a].open_off + k], mrow[W + CW + k] = opened[cm[a].open_off + (W - CW) + k];
-        const V *plocal = nullptr, *pnext = nullptr, *qlocal = nullptr, *qnext = nullptr;
-        const std::array<V, 4>* expo = nullptr;
-        if (pg[a].prep_width) {
-            qlocal = &opened[cm[cm_prep0 + k_prep].open_off];
-            qnext = qlocal + pg[a].prep_width;
-            k_prep++;
-        }
-        if (!pg[a].ints.empty()) {
-            plocal = &opened[cm[cm_perm0 + k_lu].open_off];
-            pnext = plocal + pg[a].perm_width();
-            expo = &exposed_coords[k_lu];
-            k_lu++;
-        }
-        std::vector<V> vals(pg[a].n_nodes);
-        for (uint32_t i = 0; i < pg[a].n_nodes; i++) {
-            const uint32_t op = pg[a].nodes[3 * i], x = pg[a].nodes[3 * i + 1], y = pg[a].nodes[3 * i + 2];
-            switch (op) {
-                case A_VAR: vals[i] = y ? mrow[W + x] : mrow[x]; break;
-                case A_PUB: vals[i] = out.pvs[a][x]; break;
-                case A_CONST: vals[i] = cst_u(x); break;
-                case A_FIRST: vals[i] = is_first; break;
-                case A_LAST: vals[i] = is_last; break;
-                case A_TRANS: vals[i] = is_trans; break;
-                case A_ADD: vals[i] = b.add(vals[x], vals[y]); break;
-                case A_SUB: vals[i] = b.sub(vals[x], vals[y]); break;
-                case A_MUL: vals[i] = b.mul(vals[x], vals[y]); break;
-                case A_NEG: vals[i] = b.scale(vals[x], b.NEG1); break;
-                case A_PERM: vals[i] = y ? pnext[x] : plocal[x]; break;
-                case A_CHAL: vals[i] = chal_at(x); break;
-                case A_PREP: vals[i] = y ? qnext[x] : qlocal[x]; break;
-                default: vals[i] = (*expo)[x]; break;
+    void constraints_at_zeta() {
+        b.phase = "constraints at zeta";
+        size_t k_lu = 0, k_prep = 0, k_cached = 0;
+        std::map<unsigned, V> zn_of;  // zeta^(2^lh)
+        for (size_t a = 0; a < n_airs; a++) {
+            const unsigned lh = vk.log_heights[a];
+            const size_t W = vk.widths[a], CW = pg[a].cached_width;
+            if (!zn_of.count(lh)) {
+                V zn = zeta;
+                for (unsigned k = 0; k < lh; k++) zn = b.mul(zn, zn);
+                zn_of[lh] = zn;
             }
+            const V zn = zn_of[lh];
+            const V zh = b.add_const(zn, ext_from_base(mneg(MONTY_ONE)));
+            const V d1 = b.add_const(zeta, ext_from_base(mneg(MONTY_ONE)));
+            const V is_first = b.div(zh, d1);
+            const V is_trans = b.add_const(zeta, ext_from_base(mneg(minv(two_adic_generator(lh)))));
+            const V is_last = b.div(zh, is_trans);
+            const V inv_zh = b.inv(zh);
+            std::vector<V> mrow(2 * W);
+            if (CW) {
+                const V* co = &opened[cm[cm_cached0 + k_cached++].open_off];
+                for (size_t k = 0; k < CW; k++) mrow[k] = co[k], mrow[W + k] = co[CW + k];
+            }
+            for (size_t k = 0; k < W - CW; k++) mrow[CW + k] = opened[cm[a].open_off + k], mrow[W + CW + k] = opened[cm[a].open_off + (W - CW) + k];
+            const V *plocal = nullptr, *pnext = nullptr, *qlocal = nullptr, *qnext = nullptr;
+            const std::array<V, 4>* expo = nullptr;
+            if (pg[a].prep_width) {
+                qlocal = &opened[cm[cm_prep0 + k_prep].open_off];
+                qnext = qlocal + pg[a].prep_width;
+                k_prep++;
+            }
+            if (!pg[a].ints.empty()) {
+                plocal = &opened[cm[cm_perm0 + k_lu].open_off];
+                pnext = plocal + pg[a].perm_width();
+                expo = &exposed_coords[k_lu];
+                k_lu++;
+            }
+            std::vector<V> vals(pg[a].n_nodes);
+            for (uint32_t i = 0; i < pg[a].n_nodes; i++) {
+                const uint32_t op = pg[a].nodes[3 * i], x = pg[a].nodes[3 * i + 1], y = pg[a].nodes[3 * i + 2];
+                switch (op) {
+                    case A_VAR: vals[i] = y ? mrow[W + x] : mrow[x]; break;
+                    case A_PUB: vals[i] = out.pvs[a][x]; break;
+                    case A_CONST: vals[i] = cst_u(x); break;
+                    case A_FIRST: vals[i] = is_first; break;
+                    case A_LAST: vals[i] = is_last; break;
+                    case A_TRANS: vals[i] = is_trans; break;
+                    case A_ADD: vals[i] = b.add(vals[x], vals[y]); break;
+                    case A_SUB: vals[i] = b.sub(vals[x], vals[y]); break;
+                    case A_MUL: vals[i] = b.mul(vals[x], vals[y]); break;
+                    case A_NEG: vals[i] = b.scale(vals[x], b.NEG1); break;
+                    case A_PERM: vals[i] = y ? pnext[x] : plocal[x]; break;
+                    case A_CHAL: vals[i] = chal_at(x); break;
+                    case A_PREP: vals[i] = y ? qnext[x] : qlocal[x]; break;
+                    default: vals[i] = (*expo)[x]; break;
+                }
+            }
+            V acc = cst(ext_zero());
+            for (uint32_t k = 0; k < pg[a].n_cons; k++) acc = b.mul_add(acc, alpha, vals[pg[a].cons[k]]);
+            const V lhs = b.mul(acc, inv_zh);
+            b.assert_eq(lhs, quotient_at_zeta(a, zn));
         }
-        V acc = cst(ext_zero());
-        for (uint32_t k = 0; k < pg[a].n_cons; k++) acc = b.mul_add(acc, alpha, vals[pg[a].cons[k]]);
-        const V lhs = b.mul(acc, inv_zh);
-        const uint32_t wM = two_adic_generator(h);
+    }
+    // sum_j chunk_j(zeta) prod_{k != j} ((zeta / s_k)^N - 1) / ((s_j / s_k)^N - 1) over the quotient chunks of AIR a (zn = zeta^N)
+    V quotient_at_zeta(size_t a, const V& zn) {
+        const unsigned lh = vk.log_heights[a];
+        const uint32_t wM = two_adic_generator(lh + bl);
         V rhs = cst(ext_zero());
         const unsigned nch = pg[a].qd();
         for (unsigned j = 0; j < nch; j++) {
@@ -845,30 +891,24 @@ static ChildValues verify_child_sym(Builder& b, const ChildVk& vk, uint32_t ci, 
             v = b.mul_add(v, x, chunk[0]);
             rhs = b.mul_add(v, zps, rhs);
         }
-        b.assert_eq(lhs, rhs);
+        return rhs;
     }
 
     // ---- FRI transcript ----
-    b.phase = "transcript";
-    std::vector<V> betas(n_layers), betas_sq(n_layers);
-    for (unsigned l = 0; l < n_layers; l++) {
-        ch.observe_ext(fri_roots[l][0]), ch.observe_ext(fri_roots[l][1]);
-        ch.check_witness(prm.commit_pow_bits, fri_pow[l]);
-        betas[l] = ch.sample_ext();
+    void fri_transcript() {
+        b.phase = "transcript";
+        betas.resize(n_layers), betas_sq.resize(n_layers);
+        for (unsigned l = 0; l < n_layers; l++) {
+            ch.observe_ext(fri_roots[l][0]), ch.observe_ext(fri_roots[l][1]);
+            ch.check_witness(prm.commit_pow_bits, fri_pow[l]);
+            betas[l] = ch.sample_ext();
+        }
+        for (size_t j = 0; j < n_fin; j++) ch.observe_ext(fin[j]);
+        ch.check_witness(prm.query_pow_bits, qpow);
     }
-    for (size_t j = 0; j < n_fin; j++) ch.observe_ext(fin[j]);
-    ch.check_witness(prm.query_pow_bits, qpow);
 
-    struct Batch {
-        size_t first, n;
-        std::array<V, 2> root;
-        std::vector<unsigned> lhs;
-        std::vector<size_t> ws;
-        size_t tw = 0;
-        unsigned bh = 0;
-    };
-    std::vector<Batch> batches;
-    auto add_batch = [&](size_t first, size_t n, const std::array<V, 2>& root) {
+    // the commitments the queries open, each with the matrices under it
+    void add_batch(size_t first, size_t n, const std::array<V, 2>& root) {
         Batch bt;
         bt.first = first, bt.n = n, bt.root = root;
         for (size_t m = first; m < first + n; m++) {
@@ -877,115 +917,126 @@ static ChildValues verify_child_sym(Builder& b, const ChildVk& vk, uint32_t ci, 
             bt.bh = std::max(bt.bh, cm[m].h);
         }
         batches.push_back(bt);
-    };
-    add_batch(0, n_airs, root_main);
-    for (size_t k = 0; k < n_cached; k++) add_batch(cm_cached0 + k, 1, roots_cached[k]);
-    {
-        size_t k = 0;
-        for (size_t a = 0; a < n_airs; a++)
-            if (pg[a].prep_width) {
-                const auto& pc = vk.prep_commit[a];
-                std::array<V, 2> root{cst(Ext{{to_monty(pc[0]), to_monty(pc[1]), to_monty(pc[2]), to_monty(pc[3])}}),
-                                      cst(Ext{{to_monty(pc[4]), to_monty(pc[5]), to_monty(pc[6]), to_monty(pc[7])}})};
-                if (prep_sym) {
-                    const std::array<V, 8>& ps = (*prep_sym)[a];
-                    root = {b.pack({ps[0], ps[1], ps[2], ps[3]}), b.pack({ps[4], ps[5], ps[6], ps[7]})};
-                }
-                add_batch(cm_prep0 + k++, 1, root);
-            }
     }
-    if (n_lu) add_batch(cm_perm0, n_lu, root_perm);
-    add_batch(cm_quot0, qoff[n_airs], root_quot);
+    void build_batches() {
+        add_batch(0, n_airs, root_main);
+        for (size_t k = 0; k < n_cached; k++) add_batch(cm_cached0 + k, 1, roots_cached[k]);
+        {
+            size_t k = 0;
+            for (size_t a = 0; a < n_airs; a++)
+                if (pg[a].prep_width) {
+                    const auto& pc = vk.prep_commit[a];
+                    std::array<V, 2> root{cst(Ext{{to_monty(pc[0]), to_monty(pc[1]), to_monty(pc[2]), to_monty(pc[3])}}),
+                                          cst(Ext{{to_monty(pc[4]), to_monty(pc[5]), to_monty(pc[6]), to_monty(pc[7])}})};
+                    if (prep_sym) {
+                        const std::array<V, 8>& ps = (*prep_sym)[a];
+                        root = {b.pack({ps[0], ps[1], ps[2], ps[3]}), b.pack({ps[4], ps[5], ps[6], ps[7]})};
+                    }
+                    add_batch(cm_prep0 + k++, 1, root);
+                }
+        }
+        if (n_lu) add_batch(cm_perm0, n_lu, root_perm);
+        add_batch(cm_quot0, qoff[n_airs], root_quot);
+    }
 
-    b.phase = "reduced openings, per proof";
     // ---- per-proof parts of the reduced openings: alpha_f powers, sum_k alpha_f^k p_k(z) per (matrix, point), alpha_f^offset ----
-    size_t max_w = 1;
-    for (const auto& m : cm) max_w = std::max(max_w, m.width);
-    std::vector<V> apow(max_w + 1);
-    apow[0] = cst(ext_one());
-    for (size_t k = 1; k <= max_w; k++) apow[k] = k == 1 ? alpha_f : b.mul(apow[k - 1], alpha_f);
-    struct RoTerm {
-        V ry[2], off_pow[2];
-    };
-    std::vector<RoTerm> ro_terms(cm.size());
-    std::vector<char> has(hmax + 1, 0);
-    {
-        std::vector<V> run(hmax + 1, cst(ext_one()));
-        size_t oi = 0;
-        for (const auto& bt : batches)
-            for (size_t mi = 0; mi < bt.n; mi++) {
-                const size_t m = bt.first + mi;
-                const CMat& M = cm[m];
-                has[M.h] = 1;
-                for (unsigned pt = 0; pt < M.n_pts; pt++) {
-                    V ry = cst(ext_zero());
-                    for (size_t k = M.width; k-- > 0;) ry = b.mul_add(ry, alpha_f, opened[oi + k]);  // Horner: sum_k alpha_f^k p_k
-                    ro_terms[m].ry[pt] = ry;
-                    ro_terms[m].off_pow[pt] = run[M.h];
-                    run[M.h] = b.mul(run[M.h], apow[M.width]);
-                    oi += M.width;
-                }
-            }
-    }
-    for (unsigned l = 0; l < n_layers; l++)
-        if (has[hmax - l - 1]) betas_sq[l] = b.mul(betas[l], betas[l]);
-    // z - x denominators: z per (height, point) is a per-proof value
-    std::map<std::pair<unsigned, unsigned>, V> z_of;
-    for (const auto& M : cm)
-        for (unsigned pt = 0; pt < M.n_pts; pt++)
-            if (!z_of.count({M.h, pt})) z_of[{M.h, pt}] = pt == 0 ? zeta : b.scale(zeta, two_adic_generator(M.lh));
-
-    // ---- queries ----
-    b.phase = "query indices";
-    const uint32_t half = minv(to_monty(2));
-    // the query indices first (the challenger is a chain: nothing else touches it from here on), then the queries, each a part of the
-    // circuit of its own
-    std::vector<std::vector<V>> idx_of(prm.num_queries);
-    for (unsigned qn = 0; qn < prm.num_queries; qn++) idx_of[qn] = ch.sample_bits(hmax);  // least significant first
-    b.c.sub.emplace_back();
-    for (unsigned qn = 0; qn < prm.num_queries; qn++) {
-        b.close_input_rows();
-        b.c.sub.back().push_back(b.c.order.size());
-        const std::vector<V>& idx = idx_of[qn];
-        std::vector<std::vector<Lane>> rows_of(batches.size());
-        for (size_t bi = 0; bi < batches.size(); bi++) {
-            b.phase = "query: opened rows (inputs, sponge, paths)";
-            const Batch& bt = batches[bi];
-            // The opened row of the batch comes in PACKED, four cells to a value, in the order the level's sponge takes them (per level: its
-            // matrices one after the other): the sponge then absorbs the values as they are -- no row that packs four base wires --, and the
-            // reduced opening below walks the coordinates of the same values (Builder::hstep).
-            rows_of[bi].resize(bt.tw);
-            {
-                std::vector<size_t> moff(bt.n + 1, 0);
-                for (size_t mi = 0; mi < bt.n; mi++) moff[mi + 1] = moff[mi] + bt.ws[mi];
-                std::vector<unsigned> levels(bt.lhs);
-                std::sort(levels.begin(), levels.end(), std::greater<unsigned>());
-                levels.erase(std::unique(levels.begin(), levels.end()), levels.end());
-                for (unsigned lv : levels) {
-                    std::vector<size_t> seq;
-                    for (size_t mi = 0; mi < bt.n; mi++)
-                        if (bt.lhs[mi] == lv)
-                            for (size_t k = 0; k < bt.ws[mi]; k++) seq.push_back(moff[mi] + k);
-                    for (size_t j = 0; j < seq.size(); j += 4) {
-                        std::array<uint32_t, 4> offs;
-                        for (size_t q = 0; q < 4; q++) offs[q] = j + q < seq.size() ? (uint32_t)(r + seq[j + q]) : ~0u;
-                        const V w = b.in_packed(ci, offs);
-                        for (size_t q = 0; q < 4 && j + q < seq.size(); q++) rows_of[bi][seq[j + q]] = Lane{w, (int)q};
+    void reduced_opening_terms() {
+        b.phase = "reduced openings, per proof";
+        size_t max_w = 1;
+        for (const auto& m : cm) max_w = std::max(max_w, m.width);
+        std::vector<V> apow(max_w + 1);
+        apow[0] = cst(ext_one());
+        for (size_t k = 1; k <= max_w; k++) apow[k] = k == 1 ? alpha_f : b.mul(apow[k - 1], alpha_f);
+        ro_terms.resize(cm.size());
+        has.assign(hmax + 1, 0);
+        {
+            std::vector<V> run(hmax + 1, cst(ext_one()));
+            size_t oi = 0;
+            for (const auto& bt : batches)
+                for (size_t mi = 0; mi < bt.n; mi++) {
+                    const size_t m = bt.first + mi;
+                    const CMat& M = cm[m];
+                    has[M.h] = 1;
+                    for (unsigned pt = 0; pt < M.n_pts; pt++) {
+                        V ry = cst(ext_zero());
+                        for (size_t k = M.width; k-- > 0;) ry = b.mul_add(ry, alpha_f, opened[oi + k]);  // Horner: sum_k alpha_f^k p_k
+                        ro_terms[m].ry[pt] = ry;
+                        ro_terms[m].off_pow[pt] = run[M.h];
+                        run[M.h] = b.mul(run[M.h], apow[M.width]);
+                        oi += M.width;
                     }
                 }
-            }
-            r += bt.tw;
-            std::vector<std::array<V, 2>> path(bt.bh);
-            for (unsigned l = 0; l < bt.bh; l++) path[l] = in_digest(r + 8 * (size_t)l);
-            r += 8 * (size_t)bt.bh;
-            const std::vector<V> ibits(idx.begin() + (hmax - bt.bh), idx.end());
-            verify_opening_sym(b, bt.root, bt.lhs, bt.ws, ibits, rows_of[bi], path);
         }
-        // evaluation points of this query per LDE height, and 1 / (z - x)
+        for (unsigned l = 0; l < n_layers; l++)
+            if (has[hmax - l - 1]) betas_sq[l] = b.mul(betas[l], betas[l]);
+        // z - x denominators: z per (height, point) is a per-proof value
+        for (const auto& M : cm)
+            for (unsigned pt = 0; pt < M.n_pts; pt++)
+                if (!z_of.count({M.h, pt})) z_of[{M.h, pt}] = pt == 0 ? zeta : b.scale(zeta, two_adic_generator(M.lh));
+    }
+
+    // ---- queries ----
+    // the query indices first (the challenger is a chain: nothing else touches it from here on), then the queries, each a part of the
+    // circuit of its own
+    void sample_query_indices() {
+        b.phase = "query indices";
+        idx_of.resize(prm.num_queries);
+        for (unsigned qn = 0; qn < prm.num_queries; qn++) idx_of[qn] = ch.sample_bits(hmax);  // least significant first
+        b.c.sub.emplace_back();
+    }
+
+    struct Query {
+        const std::vector<V>& idx;
+        std::vector<std::vector<Lane>> rows_of;   // per batch: the opened row, cell by cell
+        std::vector<V> roq;                       // per LDE height: the reduced opening
+    };
+    void verify_query(unsigned qn) {
+        b.close_input_rows();
+        b.c.sub.back().push_back(b.c.order.size());
+        Query q{idx_of[qn], std::vector<std::vector<Lane>>(batches.size()), {}};
+        for (size_t bi = 0; bi < batches.size(); bi++) open_rows(q, bi);
+        reduced_openings_of_query(q);
+        fold_layers(q);
+    }
+    // The opened row of the batch comes in PACKED, four cells to a value, in the order the level's sponge takes them (per level: its
+    // matrices one after the other): the sponge then absorbs the values as they are -- no row that packs four base wires --, and the
+    // reduced opening walks the coordinates of the same values (Builder::hstep).
+    void open_rows(Query& q, size_t bi) {
+        b.phase = "query: opened rows (inputs, sponge, paths)";
+        const Batch& bt = batches[bi];
+        q.rows_of[bi].resize(bt.tw);
+        {
+            std::vector<size_t> moff(bt.n + 1, 0);
+            for (size_t mi = 0; mi < bt.n; mi++) moff[mi + 1] = moff[mi] + bt.ws[mi];
+            std::vector<unsigned> levels(bt.lhs);
+            std::sort(levels.begin(), levels.end(), std::greater<unsigned>());
+            levels.erase(std::unique(levels.begin(), levels.end()), levels.end());
+            for (unsigned lv : levels) {
+                std::vector<size_t> seq;
+                for (size_t mi = 0; mi < bt.n; mi++)
+                    if (bt.lhs[mi] == lv)
+                        for (size_t k = 0; k < bt.ws[mi]; k++) seq.push_back(moff[mi] + k);
+                for (size_t j = 0; j < seq.size(); j += 4) {
+                    std::array<uint32_t, 4> offs;
+                    for (size_t c4 = 0; c4 < 4; c4++) offs[c4] = j + c4 < seq.size() ? (uint32_t)(r + seq[j + c4]) : ~0u;
+                    const V w = b.in_packed(ci, offs);
+                    for (size_t c4 = 0; c4 < 4 && j + c4 < seq.size(); c4++) q.rows_of[bi][seq[j + c4]] = Lane{w, (int)c4};
+                }
+            }
+        }
+        r += bt.tw;
+        std::vector<std::array<V, 2>> path(bt.bh);
+        for (unsigned l = 0; l < bt.bh; l++) path[l] = in_digest(r + 8 * (size_t)l);
+        r += 8 * (size_t)bt.bh;
+        const std::vector<V> ibits(q.idx.begin() + (hmax - bt.bh), q.idx.end());
+        verify_opening_sym(b, bt.root, bt.lhs, bt.ws, ibits, q.rows_of[bi], path);
+    }
+    // evaluation points of this query per LDE height, and 1 / (z - x)
+    void reduced_openings_of_query(Query& q) {
         b.phase = "query: reduced openings";
         std::map<unsigned, V> x_of;
         std::map<std::pair<unsigned, unsigned>, V> invd;
-        std::vector<V> roq(hmax + 1, cst(ext_zero()));
+        q.roq.assign(hmax + 1, cst(ext_zero()));
         for (size_t bi = 0; bi < batches.size(); bi++) {
             size_t off = 0;
             for (size_t mi = 0; mi < batches[bi].n; mi++) {
@@ -994,7 +1045,7 @@ static ChildValues verify_child_sym(Builder& b, const ChildVk& vk, uint32_t ci, 
                 const unsigned h = M.h;
                 if (!x_of.count(h)) {
                     // x = gen * w_h^bitrev(ih, h), ih = idx >> (hmax - h): bit j of ih contributes w_h^(2^(h-1-j))
-                    std::vector<V> bits(idx.begin() + (hmax - h), idx.end());
+                    std::vector<V> bits(q.idx.begin() + (hmax - h), q.idx.end());
                     std::vector<uint32_t> roots(h);
                     for (unsigned j = 0; j < h; j++) roots[j] = mpow(two_adic_generator(h), (uint64_t)1 << (h - 1 - j));
                     x_of[h] = bit_product(b, bits, roots, cst_base(gen));
@@ -1002,28 +1053,31 @@ static ChildValues verify_child_sym(Builder& b, const ChildVk& vk, uint32_t ci, 
                 // sum_k alpha_f^k p_k(x), last cell first: the cells of this matrix that share a packed value take ONE row
                 V rrow = cst(ext_zero());
                 for (size_t k = M.width; k > 0;) {
-                    const Lane& top = rows_of[bi][off + k - 1];
+                    const Lane& top = q.rows_of[bi][off + k - 1];
                     unsigned mask = 0;
-                    while (k > 0 && rows_of[bi][off + k - 1].v.wire == top.v.wire) mask |= 1u << rows_of[bi][off + k - 1].coord, k--;
+                    while (k > 0 && q.rows_of[bi][off + k - 1].v.wire == top.v.wire) mask |= 1u << q.rows_of[bi][off + k - 1].coord, k--;
                     rrow = b.hstep(rrow, top.v, mask, alpha_f);
                 }
                 for (unsigned pt = 0; pt < M.n_pts; pt++) {
                     if (!invd.count({h, pt})) invd[{h, pt}] = b.inv(b.sub(z_of[{h, pt}], x_of[h]));
                     const V t = b.mul(b.sub(ro_terms[m].ry[pt], rrow), invd[{h, pt}]);
-                    roq[h] = b.mul_add(t, ro_terms[m].off_pow[pt], roq[h]);
+                    q.roq[h] = b.mul_add(t, ro_terms[m].off_pow[pt], q.roq[h]);
                 }
                 off += M.width;
             }
         }
+    }
+    void fold_layers(Query& q) {
         b.phase = "query: fold layers";
-        V eval = roq[hmax];
+        const std::vector<V>& idx = q.idx;
+        V eval = q.roq[hmax];
         V xi;  // 1 / x of the current layer's pair
         for (unsigned l = 0; l < n_layers; l++) {
             const unsigned log_len = hmax - l;
             const V sib = in_ext_at(r);
             r += 4;
             std::vector<std::array<V, 2>> path(log_len - 1);
-            for (unsigned q = 0; q + 1 < log_len; q++) path[q] = in_digest(r + 8 * (size_t)q);
+            for (unsigned p = 0; p + 1 < log_len; p++) path[p] = in_digest(r + 8 * (size_t)p);
             r += 8 * (size_t)(log_len - 1);
             V lo, hi;
             b.swap_if(idx[l], eval, sib, &lo, &hi);
@@ -1033,9 +1087,9 @@ static ChildValues verify_child_sym(Builder& b, const ChildVk& vk, uint32_t ci, 
                 std::vector<Lane> lanes;
                 Builder::ext_lanes(lo, &lanes), Builder::ext_lanes(hi, &lanes);
                 std::array<V, 2> cur = b.sponge(lanes);
-                for (unsigned q = 0; q + 1 < log_len; q++) {
+                for (unsigned p = 0; p + 1 < log_len; p++) {
                     std::array<V, 2> left, right;
-                    for (int k = 0; k < 2; k++) b.swap_if(kbits[q], cur[k], path[q][k], &left[k], &right[k]);
+                    for (int k = 0; k < 2; k++) b.swap_if(kbits[p], cur[k], path[p][k], &left[k], &right[k]);
                     cur = b.compress(left, right);
                 }
                 b.assert_eq(cur[0], fri_roots[l][0]);
@@ -1055,7 +1109,7 @@ static ChildValues verify_child_sym(Builder& b, const ChildVk& vk, uint32_t ci, 
             const V d = b.sub(hi, lo);
             const V t = b.mul(b.mul(betas[l], xi), d);
             eval = b.lin3(lo, b.ONE, d, half, t, mneg(half));
-            if (has[log_len - 1]) eval = b.mul_add(betas_sq[l], roq[log_len - 1], eval);
+            if (has[log_len - 1]) eval = b.mul_add(betas_sq[l], q.roq[log_len - 1], eval);
         }
         V want = fin[n_fin - 1];
         if (lfp) {
@@ -1068,12 +1122,31 @@ static ChildValues verify_child_sym(Builder& b, const ChildVk& vk, uint32_t ci, 
         }
         b.assert_eq(eval, want);
     }
-    b.close_input_rows();
-    b.c.sub.back().push_back(b.c.order.size());
-    b.phase = "statement";
-    if (r != vk.proof_words) throw BuildError{"internal: the circuit's walk over the proof does not end at its last word"};
-    return out;
+
+    // the queries' part ends; the walk over the proof must have ended at its last word
+    ChildValues finish() {
+        b.close_input_rows();
+        b.c.sub.back().push_back(b.c.order.size());
+        b.phase = "statement";
+        if (r != vk.proof_words) throw BuildError{"internal: the circuit's walk over the proof does not end at its last word"};
+        return std::move(out);
+    }
+};
+
+static ChildValues verify_child_sym(Builder& b, const ChildVk& vk, uint32_t ci, const std::vector<std::array<V, 8>>* prep_sym = nullptr) {
+    ChildVerifier cv(b, vk, ci, prep_sym);
+    cv.layout_matrices();
+    cv.read_fixed_part();
+    cv.run_transcript();
+    cv.constraints_at_zeta();
+    cv.fri_transcript();
+    cv.build_batches();
+    cv.reduced_opening_terms();
+    cv.sample_query_indices();
+    for (unsigned qn = 0; qn < vk.prm.num_queries; qn++) cv.verify_query(qn);
+    return cv.finish();
 }
+
 
 }  // namespace rec
 }  // namespace zk
@@ -1175,10 +1248,14 @@ void build_programs(RecCore& K, const unsigned min_log[2]) {
         auto slot = [&](int s) { return std::array<Expr, 4>{b.var(4 * s), b.var(4 * s + 1), b.var(4 * s + 2), b.var(4 * s + 3)}; };
         const auto a = slot(0), bb = slot(1), cc = slot(2), d = slot(3);
         const Expr qM = b.prep(8), qA = b.prep(9), qB = b.prep(10), qC = b.prep(11), qD = b.prep(12), qbase = b.prep(17);
-        const Expr ab[4] = {a[0] * bb[0] + (a[1] * bb[3] + a[2] * bb[2] + a[3] * bb[1]) * 11,
-                            a[0] * bb[1] + a[1] * bb[0] + (a[2] * bb[3] + a[3] * bb[2]) * 11,
-                            a[0] * bb[2] + a[1] * bb[1] + a[2] * bb[0] + a[3] * bb[3] * 11,
-                            a[0] * bb[3] + a[1] * bb[2] + a[2] * bb[1] + a[3] * bb[0]};
+        // the four coordinates of x y in F_p[X]/(X^4 - 11)
+        auto ext_product = [](const std::array<Expr, 4>& x, const std::array<Expr, 4>& y) {
+            return std::array<Expr, 4>{x[0] * y[0] + (x[1] * y[3] + x[2] * y[2] + x[3] * y[1]) * 11,
+                                       x[0] * y[1] + x[1] * y[0] + (x[2] * y[3] + x[3] * y[2]) * 11,
+                                       x[0] * y[2] + x[1] * y[1] + x[2] * y[0] + x[3] * y[3] * 11,
+                                       x[0] * y[3] + x[1] * y[2] + x[2] * y[1] + x[3] * y[0]};
+        };
+        const std::array<Expr, 4> ab = ext_product(a, bb);
         for (int k = 0; k < 4; k++) b.assert_zero(qM * ab[k] + qA * a[k] + qB * bb[k] + qC * cc[k] + qD * d[k] + b.prep(13 + k));
         for (int s = 0; s < 4; s++)
             for (int k = 1; k < 4; k++) b.assert_zero(qbase * b.var(4 * s + k));
@@ -1191,10 +1268,7 @@ void build_programs(RecCore& K, const unsigned min_log[2]) {
                 const int j = 3 - i;
                 const Expr hj = b.prep(19 + j);
                 const std::array<Expr, 4> nx = i < 3 ? slot(4 + i) : cc;
-                const Expr td[4] = {t[0] * d[0] + (t[1] * d[3] + t[2] * d[2] + t[3] * d[1]) * 11,
-                                    t[0] * d[1] + t[1] * d[0] + (t[2] * d[3] + t[3] * d[2]) * 11,
-                                    t[0] * d[2] + t[1] * d[1] + t[2] * d[0] + t[3] * d[3] * 11,
-                                    t[0] * d[3] + t[1] * d[2] + t[2] * d[1] + t[3] * d[0]};
+                const std::array<Expr, 4> td = ext_product(t, d);
                 for (int k = 0; k < 4; k++) {
                     Expr step = td[k] - t[k];
                     if (k == 0) step = step + bb[j];
@@ -1361,185 +1435,186 @@ static std::array<V, 2> key_commit_const(const ChildVk& vk) {
 // of its deferral region (4096 cells + 19 siblings; include/zkhip_vm_flow.hpp DEFERRAL_REGION_BYTES) and the claim-count flags
 constexpr size_t DEFERRAL_PV_AUX = 16 + 27 * 8, DEFERRAL_REGION_CELLS = 4096, DEFERRAL_REGION_SIBS = 19, DEFERRAL_MAX_CLAIMS = 63;
 
-// The statement logic behind the verified children, then the public-value binding and the parallelism check.
-static int finish_build(std::unique_ptr<zkhip_recursion>& R, const unsigned* min_log_height, zkhip_recursion** out) {
-    RecCore& K = *R->k;
-    const size_t max_children = K.max_children;
-    const StmtSpec& sp = K.spec;
-    const bool timing = getenv("ZKHIP_RECURSION_TIMING") != nullptr;   // stage times of the circuit builder on stderr
-    auto tprev = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        const auto now = std::chrono::steady_clock::now();
-        if (timing) std::fprintf(stderr, "[recursion build] %-28s %.3f s\n", what, std::chrono::duration<double>(now - tprev).count());
-        tprev = now;
-    };
-    try {
-        Builder b;
-        const size_t NS = K.n_state;
-        std::vector<ChildValues> kids;
-        std::vector<std::vector<std::array<V, 8>>> prep_in(max_children);   // uniform node: the children's preprocessed commitments
+// The circuit of one node as the steps finish_build calls in order: the children, the statement of the circuit's mode (each returns
+// the lanes of the node's public values), the public-value binding.
+struct NodeBuilder {
+    Builder& b;
+    const RecCore& K;
+    const ChildVk& vk;   // the key of slot 0 (every slot's but a join's slot 1)
+    const size_t max_children, n_airs, NS;
+    std::vector<ChildValues> kids;
+    std::vector<std::vector<std::array<V, 8>>> prep_in;   // uniform node: the children's preprocessed commitments
+
+    NodeBuilder(Builder& bb, const RecCore& core)
+        : b(bb), K(core), vk(core.vk), max_children(core.max_children), n_airs(core.vk.pg.size()), NS(core.n_state), prep_in(core.max_children) {}
+
+    std::array<V, 2> pack8(const V* v) { return std::array<V, 2>{b.pack({v[0], v[1], v[2], v[3]}), b.pack({v[4], v[5], v[6], v[7]})}; }
+    V not_of(const V& bit) { return b.lin(0, bit, V{}, b.NEG1, 0, V{}, 0, ext_one()); }   // 1 - bit
+
+    void verify_children() {
         for (size_t ci = 0; ci < max_children; ci++) {
-            const ChildVk& vk = K.vk_of(ci);
-            const size_t n_airs = vk.pg.size();
+            const ChildVk& cvk = K.vk_of(ci);
+            const size_t n = cvk.pg.size();
             b.close_input_rows();
             b.c.sections.push_back(b.c.order.size());
             if (K.mode == 2) {
-                prep_in[ci].resize(n_airs);
-                for (size_t a = 0; a < n_airs; a++)
-                    if (vk.has_prep[a])
-                        for (uint32_t k = 0; k < 8; k++) {
-                            Src sr;
-                            sr.kind = S_PREP, sr.child = (uint32_t)ci, sr.a = (uint32_t)a, sr.b = k;
-                            prep_in[ci][a][k] = b.in_base(sr);
-                        }
+                prep_in[ci].resize(n);
+                for (size_t a = 0; a < n; a++)
+                    if (cvk.has_prep[a])
+                        for (uint32_t k = 0; k < 8; k++) prep_in[ci][a][k] = b.in_base(make_src(S_PREP, (uint32_t)ci, (uint32_t)a, k));
             }
-            kids.push_back(verify_child_sym(b, vk, (uint32_t)ci, K.mode == 2 ? &prep_in[ci] : nullptr));
+            kids.push_back(verify_child_sym(b, cvk, (uint32_t)ci, K.mode == 2 ? &prep_in[ci] : nullptr));
         }
         b.close_input_rows();
         b.c.sections.push_back(b.c.order.size());
-        lap("children verified");
-        if (timing) {
-            std::map<std::string, size_t> rows, perms;   // (one literal may live at several addresses)
-            for (const auto& kv : b.phase_gates) rows[kv.first] += kv.second;
-            for (const auto& kv : b.phase_perms) perms[kv.first] += kv.second;
-            for (const auto& kv : rows) std::fprintf(stderr, "[recursion build]   rows %-48s %10zu\n", kv.first.c_str(), kv.second);
-            for (const auto& kv : perms) std::fprintf(stderr, "[recursion build]   perm %-48s %10zu\n", kv.first.c_str(), kv.second);
-        }
-        const ChildVk& vk = K.vk;
-        const size_t n_airs = vk.pg.size();
-        std::vector<Lane> pvl;   // the node's public values
-        auto pack8 = [&](const V* v) { return std::array<V, 2>{b.pack({v[0], v[1], v[2], v[3]}), b.pack({v[4], v[5], v[6], v[7]})}; };
-        if (K.mode == 4) {
-            // JOIN (a batch-like proof = the guest's root + the proof of what it deferred): slot 0 is a root under aggregation key A
-            // (its internal commitment must be A's own), slot 1 a deferral node whose chain starts at zero.  Public values: the root's
-            // statement, then the deferral accumulator -- the verifier opens the guest's claims in the final memory root and hashes them.
-            const std::vector<V>& rp = kids[0].pvs[K.vk.pg.size() - 1];
-            const std::vector<V>& dp = kids[1].pvs[K.vk_b->pg.size() - 1];
-            const std::array<V, 2> ic = key_commit_const(K.vk);
-            const std::array<V, 2> got = pack8(&rp[rp.size() - 8]);
-            for (int k = 0; k < 2; k++) b.assert_eq(got[k], ic[k]);
-            // (slot 1 may also be a FOLD of deferral nodes -- a node over their proofs with the chain as its chained state,
-            // [key digest (8) | chain before (8) | chain after (8) | accumulator (8)]: a task with more children than one deferral node takes)
-            const size_t o = dp.size() == 32 ? 8 : 0;
-            for (int k = 0; k < 8; k++) b.assert_zero(dp[o + k]);
-            for (const V& v : rp) pvl.push_back(Lane{v, -1});
-            for (int k = 0; k < 8; k++) pvl.push_back(Lane{dp[o + 8 + k], -1});
-        } else {
-        // presence flags: child 0 is present, present children form a prefix
+    }
+
+    // ZKHIP_RECURSION_TIMING: where the rows went
+    void print_phase_table() const {
+        std::map<std::string, size_t> rows, perms;   // (one literal may live at several addresses)
+        for (const auto& kv : b.phase_gates) rows[kv.first] += kv.second;
+        for (const auto& kv : b.phase_perms) perms[kv.first] += kv.second;
+        for (const auto& kv : rows) std::fprintf(stderr, "[recursion build]   rows %-48s %10zu\n", kv.first.c_str(), kv.second);
+        for (const auto& kv : perms) std::fprintf(stderr, "[recursion build]   perm %-48s %10zu\n", kv.first.c_str(), kv.second);
+    }
+
+    // JOIN (a batch-like proof = the guest's root + the proof of what it deferred): slot 0 is a root under aggregation key A
+    // (its internal commitment must be A's own), slot 1 a deferral node whose chain starts at zero.  Public values: the root's
+    // statement, then the deferral accumulator -- the verifier opens the guest's claims in the final memory root and hashes them.
+    std::vector<Lane> statement_join() {
+        std::vector<Lane> pvl;
+        const std::vector<V>& rp = kids[0].pvs[K.vk.pg.size() - 1];
+        const std::vector<V>& dp = kids[1].pvs[K.vk_b->pg.size() - 1];
+        const std::array<V, 2> ic = key_commit_const(K.vk);
+        const std::array<V, 2> got = pack8(&rp[rp.size() - 8]);
+        for (int k = 0; k < 2; k++) b.assert_eq(got[k], ic[k]);
+        // (slot 1 may also be a FOLD of deferral nodes -- a node over their proofs with the chain as its chained state,
+        // [key digest (8) | chain before (8) | chain after (8) | accumulator (8)]: a task with more children than one deferral node takes)
+        const size_t o = dp.size() == 32 ? 8 : 0;
+        for (int k = 0; k < 8; k++) b.assert_zero(dp[o + k]);
+        for (const V& v : rp) pvl.push_back(Lane{v, -1});
+        for (int k = 0; k < 8; k++) pvl.push_back(Lane{dp[o + 8 + k], -1});
+        return pvl;
+    }
+
+    // presence flags: child 0 is present, present children form a prefix
+    std::vector<V> presence_flags() {
         std::vector<V> flag(max_children);
         flag[0] = cst(ext_one());
         for (size_t ci = 1; ci < max_children; ci++) {
-            Src s;
-            s.kind = S_FLAG, s.child = (uint32_t)ci;
-            flag[ci] = b.in_base(s);
+            flag[ci] = b.in_base(make_src(S_FLAG, (uint32_t)ci));
             b.assert_bool(flag[ci]);
-            if (ci > 1) b.assert_product_zero(flag[ci], b.lin(0, flag[ci - 1], V{}, b.NEG1, 0, V{}, 0, ext_one()));
+            if (ci > 1) b.assert_product_zero(flag[ci], not_of(flag[ci - 1]));
         }
-        if (K.mode == 3) {
-            // DEFERRAL NODE (crates/prover/src/prover/mod.rs:200-282 VerifyProver; crates/types/circuit/src/lib.rs:137-154 verify_stark):
-            // every child is a ROOT proof under the fixed aggregation key of the child app.  Per child the circuit derives the claim a
-            // parent guest makes about it -- input commitment (sponge of the root's statement), exe commitment (entry pc, initial memory
-            // root), vm commitment (app-vk digest, leaf commitment), the 32 public-value bytes opened in the final memory root (their 16
-            // cells and the 27 siblings above the block pair are auxiliary inputs) -- requires exit code 0 and the key's own internal
-            // commitment, and chains acc <- compress(acc, chunk) over the claim's five 8-element chunks.
-            const size_t pa = n_airs - 1, NSc = 9;
-            const std::array<V, 2> ic = key_commit_const(vk);
-            std::array<V, 8> acc0;
-            for (uint32_t k = 0; k < 8; k++) {
-                Src sr;
-                sr.kind = S_COMMIT, sr.a = 2, sr.b = k;
-                acc0[k] = b.in_base(sr);
+        return flag;
+    }
+
+    // DEFERRAL NODE (crates/prover/src/prover/mod.rs:200-282 VerifyProver; crates/types/circuit/src/lib.rs:137-154 verify_stark):
+    // every child is a ROOT proof under the fixed aggregation key of the child app.  Per child the circuit derives the claim a
+    // parent guest makes about it -- input commitment (sponge of the root's statement), exe commitment (entry pc, initial memory
+    // root), vm commitment (app-vk digest, leaf commitment), the 32 public-value bytes opened in the final memory root (their 16
+    // cells and the 27 siblings above the block pair are auxiliary inputs) -- requires exit code 0 and the key's own internal
+    // commitment, and chains acc <- compress(acc, chunk) over the claim's five 8-element chunks.
+    std::vector<Lane> statement_deferral(const std::vector<V>& flag) {
+        const size_t pa = n_airs - 1, NSc = 9;
+        const std::array<V, 2> ic = key_commit_const(vk);
+        std::array<V, 8> acc0;
+        for (uint32_t k = 0; k < 8; k++) acc0[k] = b.in_base(make_src(S_COMMIT, 0, 2, k));
+        std::array<V, 2> acc = pack8(acc0.data());
+        for (size_t ci = 0; ci < max_children; ci++) {
+            const std::vector<V>& pv = kids[ci].pvs[pa];
+            const V* app = &pv[0];
+            const V pc_start = pv[8], pc_end = pv[8 + NSc];
+            const V *root0 = &pv[9], *root1 = &pv[9 + NSc], *lc = &pv[16 + 2 * NSc], *icv = &pv[24 + 2 * NSc];
+            if (!K.region_index) {   // (a join pins its root's internal commitment itself)
+                const std::array<V, 2> got_ic = pack8(icv);
+                for (int k = 0; k < 2; k++) b.assert_eq(got_ic[k], ic[k]);
             }
-            std::array<V, 2> acc = pack8(acc0.data());
-            for (size_t ci = 0; ci < max_children; ci++) {
-                const std::vector<V>& pv = kids[ci].pvs[pa];
-                const V* app = &pv[0];
-                const V pc_start = pv[8], pc_end = pv[8 + NSc];
-                const V *root0 = &pv[9], *root1 = &pv[9 + NSc], *lc = &pv[16 + 2 * NSc], *icv = &pv[24 + 2 * NSc];
-                if (!K.region_index) {   // (a join pins its root's internal commitment itself)
-                    const std::array<V, 2> got_ic = pack8(icv);
-                    for (int k = 0; k < 2; k++) b.assert_eq(got_ic[k], ic[k]);
-                }
-                b.assert_zero(pc_end);
-                std::vector<V> aux(K.n_aux);
-                for (uint32_t i = 0; i < K.n_aux; i++) {
-                    Src sr;
-                    sr.kind = S_AUX, sr.child = (uint32_t)ci, sr.a = i;
-                    aux[i] = b.in_base(sr);
-                }
-                const V zero = cst(ext_zero());
-                const std::array<V, 2> z2{zero, zero};
-                const std::array<V, 2> cells0 = pack8(&aux[0]), cells1 = pack8(&aux[8]);
-                std::array<V, 2> cur = b.compress(b.compress(cells0, z2), b.compress(cells1, z2));   // the two public-value blocks are siblings
-                uint32_t idx = (3u << 26) >> 1;
-                for (unsigned l = 27; l > 0; l--, idx >>= 1) {
-                    const std::array<V, 2> sib = pack8(&aux[16 + 8 * (27 - l)]);
-                    cur = (idx & 1u) ? b.compress(sib, cur) : b.compress(cur, sib);
-                }
-                const std::array<V, 2> r1 = pack8(root1);
-                for (int k = 0; k < 2; k++) b.assert_eq(cur[k], r1[k]);
-                if (K.region_index) {
-                    // The child is a JOIN proof (a batch under a bundle: a proof whose own guest deferred verification).  Its statement ends
-                    // with the chain its deferral node verified; what a verifier of the join does on the host -- open the guest's deferral
-                    // region (4096 cells = 512 blocks, one subtree of the memory tree) in the final memory root, read the n claims, chain
-                    // them, compare -- happens here: cells, the 20 siblings above the subtree and n one-hot-prefix flags are auxiliary inputs.
-                    // (A commitment word is read as the field element lo + 2^16 hi: a word >= p, which the host verifier refuses, is its
-                    // residue here.)
-                    const V* rc = &aux[DEFERRAL_PV_AUX];
-                    const V* rs = rc + DEFERRAL_REGION_CELLS;
-                    const V* fl = rs + 8 * DEFERRAL_REGION_SIBS;
-                    std::vector<std::array<V, 2>> level(DEFERRAL_REGION_CELLS / 8);
-                    for (size_t blk = 0; blk < level.size(); blk++) level[blk] = b.compress(pack8(rc + 8 * blk), z2);
-                    while (level.size() > 1) {
-                        std::vector<std::array<V, 2>> up(level.size() / 2);
-                        for (size_t i = 0; i < up.size(); i++) up[i] = b.compress(level[2 * i], level[2 * i + 1]);
-                        level = std::move(up);
-                    }
-                    std::array<V, 2> node = level[0];
-                    uint32_t ridx = K.region_index;
-                    for (size_t l = 0; l < DEFERRAL_REGION_SIBS; l++, ridx >>= 1) {
-                        const std::array<V, 2> sib = pack8(rs + 8 * l);
-                        node = (ridx & 1u) ? b.compress(sib, node) : b.compress(node, sib);
-                    }
-                    for (int k = 0; k < 2; k++) b.assert_eq(node[k], r1[k]);
-                    // word 0 of the region = n <= 63: flags f_0 >= f_1 >= ... with sum n; at least one claim (a join without claims is refused)
-                    b.assert_zero(rc[1]);
-                    V count = cst(ext_zero());
-                    for (size_t k = 0; k < DEFERRAL_MAX_CLAIMS; k++) {
-                        b.assert_bool(fl[k]);
-                        if (k > 0) b.assert_product_zero(fl[k], b.lin(0, fl[k - 1], V{}, b.NEG1, 0, V{}, 0, ext_one()));
-                        count = b.add(count, fl[k]);
-                    }
-                    b.assert_eq(count, rc[0]);
-                    b.assert_eq(fl[0], cst(ext_one()));
-                    std::array<V, 2> chain{zero, zero};
-                    const uint32_t two16 = to_monty(65536);
-                    for (size_t k = 0; k < DEFERRAL_MAX_CLAIMS; k++) {
-                        const V* cw = rc + 2 * (32 + 32 * k);   // the claim's 32 words as 64 cells
-                        std::array<V, 2> nx = chain;
-                        for (int c3 = 0; c3 < 3; c3++) {
-                            V e[8];
-                            for (int j = 0; j < 8; j++) e[j] = b.lin3(cw[2 * (8 * c3 + j)], b.ONE, cw[2 * (8 * c3 + j) + 1], two16, V{}, 0);
-                            nx = b.compress(nx, pack8(e));
-                        }
-                        for (int h = 0; h < 2; h++) nx = b.compress(nx, pack8(cw + 48 + 8 * h));
-                        for (int q = 0; q < 2; q++) chain[q] = b.select(fl[k], nx[q], chain[q]);
-                    }
-                    const std::array<V, 2> stated = pack8(&pv[50]);
-                    for (int k = 0; k < 2; k++) b.assert_eq(chain[k], stated[k]);
-                }
-                std::vector<Lane> stmt_lanes;
-                for (const V& v : pv) stmt_lanes.push_back(Lane{v, -1});
-                const std::array<V, 2> input_commit = b.sponge(stmt_lanes);
-                const std::array<V, 2> exe_commit = b.compress(pack8(root0), {b.pack({pc_start, zero, zero, zero}), zero});
-                const std::array<V, 2> vm_commit = b.compress(pack8(app), pack8(lc));
-                std::array<V, 2> nx = acc;
-                for (const std::array<V, 2>& chunk : {input_commit, exe_commit, vm_commit, cells0, cells1}) nx = b.compress(nx, chunk);
-                for (int k = 0; k < 2; k++) acc[k] = b.select(flag[ci], nx[k], acc[k]);
+            b.assert_zero(pc_end);
+            std::vector<V> aux(K.n_aux);
+            for (uint32_t i = 0; i < K.n_aux; i++) aux[i] = b.in_base(make_src(S_AUX, (uint32_t)ci, i));
+            const V zero = cst(ext_zero());
+            const std::array<V, 2> z2{zero, zero};
+            const std::array<V, 2> cells0 = pack8(&aux[0]), cells1 = pack8(&aux[8]);
+            std::array<V, 2> cur = b.compress(b.compress(cells0, z2), b.compress(cells1, z2));   // the two public-value blocks are siblings
+            uint32_t idx = (3u << 26) >> 1;
+            for (unsigned l = 27; l > 0; l--, idx >>= 1) {
+                const std::array<V, 2> sib = pack8(&aux[16 + 8 * (27 - l)]);
+                cur = (idx & 1u) ? b.compress(sib, cur) : b.compress(cur, sib);
             }
-            for (int k = 0; k < 8; k++) pvl.push_back(Lane{acc0[k], -1});
-            Builder::ext_lanes(acc[0], &pvl), Builder::ext_lanes(acc[1], &pvl);
-        } else {
+            const std::array<V, 2> r1 = pack8(root1);
+            for (int k = 0; k < 2; k++) b.assert_eq(cur[k], r1[k]);
+            if (K.region_index) open_deferral_region(&aux[DEFERRAL_PV_AUX], r1, &pv[50]);
+            std::vector<Lane> stmt_lanes;
+            for (const V& v : pv) stmt_lanes.push_back(Lane{v, -1});
+            const std::array<V, 2> input_commit = b.sponge(stmt_lanes);
+            const std::array<V, 2> exe_commit = b.compress(pack8(root0), {b.pack({pc_start, zero, zero, zero}), zero});
+            const std::array<V, 2> vm_commit = b.compress(pack8(app), pack8(lc));
+            std::array<V, 2> nx = acc;
+            for (const std::array<V, 2>& chunk : {input_commit, exe_commit, vm_commit, cells0, cells1}) nx = b.compress(nx, chunk);
+            for (int k = 0; k < 2; k++) acc[k] = b.select(flag[ci], nx[k], acc[k]);
+        }
+        std::vector<Lane> pvl;
+        for (int k = 0; k < 8; k++) pvl.push_back(Lane{acc0[k], -1});
+        Builder::ext_lanes(acc[0], &pvl), Builder::ext_lanes(acc[1], &pvl);
+        return pvl;
+    }
+    // The child is a JOIN proof (a batch under a bundle: a proof whose own guest deferred verification).  Its statement ends
+    // with the chain its deferral node verified; what a verifier of the join does on the host -- open the guest's deferral
+    // region (4096 cells = 512 blocks, one subtree of the memory tree) in the final memory root `r1`, read the n claims, chain
+    // them, compare with the eight words at `stated_chain` -- happens here: cells, the 20 siblings above the subtree and n
+    // one-hot-prefix flags are auxiliary inputs (`rc`).  (A commitment word is read as the field element lo + 2^16 hi: a word >= p, which the host verifier refuses, is
+    // its residue here.)
+    void open_deferral_region(const V* rc, const std::array<V, 2>& r1, const V* stated_chain) {
+        const V zero = cst(ext_zero());
+        const std::array<V, 2> z2{zero, zero};
+        const V* rs = rc + DEFERRAL_REGION_CELLS;
+        const V* fl = rs + 8 * DEFERRAL_REGION_SIBS;
+        std::vector<std::array<V, 2>> level(DEFERRAL_REGION_CELLS / 8);
+        for (size_t blk = 0; blk < level.size(); blk++) level[blk] = b.compress(pack8(rc + 8 * blk), z2);
+        while (level.size() > 1) {
+            std::vector<std::array<V, 2>> up(level.size() / 2);
+            for (size_t i = 0; i < up.size(); i++) up[i] = b.compress(level[2 * i], level[2 * i + 1]);
+            level = std::move(up);
+        }
+        std::array<V, 2> node = level[0];
+        uint32_t ridx = K.region_index;
+        for (size_t l = 0; l < DEFERRAL_REGION_SIBS; l++, ridx >>= 1) {
+            const std::array<V, 2> sib = pack8(rs + 8 * l);
+            node = (ridx & 1u) ? b.compress(sib, node) : b.compress(node, sib);
+        }
+        for (int k = 0; k < 2; k++) b.assert_eq(node[k], r1[k]);
+        // word 0 of the region = n <= 63: flags f_0 >= f_1 >= ... with sum n; at least one claim (a join without claims is refused)
+        b.assert_zero(rc[1]);
+        V count = cst(ext_zero());
+        for (size_t k = 0; k < DEFERRAL_MAX_CLAIMS; k++) {
+            b.assert_bool(fl[k]);
+            if (k > 0) b.assert_product_zero(fl[k], not_of(fl[k - 1]));
+            count = b.add(count, fl[k]);
+        }
+        b.assert_eq(count, rc[0]);
+        b.assert_eq(fl[0], cst(ext_one()));
+        std::array<V, 2> chain{zero, zero};
+        const uint32_t two16 = to_monty(65536);
+        for (size_t k = 0; k < DEFERRAL_MAX_CLAIMS; k++) {
+            const V* cw = rc + 2 * (32 + 32 * k);   // the claim's 32 words as 64 cells
+            std::array<V, 2> nx = chain;
+            for (int c3 = 0; c3 < 3; c3++) {
+                V e[8];
+                for (int j = 0; j < 8; j++) e[j] = b.lin3(cw[2 * (8 * c3 + j)], b.ONE, cw[2 * (8 * c3 + j) + 1], two16, V{}, 0);
+                nx = b.compress(nx, pack8(e));
+            }
+            for (int h = 0; h < 2; h++) nx = b.compress(nx, pack8(cw + 48 + 8 * h));
+            for (int q = 0; q < 2; q++) chain[q] = b.select(fl[k], nx[q], chain[q]);
+        }
+        const std::array<V, 2> stated = pack8(stated_chain);
+        for (int k = 0; k < 2; k++) b.assert_eq(chain[k], stated[k]);
+    }
+
+    // LEAF, INTERNAL and UNIFORM nodes: [vk(8) start(K) end(K) acc(8)] (+ [leaf commitment (8) | internal commitment (8)] under one
+    // key: zero at a leaf, whose proofs must have the public-value layout of the internal circuit's)
+    std::vector<Lane> statement_chain(const std::vector<V>& flag) {
+        const StmtSpec& sp = K.spec;
         auto pv_of = [&](size_t ci, const std::pair<uint32_t, uint32_t>& at) { return kids[ci].pvs[at.first][at.second]; };
         // app vk digest: the constant digest of the child vk (leaf level) or what the children carry (all equal)
         std::array<V, 8> vkd;
@@ -1552,77 +1627,9 @@ static int finish_build(std::unique_ptr<zkhip_recursion>& R, const unsigned* min
             for (size_t ci = 1; ci < max_children; ci++)
                 for (int k = 0; k < 8; k++) b.assert_product_zero(flag[ci], b.sub(kids[ci].pvs[pa][k], vkd[k]));
         }
-        // one key: every child is a proof of the leaf circuit or of the internal circuit -- the digest of ITS preprocessed commitments
-        // equals the leaf / internal commitment this node states, and an internal child states the same pair (by induction every
-        // node below is under one of the two; the verifier holds the pair)
         std::array<V, 8> leaf_commit, internal_commit;
         for (int k = 0; k < 8; k++) leaf_commit[k] = internal_commit[k] = cst(ext_zero());
-        if (K.mode == 2) {
-            // the leaf circuits' commitments (one per shape) and the internal circuit's: values of this node; what it STATES as its leaf
-            // commitment is the one commitment (one shape) or the sponge of the list
-            const size_t S = K.n_leaf_shapes;
-            std::vector<std::array<V, 8>> leaf_list(S);
-            for (uint32_t j = 0; j < S; j++)
-                for (uint32_t k = 0; k < 8; k++) {
-                    Src sr;
-                    sr.kind = S_COMMIT, sr.a = 0, sr.b = 8 * j + k;
-                    leaf_list[j][k] = b.in_base(sr);
-                }
-            for (uint32_t k = 0; k < 8; k++) {
-                Src sr;
-                sr.kind = S_COMMIT, sr.a = 1, sr.b = k;
-                internal_commit[k] = b.in_base(sr);
-            }
-            std::vector<std::array<V, 2>> lcs(S);
-            for (size_t j = 0; j < S; j++) lcs[j] = {b.pack({leaf_list[j][0], leaf_list[j][1], leaf_list[j][2], leaf_list[j][3]}),
-                                                   b.pack({leaf_list[j][4], leaf_list[j][5], leaf_list[j][6], leaf_list[j][7]})};
-            if (S == 1) {
-                leaf_commit = leaf_list[0];
-            } else {
-                std::vector<Lane> lanes;
-                for (size_t j = 0; j < S; j++)
-                    for (int k = 0; k < 8; k++) lanes.push_back(Lane{leaf_list[j][k], -1});
-                const std::array<V, 2> h = b.sponge(lanes);
-                const std::array<V, 4> h0 = b.unpack(h[0]), h1 = b.unpack(h[1]);
-                for (int k = 0; k < 4; k++) leaf_commit[k] = h0[k], leaf_commit[4 + k] = h1[k];
-            }
-            const std::array<V, 2> ic{b.pack({internal_commit[0], internal_commit[1], internal_commit[2], internal_commit[3]}),
-                                      b.pack({internal_commit[4], internal_commit[5], internal_commit[6], internal_commit[7]})};
-            const size_t pa = n_airs - 1, o = 16 + 2 * NS;
-            for (size_t ci = 0; ci < max_children; ci++) {   // (an absent slot repeats child 0, commitments and kind included)
-                Src sr;
-                sr.kind = S_KIND, sr.child = (uint32_t)ci, sr.a = 0;
-                const V is_leaf = b.in_base(sr);
-                b.assert_bool(is_leaf);
-                // which leaf circuit: a one-hot selector over the shapes (one shape: the selector is is_leaf itself)
-                std::vector<V> sel(S, is_leaf);
-                if (S > 1) {
-                    V sum = cst(ext_zero());
-                    for (uint32_t j = 0; j < S; j++) {
-                        sr.a = j + 1;
-                        sel[j] = b.in_base(sr);
-                        b.assert_bool(sel[j]);
-                        sum = b.add(sum, sel[j]);
-                    }
-                    b.assert_eq(sum, is_leaf);
-                }
-                std::vector<Lane> lanes;
-                for (size_t a = 0; a < n_airs; a++)
-                    if (vk.has_prep[a])
-                        for (int k = 0; k < 8; k++) lanes.push_back(Lane{prep_in[ci][a][k], -1});
-                const std::array<V, 2> d = b.sponge(lanes);
-                for (int k = 0; k < 2; k++) {
-                    V target = ic[k];   // ic + sum_j sel_j (lc_j - ic)
-                    for (size_t j = 0; j < S; j++) target = b.mul_add(sel[j], b.sub(lcs[j][k], ic[k]), target);
-                    b.assert_eq(d[k], target);
-                }
-                const V is_node = b.lin(0, is_leaf, V{}, b.NEG1, 0, V{}, 0, ext_one());
-                for (int k = 0; k < 8; k++) {
-                    b.assert_product_zero(is_node, b.sub(kids[ci].pvs[pa][o + k], leaf_commit[k]));
-                    b.assert_product_zero(is_node, b.sub(kids[ci].pvs[pa][o + 8 + k], internal_commit[k]));
-                }
-            }
-        }
+        if (K.mode == 2) one_key_commitments(leaf_commit, internal_commit);
         // chained state
         std::vector<V> start(NS), end(NS);
         for (size_t k = 0; k < NS; k++) start[k] = pv_of(0, sp.start[k]), end[k] = pv_of(0, sp.end[k]);
@@ -1649,8 +1656,7 @@ static int finish_build(std::unique_ptr<zkhip_recursion>& R, const unsigned* min
             const std::array<V, 2> nx = b.compress(acc, h);
             for (int k = 0; k < 2; k++) acc[k] = b.select(flag[ci], nx[k], acc[k]);
         }
-        // public values of the node: [vk(8) start(K) end(K) acc(8)] (+ [leaf commitment (8) | internal commitment (8)] under one key: zero
-        // at a leaf, whose proofs must have the public-value layout of the internal circuit's), bound four at a time
+        std::vector<Lane> pvl;
         for (int k = 0; k < 8; k++) pvl.push_back(Lane{vkd[k], -1});
         for (size_t k = 0; k < NS; k++) pvl.push_back(Lane{start[k], -1});
         for (size_t k = 0; k < NS; k++) pvl.push_back(Lane{end[k], -1});
@@ -1659,71 +1665,151 @@ static int finish_build(std::unique_ptr<zkhip_recursion>& R, const unsigned* min
             for (int k = 0; k < 8; k++) pvl.push_back(Lane{leaf_commit[k], -1});
             for (int k = 0; k < 8; k++) pvl.push_back(Lane{internal_commit[k], -1});
         }
+        return pvl;
+    }
+    // one key: every child is a proof of the leaf circuit or of the internal circuit -- the digest of ITS preprocessed commitments
+    // equals the leaf / internal commitment this node states, and an internal child states the same pair (by induction every
+    // node below is under one of the two; the verifier holds the pair)
+    void one_key_commitments(std::array<V, 8>& leaf_commit, std::array<V, 8>& internal_commit) {
+        // the leaf circuits' commitments (one per shape) and the internal circuit's: values of this node; what it STATES as its leaf
+        // commitment is the one commitment (one shape) or the sponge of the list
+        const size_t S = K.n_leaf_shapes;
+        std::vector<std::array<V, 8>> leaf_list(S);
+        for (uint32_t j = 0; j < S; j++)
+            for (uint32_t k = 0; k < 8; k++) leaf_list[j][k] = b.in_base(make_src(S_COMMIT, 0, 0, 8 * j + k));
+        for (uint32_t k = 0; k < 8; k++) internal_commit[k] = b.in_base(make_src(S_COMMIT, 0, 1, k));
+        std::vector<std::array<V, 2>> lcs(S);
+        for (size_t j = 0; j < S; j++) lcs[j] = pack8(leaf_list[j].data());
+        if (S == 1) {
+            leaf_commit = leaf_list[0];
+        } else {
+            std::vector<Lane> lanes;
+            for (size_t j = 0; j < S; j++)
+                for (int k = 0; k < 8; k++) lanes.push_back(Lane{leaf_list[j][k], -1});
+            const std::array<V, 2> h = b.sponge(lanes);
+            const std::array<V, 4> h0 = b.unpack(h[0]), h1 = b.unpack(h[1]);
+            for (int k = 0; k < 4; k++) leaf_commit[k] = h0[k], leaf_commit[4 + k] = h1[k];
         }
+        const std::array<V, 2> ic = pack8(internal_commit.data());
+        const size_t pa = n_airs - 1, o = 16 + 2 * NS;
+        for (size_t ci = 0; ci < max_children; ci++) {   // (an absent slot repeats child 0, commitments and kind included)
+            const V is_leaf = b.in_base(make_src(S_KIND, (uint32_t)ci, 0));
+            b.assert_bool(is_leaf);
+            // which leaf circuit: a one-hot selector over the shapes (one shape: the selector is is_leaf itself)
+            std::vector<V> sel(S, is_leaf);
+            if (S > 1) {
+                V sum = cst(ext_zero());
+                for (uint32_t j = 0; j < S; j++) {
+                    sel[j] = b.in_base(make_src(S_KIND, (uint32_t)ci, j + 1));
+                    b.assert_bool(sel[j]);
+                    sum = b.add(sum, sel[j]);
+                }
+                b.assert_eq(sum, is_leaf);
+            }
+            std::vector<Lane> lanes;
+            for (size_t a = 0; a < n_airs; a++)
+                if (vk.has_prep[a])
+                    for (int k = 0; k < 8; k++) lanes.push_back(Lane{prep_in[ci][a][k], -1});
+            const std::array<V, 2> d = b.sponge(lanes);
+            for (int k = 0; k < 2; k++) {
+                V target = ic[k];   // ic + sum_j sel_j (lc_j - ic)
+                for (size_t j = 0; j < S; j++) target = b.mul_add(sel[j], b.sub(lcs[j][k], ic[k]), target);
+                b.assert_eq(d[k], target);
+            }
+            const V is_node = not_of(is_leaf);
+            for (int k = 0; k < 8; k++) {
+                b.assert_product_zero(is_node, b.sub(kids[ci].pvs[pa][o + k], leaf_commit[k]));
+                b.assert_product_zero(is_node, b.sub(kids[ci].pvs[pa][o + 8 + k], internal_commit[k]));
+            }
         }
+    }
+
+    // the node's public values, bound four at a time
+    void bind_public_values(std::vector<Lane> pvl) {
         b.c.n_pvs = pvl.size();
         while (pvl.size() % 4) pvl.push_back(Lane{cst(ext_zero()), -1});
         for (size_t g = 0; g < pvl.size(); g += 4) b.c.pv_wires.push_back(b.use(b.pack_lanes(&pvl[g])));
-        lap("statement");
-        // May the queries of a child run side by side?  Every wire a query part reads must be written by a constant row, by the child's
-        // part before its queries, or by the same query part (roles: 2 = written here, 1 = read here; a permutation reads in, writes out).
-        {
-            Circuit& c = b.c;
-            const size_t n_children = c.sections.size() - 1;
-            bool ok = c.sub.size() == n_children;
-            auto is_const_row = [](const Gate& G) { return G.kind == K_LIN && !G.role[0] && !G.role[1] && !G.role[3]; };
-            std::vector<uint32_t> part_of_wire(c.n_wires + 1, 0);   // 0 = constant, else 1 + part id
-            // part ids: child i: pre = 3 i (n_q + 2) ... keep it simple: id = (i, k) -> i * stride + k, k = 0 pre, 1 .. n_q queries, n_q + 1 post
-            size_t stride = 0;
-            for (const auto& sb : c.sub) stride = std::max(stride, sb.size() + 2);
-            auto part_at = [&](size_t oi) -> uint32_t {
-                size_t i = std::upper_bound(c.sections.begin(), c.sections.end(), oi) - c.sections.begin() - 1;
-                if (i >= n_children) return (uint32_t)(n_children * stride + 1);   // the statement logic behind the children
-                const auto& sb = c.sub[i];
-                const size_t k = std::upper_bound(sb.begin(), sb.end(), oi) - sb.begin();   // 0 = before the queries
-                return (uint32_t)(i * stride + k + 1);
-            };
-            for (size_t pass = 0; pass < 2 && ok; pass++) {
-                size_t cur_i = 0, cur_k = 0;   // part_at(oi) for rising oi without its two binary searches (11 M rows for a 51-chip child)
-                for (size_t oi = 0; oi < c.order.size() && ok; oi++) {
-                    const Op& op = c.order[oi];
-                    uint32_t part;
-                    if (oi < c.sections[0]) {
-                        part = part_at(oi);
-                    } else {
-                        while (cur_i + 1 < c.sections.size() && c.sections[cur_i + 1] <= oi) cur_i++, cur_k = 0;
-                        if (cur_i >= n_children) {
-                            part = (uint32_t)(n_children * stride + 1);
-                        } else {
-                            const auto& sb = c.sub[cur_i];
-                            while (cur_k < sb.size() && sb[cur_k] <= oi) cur_k++;
-                            part = (uint32_t)(cur_i * stride + cur_k + 1);
-                        }
-                    }
-                    const size_t i = (part - 1) / stride, k = (part - 1) % stride;
-                    const bool is_query = i < n_children && k >= 1 && k + 1 < c.sub[i].size() + 1 && k <= c.sub[i].size() - 1;
-                    auto wr = [&](uint32_t w, bool constant) {
-                        if (pass == 0) part_of_wire[w] = constant ? 0 : part;
-                    };
-                    auto rd = [&](uint32_t w) {
-                        if (pass == 0 || !is_query || !w) return;
-                        const uint32_t src = part_of_wire[w];
-                        if (src != 0 && src != part && src != (uint32_t)(i * stride + 1)) ok = false;   // not constant, not own, not the child's part before the queries
-                    };
-                    if (op.is_perm) {
-                        for (int j = 0; j < 4; j++) rd(c.perms[op.idx].in[j]), wr(c.perms[op.idx].out[j], false);
-                    } else {
-                        const Gate& G = c.gates[op.idx];
-                        for (int sl = 0; sl < 4; sl++) {
-                            if (G.role[sl] == 2) wr(G.w[sl], is_const_row(G));
-                            else if (G.role[sl] == 1) rd(G.w[sl]);
-                            if (G.kind == K_INPUT && G.role[sl] == 2 && (G.src[sl].kind == S_HINT_BIT || G.src[sl].kind == S_HINT_COORD)) rd(G.src[sl].a);
-                        }
-                    }
+    }
+};
+
+// May the queries of a child run side by side?  Every wire a query part reads must be written by a constant row, by the child's
+// part before its queries, or by the same query part (roles: 2 = written here, 1 = read here; a permutation reads in, writes out).
+// The parts of child i are numbered i * stride + k + 1 -- k = 0 before the queries, k = 1 .. n_q the queries, k = n_q + 1 after them --,
+// the statement logic behind the children n_children * stride + 1, and 0 stands for a constant wire.  The order is walked twice with
+// one cursor that only moves forward (11 M rows for a 51-chip child): first every wire's writer is noted, then every read is checked.
+static bool check_query_independence(const Circuit& c) {
+    const size_t n_children = c.sections.size() - 1;
+    if (c.sub.size() != n_children) return false;
+    std::vector<uint32_t> part_of_wire(c.n_wires + 1, 0);
+    size_t stride = 0;
+    for (const auto& sb : c.sub) stride = std::max(stride, sb.size() + 2);
+    const uint32_t statement = (uint32_t)(n_children * stride + 1);
+    for (int pass = 0; pass < 2; pass++) {
+        size_t i = 0, k = 0;   // the cursor: child section i, k boundaries of c.sub[i] passed
+        for (size_t oi = 0; oi < c.order.size(); oi++) {
+            uint32_t part = statement, before_queries = 0;
+            bool is_query = false;
+            if (oi >= c.sections[0]) {
+                while (i + 1 < c.sections.size() && c.sections[i + 1] <= oi) i++, k = 0;
+                if (i < n_children) {
+                    const auto& sb = c.sub[i];
+                    while (k < sb.size() && sb[k] <= oi) k++;
+                    part = (uint32_t)(i * stride + k + 1), before_queries = (uint32_t)(i * stride + 1);
+                    is_query = k != 0 && k != sb.size();   // neither the part before the queries nor the part after
                 }
             }
-            c.query_parallel = ok && process_config().parallel_queries;
+            auto wr = [&](uint32_t w, bool constant) {
+                if (pass == 0) part_of_wire[w] = constant ? 0 : part;
+            };
+            auto rd = [&](uint32_t w) {   // (true: the read keeps the queries independent)
+                if (pass == 0 || !is_query || !w) return true;
+                const uint32_t from = part_of_wire[w];
+                return from == 0 || from == part || from == before_queries;
+            };
+            const Op& op = c.order[oi];
+            bool ok = true;
+            if (op.is_perm) {
+                for (int j = 0; j < 4; j++) ok &= rd(c.perms[op.idx].in[j]), wr(c.perms[op.idx].out[j], false);
+            } else {
+                const Gate& G = c.gates[op.idx];
+                for (int sl = 0; sl < 4; sl++) {
+                    if (G.role[sl] == 2) wr(G.w[sl], is_const_row(G));
+                    else if (G.role[sl] == 1) ok &= rd(G.w[sl]);
+                    if (G.kind == K_INPUT && G.role[sl] == 2 && (G.src[sl].kind == S_HINT_BIT || G.src[sl].kind == S_HINT_COORD)) ok &= rd(G.src[sl].a);
+                }
+            }
+            if (!ok) return false;
         }
+    }
+    return true;
+}
+
+// The statement logic behind the verified children, then the public-value binding and the parallelism check.
+static int finish_build(std::unique_ptr<zkhip_recursion>& R, const unsigned* min_log_height, zkhip_recursion** out) {
+    RecCore& K = *R->k;
+    const bool timing = getenv("ZKHIP_RECURSION_TIMING") != nullptr;   // stage times of the circuit builder on stderr
+    auto tprev = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+        const auto now = std::chrono::steady_clock::now();
+        if (timing) std::fprintf(stderr, "[recursion build] %-28s %.3f s\n", what, std::chrono::duration<double>(now - tprev).count());
+        tprev = now;
+    };
+    try {
+        Builder b;
+        NodeBuilder node(b, K);
+        node.verify_children();
+        lap("children verified");
+        if (timing) node.print_phase_table();
+        std::vector<Lane> pvl;   // the node's public values
+        if (K.mode == 4) {
+            pvl = node.statement_join();
+        } else {
+            const std::vector<V> flag = node.presence_flags();
+            pvl = K.mode == 3 ? node.statement_deferral(flag) : node.statement_chain(flag);
+        }
+        node.bind_public_values(std::move(pvl));
+        lap("statement");
+        b.c.query_parallel = check_query_independence(b.c) && process_config().parallel_queries;
         lap("query independence");
         K.c = std::move(b.c);
     } catch (const BuildError& e) {
@@ -1735,6 +1821,7 @@ static int finish_build(std::unique_ptr<zkhip_recursion>& R, const unsigned* min
     *out = R.release();
     return ZKHIP_OK;
 }
+
 
 extern "C" {
 
@@ -1933,81 +2020,56 @@ struct DeferralIn {
     const uint32_t* aux;         // [child][16 public-value cells | 27 x 8 sibling digests above the block pair, bottom-up], canonical
     const uint32_t* acc_start;   // the chain's value before this node's children
 };
-int recursion_witness(zkhip_recursion* R, const uint8_t* const* proofs, const size_t* proof_lens, const uint32_t* const* const* child_pvs,
-                      size_t n_present, uint32_t* node_pvs_out, const UniformIn* uni, const DeferralIn* def = nullptr) {
-    if (!R || !proofs || !proof_lens || n_present == 0 || n_present > R->k->max_children) return ZKHIP_ERR_INVALID;
-    const RecCore& K = *R->k;
-    if ((K.mode == 2) != (uni != nullptr) || (K.mode == 3) != (def != nullptr)) {
-        R->error = K.mode == 2   ? "a uniform node circuit takes its children's commitments and kinds (zkhip_recursion_witness_uniform)"
-                   : K.mode == 3 ? "a deferral node circuit takes the openings of its children's public values (zkhip_recursion_witness_deferral)"
-                                 : "this circuit is built for one child verifying key (zkhip_recursion_witness)";
-        return ZKHIP_ERR_INVALID;
-    }
-    if (K.mode == 4 && n_present != 2) {
-        R->error = "a join takes the root proof and the deferral node's proof";
-        return ZKHIP_ERR_INVALID;
-    }
+
+// One run of the circuit on concrete proofs: where the inputs come from and how a stretch of the order is evaluated.
+// (Constant rows are filled in once, before the sections run side by side: `run` skips them.)
+struct WitnessRun {
+    const RecCore& K;
+    const Circuit& c;
+    Ext* const vals;
+    std::vector<const uint32_t*> pw;   // per slot: the proof's words (an absent slot repeats child 0)
+    const uint32_t* const* const* child_pvs;
+    const size_t n_present;
+    const UniformIn* uni;
+    const DeferralIn* def;
     size_t n_prep_airs = 0;
-    std::vector<size_t> prep_slot(K.vk.pg.size(), 0);
-    for (size_t a = 0; a < K.vk.pg.size(); a++)
-        if (K.vk.has_prep[a]) prep_slot[a] = n_prep_airs++;
-    if (uni) {
-        if (!uni->prep_commits || !uni->is_leaf || !uni->leaf_commit || !uni->internal_commit) return ZKHIP_ERR_INVALID;
-        for (size_t i = 0; i < 8 * n_prep_airs * n_present; i++)
-            if (uni->prep_commits[i] >= P) return ZKHIP_ERR_INVALID;
-        for (size_t k = 0; k < 8 * K.n_leaf_shapes; k++)
-            if (uni->leaf_commit[k] >= P) return ZKHIP_ERR_INVALID;
-        for (int k = 0; k < 8; k++)
-            if (uni->internal_commit[k] >= P) return ZKHIP_ERR_INVALID;
-        for (size_t c = 0; c < n_present; c++)
-            if (uni->is_leaf[c] < 0 || (size_t)uni->is_leaf[c] > K.n_leaf_shapes) return ZKHIP_ERR_INVALID;
+    std::vector<size_t> prep_slot;
+
+    // what a slot's inputs beside the proof are read from: an absent slot repeats child 0
+    size_t slot_of(const Src& sr) const {
+        if (sr.child < n_present) return sr.child;
+        return 0;
     }
-    if (def) {
-        if (!def->aux || !def->acc_start) return ZKHIP_ERR_INVALID;
-        for (size_t i = 0; i < K.n_aux * n_present; i++)
-            if (def->aux[i] >= P) return ZKHIP_ERR_INVALID;
-        for (int k = 0; k < 8; k++)
-            if (def->acc_start[k] >= P) return ZKHIP_ERR_INVALID;
-    }
-    const Circuit& c = K.c;
-    std::vector<const uint32_t*> pw(K.max_children);
-    for (size_t ci = 0; ci < K.max_children; ci++) {
-        const size_t src = ci < n_present ? ci : 0;
-        const ChildVk& cvk = K.vk_of(ci);
-        if (!proofs[src] || proof_lens[src] != 4 * cvk.proof_words) {
-            R->error = "child proof " + std::to_string(src) + " has the wrong size for this circuit's child verifying key";
-            return ZKHIP_ERR_INVALID;
-        }
-        pw[ci] = reinterpret_cast<const uint32_t*>(proofs[src]);
-        for (size_t a = 0; a < cvk.pg.size(); a++)
-            if (cvk.n_pvs[a] && (!child_pvs || !child_pvs[src] || !child_pvs[src][a])) return ZKHIP_ERR_INVALID;
-    }
-    for (size_t ci = 0; ci < n_present; ci++) {
-        const ChildVk& cvk = K.vk_of(ci);
-        // the shape words are not part of the transcript: they are fixed by the child verifying key and checked here
-        if (memcmp(pw[ci], cvk.header, 16) != 0) {
-            R->error = "child proof " + std::to_string(ci) + " does not have the shape of this circuit's child verifying key";
-            return ZKHIP_ERR_VERIFY;
-        }
-        for (size_t i = 0; i < cvk.proof_words; i++)
-            if (pw[ci][i] >= P) {
-                R->error = "child proof word not canonical";
-                return ZKHIP_ERR_VERIFY;
+
+    Ext input_value(const Src& sr) const {
+        Ext v = ext_zero();
+        switch (sr.kind) {
+            case S_PROOF_BASE: v.c[0] = to_monty(pw[sr.child][sr.a]); break;
+            case S_PROOF_EXT:
+                for (int k = 0; k < 4; k++) v.c[k] = to_monty(pw[sr.child][sr.a + k]);
+                break;
+            case S_PROOF_PACK: {
+                const std::array<uint32_t, 4>& o = c.packs[sr.a];
+                for (int k = 0; k < 4; k++) v.c[k] = o[k] == ~0u ? 0u : to_monty(pw[sr.child][o[k]]);
+                break;
             }
-        for (size_t a = 0; a < cvk.pg.size(); a++)
-            for (size_t i = 0; i < cvk.n_pvs[a]; i++)
-                if (child_pvs[ci][a][i] >= P) return ZKHIP_ERR_INVALID;
-    }
-    WireBuf& vals = R->vals;
-    if (vals.size() != (size_t)c.n_wires + 1) {   // (every wire has exactly one defining row: nothing stale survives a run)
-        try {
-            vals.reset((size_t)c.n_wires + 1);
-        } catch (const std::bad_alloc&) {
-            R->error = "no memory for the wire values";
-            return ZKHIP_ERR_INVALID;
+            case S_PV: v.c[0] = to_monty(child_pvs[slot_of(sr)][sr.a][sr.b]); break;
+            case S_FLAG: v.c[0] = sr.child < n_present ? MONTY_ONE : 0; break;
+            case S_PREP: v.c[0] = to_monty(uni->prep_commits[(slot_of(sr) * n_prep_airs + prep_slot[sr.a]) * 8 + sr.b]); break;
+            case S_KIND: {   // a = 0: is the child a leaf proof; a = j + 1: is it a proof of leaf circuit j
+                const int kind = uni->is_leaf[slot_of(sr)];
+                v.c[0] = (sr.a == 0 ? kind != 0 : kind == (int)sr.a) ? MONTY_ONE : 0;
+                break;
+            }
+            case S_COMMIT: v.c[0] = to_monty((sr.a == 2 ? def->acc_start : sr.a ? uni->internal_commit : uni->leaf_commit)[sr.b]); break;
+            case S_AUX: v.c[0] = to_monty(def->aux[slot_of(sr) * K.n_aux + sr.a]); break;
+            case S_HINT_BIT: v.c[0] = ((from_monty(vals[sr.a].c[0]) >> sr.b) & 1) ? MONTY_ONE : 0; break;
+            case S_HINT_COORD: v.c[0] = vals[sr.a].c[sr.b]; break;
+            default: break;
         }
+        return v;
     }
-    auto lin_value = [&](const Gate& G) {
+    Ext lin_value(const Gate& G) const {
         Ext r = G.qK;
         const Ext &a = vals[G.w[0]], &bq = vals[G.w[1]], &d = vals[G.w[3]];
         if (G.qM) r = ext_add(r, ext_mul_base(ext_mul(a, bq), G.qM));
@@ -2015,10 +2077,9 @@ int recursion_witness(zkhip_recursion* R, const uint8_t* const* proofs, const si
         if (G.qB) r = ext_add(r, ext_mul_base(bq, G.qB));
         if (G.qD) r = ext_add(r, ext_mul_base(d, G.qD));
         return r;
-    };
-    auto is_const_row = [](const Gate& G) { return G.kind == K_LIN && !G.role[0] && !G.role[1] && !G.role[3]; };
+    }
     // evaluates order[lo, hi); returns the first failing gate or -1
-    auto run = [&](size_t lo, size_t hi, bool skip_const) -> long {
+    long run(size_t lo, size_t hi) const {
         long first_bad = -1;
         for (size_t oi = lo; oi < hi; oi++) {
             const Op& op = c.order[oi];
@@ -2034,39 +2095,11 @@ int recursion_witness(zkhip_recursion* R, const uint8_t* const* proofs, const si
             const Gate& G = c.gates[op.idx];
             switch (G.kind) {
                 case K_INPUT:
-                    for (int s = 0; s < 4; s++) {
-                        if (G.role[s] != 2) continue;
-                        const Src& sr = G.src[s];
-                        Ext v = ext_zero();
-                        switch (sr.kind) {
-                            case S_PROOF_BASE: v.c[0] = to_monty(pw[sr.child][sr.a]); break;
-                            case S_PROOF_EXT:
-                                for (int k = 0; k < 4; k++) v.c[k] = to_monty(pw[sr.child][sr.a + k]);
-                                break;
-                            case S_PROOF_PACK: {
-                                const std::array<uint32_t, 4>& o = c.packs[sr.a];
-                                for (int k = 0; k < 4; k++) v.c[k] = o[k] == ~0u ? 0u : to_monty(pw[sr.child][o[k]]);
-                                break;
-                            }
-                            case S_PV: v.c[0] = to_monty(child_pvs[sr.child < n_present ? sr.child : 0][sr.a][sr.b]); break;
-                            case S_FLAG: v.c[0] = sr.child < n_present ? MONTY_ONE : 0; break;
-                            case S_PREP: v.c[0] = to_monty(uni->prep_commits[((sr.child < n_present ? sr.child : 0) * n_prep_airs + prep_slot[sr.a]) * 8 + sr.b]); break;
-                            case S_KIND: {   // a = 0: is the child a leaf proof; a = j + 1: is it a proof of leaf circuit j
-                                const int kind = uni->is_leaf[sr.child < n_present ? sr.child : 0];
-                                v.c[0] = (sr.a == 0 ? kind != 0 : kind == (int)sr.a) ? MONTY_ONE : 0;
-                                break;
-                            }
-                            case S_COMMIT: v.c[0] = to_monty((sr.a == 2 ? def->acc_start : sr.a ? uni->internal_commit : uni->leaf_commit)[sr.b]); break;
-                            case S_AUX: v.c[0] = to_monty(def->aux[(sr.child < n_present ? sr.child : 0) * K.n_aux + sr.a]); break;
-                            case S_HINT_BIT: v.c[0] = ((from_monty(vals[sr.a].c[0]) >> sr.b) & 1) ? MONTY_ONE : 0; break;
-                            case S_HINT_COORD: v.c[0] = vals[sr.a].c[sr.b]; break;
-                            default: break;
-                        }
-                        vals[G.w[s]] = v;
-                    }
+                    for (int s = 0; s < 4; s++)
+                        if (G.role[s] == 2) vals[G.w[s]] = input_value(G.src[s]);
                     break;
                 case K_LIN:
-                    if (skip_const && is_const_row(G)) break;
+                    if (is_const_row(G)) break;
                     vals[G.w[2]] = lin_value(G);
                     break;
                 case K_HSTEP: {
@@ -2107,12 +2140,12 @@ int recursion_witness(zkhip_recursion* R, const uint8_t* const* proofs, const si
             }
         }
         return first_bad;
-    };
+    }
     // SIXTEEN query parts side by side: each part is advanced to its next permutation (gates are evaluated on the way), the sixteen
     // pending states are permuted in ONE call -- a state word of all sixteen per 512-bit register (poseidon2_permute16_host) -- and
     // scattered back.  The parts are independent (query_parallel) and built by the same code, so they stay in step; one that ends
     // early rides along with a zero state.  Most of a node's ~170 k permutations are in the query parts.
-    auto run16 = [&](const size_t (*ranges)[2], size_t n_parts, long* bad_out) {
+    void run16(const size_t (*ranges)[2], size_t n_parts, long* bad_out) const {
         size_t pos[16];
         for (size_t k = 0; k < 16; k++) pos[k] = k < n_parts ? ranges[k][0] : 0;
         alignas(64) uint32_t t[256];
@@ -2127,7 +2160,7 @@ int recursion_witness(zkhip_recursion* R, const uint8_t* const* proofs, const si
                 const size_t hi = ranges[k][1];
                 while (q < hi && !c.order[q].is_perm) q++;
                 if (q > pos[k]) {
-                    const long b = run(pos[k], q, true);
+                    const long b = run(pos[k], q);
                     if (b >= 0 && (bad_out[k] < 0 || b < bad_out[k])) bad_out[k] = b;
                 }
                 pos[k] = q;
@@ -2144,85 +2177,150 @@ int recursion_witness(zkhip_recursion* R, const uint8_t* const* proofs, const si
                 pos[k]++;
             }
         }
-    };
-    // constant rows first (a constant's row sits in whichever section used it first), then one thread per child section,
-    // then the statement logic behind them
-    for (const Gate& G : c.gates)
-        if (is_const_row(G)) vals[G.w[2]] = G.qK;
-    long first_bad = -1;
-    {
-        const size_t n_sec = c.sections.size() - 1;
-        std::vector<long> bad(n_sec, -1);
-        auto keep_first = [](long& acc, long b) {
-            if (b >= 0 && (acc < 0 || b < acc)) acc = b;
-        };
-        // (a thread the system refuses -- a process at its thread limit -- is not fatal: the caller does that share itself)
-        auto spawn = [](std::vector<std::thread>& th, auto&& fn) {
-            try {
-                th.emplace_back(fn);
-                return true;
-            } catch (const std::system_error&) {
-                return false;
-            }
-        };
-        if (!c.query_parallel) {
-            std::vector<std::thread> th;
-            for (size_t i = 1; i < n_sec; i++) {
-                auto part = [&, i]() { bad[i] = run(c.sections[i], c.sections[i + 1], true); };
-                if (!spawn(th, part)) part();
-            }
-            bad[0] = run(c.sections[0], c.sections[1], true);
-            for (auto& t : th) t.join();
-        } else {
-            // the children's parts before their queries side by side, then every (child, query) part from a shared counter, then what
-            // follows the queries
-            auto each_child = [&](auto&& f) {
-                std::vector<std::thread> th;
-                for (size_t i = 1; i < n_sec; i++) {
-                    auto part = [&, i]() { f(i); };
-                    if (!spawn(th, part)) part();
-                }
-                f(0);
-                for (auto& t : th) t.join();
-            };
-            each_child([&](size_t i) { keep_first(bad[i], run(c.sections[i], c.sub[i].front(), true)); });
-            std::vector<std::pair<size_t, size_t>> tasks;
-            for (size_t i = 0; i < n_sec; i++)
-                for (size_t q = 0; q + 1 < c.sub[i].size(); q++) tasks.push_back({i, q});
-            // (all cores the process may use -- zkhip_host_cpus: the cgroup's quota, not the 256 host threads a container sees;
-            // measured in the one-flow pipeline with 4 / 8 / 16 threads on 16 cores -- the segment phase loses ~40 ms to the
-            // contention, the tree's tail gains ~100 ms; ZKHIP_WITNESS_THREADS overrides)
-            const unsigned cap = process_config().witness_threads ? process_config().witness_threads : zkhip_host_cpus();
-            const size_t n_threads = std::min<size_t>((tasks.size() + 15) / 16, std::max(1u, cap));
-            std::atomic<size_t> next{0};
-            std::vector<std::vector<long>> tb(n_threads, std::vector<long>(n_sec, -1));
-            std::vector<std::thread> th;
-            auto worker = [&](size_t t) {
-                // bundles of sixteen query parts from the shared counter, advanced side by side
-                for (size_t k0; (k0 = next.fetch_add(16)) < tasks.size();) {
-                    const size_t n = std::min<size_t>(16, tasks.size() - k0);
-                    size_t ranges[16][2];
-                    long bad16[16];
-                    for (size_t k = 0; k < n; k++) ranges[k][0] = c.sub[tasks[k0 + k].first][tasks[k0 + k].second], ranges[k][1] = c.sub[tasks[k0 + k].first][tasks[k0 + k].second + 1], bad16[k] = -1;
-                    run16(ranges, n, bad16);
-                    for (size_t k = 0; k < n; k++) keep_first(tb[t][tasks[k0 + k].first], bad16[k]);
-                }
-            };
-            for (size_t t = 1; t < n_threads; t++)
-                if (!spawn(th, [&, t]() { worker(t); })) break;
-            if (n_threads) worker(0);   // this thread takes tasks from the same counter
-            for (auto& t : th) t.join();
-            for (size_t t = 0; t < n_threads; t++)
-                for (size_t i = 0; i < n_sec; i++) keep_first(bad[i], tb[t][i]);
-            each_child([&](size_t i) { keep_first(bad[i], run(c.sub[i].back(), c.sections[i + 1], true)); });
-        }
-        for (long b : bad)
-            if (b >= 0 && (first_bad < 0 || b < first_bad)) first_bad = b;
-        const long tail = run(c.sections[n_sec], c.order.size(), true);
-        if (first_bad < 0) first_bad = tail;
     }
+};
+
+// Validates what the caller handed in and fills the run's proof pointers and preprocessed-commitment slots.
+int check_witness_args(zkhip_recursion* R, const uint8_t* const* proofs, const size_t* proof_lens, const uint32_t* const* const* child_pvs,
+                       size_t n_present, const UniformIn* uni, const DeferralIn* def, std::vector<const uint32_t*>& pw, size_t& n_prep_airs,
+                       std::vector<size_t>& prep_slot) {
+    if (!R || !proofs || !proof_lens || n_present == 0 || n_present > R->k->max_children) return ZKHIP_ERR_INVALID;
+    const RecCore& K = *R->k;
+    if ((K.mode == 2) != (uni != nullptr) || (K.mode == 3) != (def != nullptr)) {
+        R->error = K.mode == 2   ? "a uniform node circuit takes its children's commitments and kinds (zkhip_recursion_witness_uniform)"
+                   : K.mode == 3 ? "a deferral node circuit takes the openings of its children's public values (zkhip_recursion_witness_deferral)"
+                                 : "this circuit is built for one child verifying key (zkhip_recursion_witness)";
+        return ZKHIP_ERR_INVALID;
+    }
+    if (K.mode == 4 && n_present != 2) {
+        R->error = "a join takes the root proof and the deferral node's proof";
+        return ZKHIP_ERR_INVALID;
+    }
+    n_prep_airs = 0;
+    prep_slot.assign(K.vk.pg.size(), 0);
+    for (size_t a = 0; a < K.vk.pg.size(); a++)
+        if (K.vk.has_prep[a]) prep_slot[a] = n_prep_airs++;
+    if (uni) {
+        if (!uni->prep_commits || !uni->is_leaf || !uni->leaf_commit || !uni->internal_commit) return ZKHIP_ERR_INVALID;
+        for (size_t i = 0; i < 8 * n_prep_airs * n_present; i++)
+            if (uni->prep_commits[i] >= P) return ZKHIP_ERR_INVALID;
+        for (size_t k = 0; k < 8 * K.n_leaf_shapes; k++)
+            if (uni->leaf_commit[k] >= P) return ZKHIP_ERR_INVALID;
+        for (int k = 0; k < 8; k++)
+            if (uni->internal_commit[k] >= P) return ZKHIP_ERR_INVALID;
+        for (size_t c = 0; c < n_present; c++)
+            if (uni->is_leaf[c] < 0 || (size_t)uni->is_leaf[c] > K.n_leaf_shapes) return ZKHIP_ERR_INVALID;
+    }
+    if (def) {
+        if (!def->aux || !def->acc_start) return ZKHIP_ERR_INVALID;
+        for (size_t i = 0; i < K.n_aux * n_present; i++)
+            if (def->aux[i] >= P) return ZKHIP_ERR_INVALID;
+        for (int k = 0; k < 8; k++)
+            if (def->acc_start[k] >= P) return ZKHIP_ERR_INVALID;
+    }
+    pw.assign(K.max_children, nullptr);
+    for (size_t ci = 0; ci < K.max_children; ci++) {
+        const size_t src = ci < n_present ? ci : 0;
+        const ChildVk& cvk = K.vk_of(ci);
+        if (!proofs[src] || proof_lens[src] != 4 * cvk.proof_words) {
+            R->error = "child proof " + std::to_string(src) + " has the wrong size for this circuit's child verifying key";
+            return ZKHIP_ERR_INVALID;
+        }
+        pw[ci] = reinterpret_cast<const uint32_t*>(proofs[src]);
+        for (size_t a = 0; a < cvk.pg.size(); a++)
+            if (cvk.n_pvs[a] && (!child_pvs || !child_pvs[src] || !child_pvs[src][a])) return ZKHIP_ERR_INVALID;
+    }
+    for (size_t ci = 0; ci < n_present; ci++) {
+        const ChildVk& cvk = K.vk_of(ci);
+        // the shape words are not part of the transcript: they are fixed by the child verifying key and checked here
+        if (memcmp(pw[ci], cvk.header, 16) != 0) {
+            R->error = "child proof " + std::to_string(ci) + " does not have the shape of this circuit's child verifying key";
+            return ZKHIP_ERR_VERIFY;
+        }
+        for (size_t i = 0; i < cvk.proof_words; i++)
+            if (pw[ci][i] >= P) {
+                R->error = "child proof word not canonical";
+                return ZKHIP_ERR_VERIFY;
+            }
+        for (size_t a = 0; a < cvk.pg.size(); a++)
+            for (size_t i = 0; i < cvk.n_pvs[a]; i++)
+                if (child_pvs[ci][a][i] >= P) return ZKHIP_ERR_INVALID;
+    }
+    return ZKHIP_OK;
+}
+
+void keep_first(long& acc, long b) {   // the first failing gate is the one of lowest index
+    if (b >= 0 && (acc < 0 || b < acc)) acc = b;
+}
+// (a thread the system refuses -- a process at its thread limit -- is not fatal: the caller does that share itself)
+template <class F>
+bool spawn(std::vector<std::thread>& th, F&& fn) {
+    try {
+        th.emplace_back(fn);
+        return true;
+    } catch (const std::system_error&) {
+        return false;
+    }
+}
+// f(i) for every child section i: one thread per section beyond the first, which this thread takes
+template <class F>
+void each_child(size_t n_sec, F&& f) {
+    std::vector<std::thread> th;
+    for (size_t i = 1; i < n_sec; i++) {
+        auto part = [&, i]() { f(i); };
+        if (!spawn(th, part)) part();
+    }
+    f(0);
+    for (auto& t : th) t.join();
+}
+
+// one thread per child section; bad[i] = the section's first failing gate
+void run_sections_serial(const WitnessRun& w, std::vector<long>& bad) {
+    const Circuit& c = w.c;
+    each_child(bad.size(), [&](size_t i) { bad[i] = w.run(c.sections[i], c.sections[i + 1]); });
+}
+
+// the children's parts before their queries side by side, then every (child, query) part from a shared counter, then what
+// follows the queries
+void run_sections_query_parallel(const WitnessRun& w, std::vector<long>& bad) {
+    const Circuit& c = w.c;
+    const size_t n_sec = bad.size();
+    each_child(n_sec, [&](size_t i) { keep_first(bad[i], w.run(c.sections[i], c.sub[i].front())); });
+    std::vector<std::pair<size_t, size_t>> tasks;
+    for (size_t i = 0; i < n_sec; i++)
+        for (size_t q = 0; q + 1 < c.sub[i].size(); q++) tasks.push_back({i, q});
+    // (all cores the process may use -- zkhip_host_cpus: the cgroup's quota, not the 256 host threads a container sees;
+    // measured in the one-flow pipeline with 4 / 8 / 16 threads on 16 cores -- the segment phase loses ~40 ms to the
+    // contention, the tree's tail gains ~100 ms; ZKHIP_WITNESS_THREADS overrides)
+    const unsigned cap = process_config().witness_threads ? process_config().witness_threads : zkhip_host_cpus();
+    const size_t n_threads = std::min<size_t>((tasks.size() + 15) / 16, std::max(1u, cap));
+    std::atomic<size_t> next{0};
+    std::vector<std::vector<long>> tb(n_threads, std::vector<long>(n_sec, -1));
+    std::vector<std::thread> th;
+    auto worker = [&](size_t t) {
+        // bundles of sixteen query parts from the shared counter, advanced side by side
+        for (size_t k0; (k0 = next.fetch_add(16)) < tasks.size();) {
+            const size_t n = std::min<size_t>(16, tasks.size() - k0);
+            size_t ranges[16][2];
+            long bad16[16];
+            for (size_t k = 0; k < n; k++) ranges[k][0] = c.sub[tasks[k0 + k].first][tasks[k0 + k].second], ranges[k][1] = c.sub[tasks[k0 + k].first][tasks[k0 + k].second + 1], bad16[k] = -1;
+            w.run16(ranges, n, bad16);
+            for (size_t k = 0; k < n; k++) keep_first(tb[t][tasks[k0 + k].first], bad16[k]);
+        }
+    };
+    for (size_t t = 1; t < n_threads; t++)
+        if (!spawn(th, [&, t]() { worker(t); })) break;
+    if (n_threads) worker(0);   // this thread takes tasks from the same counter
+    for (auto& t : th) t.join();
+    for (size_t t = 0; t < n_threads; t++)
+        for (size_t i = 0; i < n_sec; i++) keep_first(bad[i], tb[t][i]);
+    each_child(n_sec, [&](size_t i) { keep_first(bad[i], w.run(c.sub[i].back(), c.sections[i + 1])); });
+}
+
+// reads out the node's public values and reports the first failing gate
+int finish_witness(zkhip_recursion* R, const Circuit& c, long first_bad, uint32_t* node_pvs_out) {
     R->node_pvs.assign(c.n_pvs, 0);
-    for (size_t i = 0; i < c.n_pvs; i++) R->node_pvs[i] = from_monty(vals[c.pv_wires[i / 4]].c[i % 4]);
+    for (size_t i = 0; i < c.n_pvs; i++) R->node_pvs[i] = from_monty(R->vals[c.pv_wires[i / 4]].c[i % 4]);
     if (node_pvs_out) memcpy(node_pvs_out, R->node_pvs.data(), 4 * c.n_pvs);
     if (first_bad >= 0) {
         R->error = "the circuit is not satisfied: gate " + std::to_string(first_bad) + " fails (a child proof does not verify)";
@@ -2231,6 +2329,41 @@ int recursion_witness(zkhip_recursion* R, const uint8_t* const* proofs, const si
     R->error.clear();
     return ZKHIP_OK;
 }
+
+int recursion_witness(zkhip_recursion* R, const uint8_t* const* proofs, const size_t* proof_lens, const uint32_t* const* const* child_pvs,
+                      size_t n_present, uint32_t* node_pvs_out, const UniformIn* uni, const DeferralIn* def = nullptr) {
+    std::vector<const uint32_t*> pw;
+    std::vector<size_t> prep_slot;
+    size_t n_prep_airs = 0;
+    const int rc = check_witness_args(R, proofs, proof_lens, child_pvs, n_present, uni, def, pw, n_prep_airs, prep_slot);
+    if (rc != ZKHIP_OK) return rc;
+    const RecCore& K = *R->k;
+    const Circuit& c = K.c;
+    WireBuf& vals = R->vals;
+    if (vals.size() != (size_t)c.n_wires + 1) {   // (every wire has exactly one defining row: nothing stale survives a run)
+        try {
+            vals.reset((size_t)c.n_wires + 1);
+        } catch (const std::bad_alloc&) {
+            R->error = "no memory for the wire values";
+            return ZKHIP_ERR_INVALID;
+        }
+    }
+    const WitnessRun w{K, c, vals.p, std::move(pw), child_pvs, n_present, uni, def, n_prep_airs, std::move(prep_slot)};
+    // constant rows first (a constant's row sits in whichever section used it first), then the child sections side by side,
+    // then the statement logic behind them
+    for (const Gate& G : c.gates)
+        if (is_const_row(G)) vals[G.w[2]] = G.qK;
+    const size_t n_sec = c.sections.size() - 1;
+    std::vector<long> bad(n_sec, -1);
+    if (c.query_parallel) run_sections_query_parallel(w, bad);
+    else run_sections_serial(w, bad);
+    long first_bad = -1;
+    for (long b : bad) keep_first(first_bad, b);
+    const long tail = w.run(c.sections[n_sec], c.order.size());
+    if (first_bad < 0) first_bad = tail;
+    return finish_witness(R, c, first_bad, node_pvs_out);
+}
+
 }  // namespace
 
 extern "C" {
