@@ -382,6 +382,30 @@ int zkhip_fri_query_tracegen(zkhip_ctx *ctx, const uint32_t *d_n_layers, const u
                              const uint32_t *d_has_ro, const uint32_t *d_ro, size_t n_calls, size_t n_rows, unsigned log_height,
                              uint32_t *d_trace, uint32_t *d_hash_inputs, uint32_t *d_leaf_digest, uint32_t *d_final);
 
+/* FRI final-polynomial chip (a piece of the recursion circuit, air.py fri_final_air; docs/fri_final.md): a query's last check of one FRI
+ * proof -- the lines behind the fold loop of the host verifier (csrc/verifier.hip): the value the loop ends in must be the proof's final
+ * polynomial at the query's point.  With L = 2^log_final_poly_len coefficients, lvl the log2 of the last domain's size (log_blowup +
+ * log_final_poly_len in a proof) and k the index the loop ends on (index >> n_layers), the point is x = g_lvl^bitrev(k, lvl) and the
+ * value is Horner over the coefficients from the highest down.
+ *   zkhip_fri_final_host      the definition, no device, canonical words: coef[4 j ..] is coefficient j (ascending); writes the point
+ *                             into x_out[0] and the value into value_out[4].  ZKHIP_ERR_INVALID for a NULL pointer, log_final_poly_len >
+ *                             ZKHIP_MAX_LOG_FINAL_POLY, lvl = 0 or > 26, k >= 2^lvl or a word >= p; nothing is written then.
+ *   zkhip_fri_final_tracegen  the chip's trace for n_calls calls of L rows each.  Records are canonical words: per call c d_k[c], d_lvl[c]
+ *                             and d_poly[c], the polynomial of d_coef ([n_polys][L][4], ascending) the call evaluates.  Fills d_trace
+ *                             (ZKHIP_FRI_FINAL_WIDTH = 19 columns, stride 2^log_height, Montgomery: coef[4] | acc[4] | x | x_inv | xi2 |
+ *                             k | lvl | j | poly | is_first | is_last | is_real | call with call = c; row t of a call holds coefficient
+ *                             j = L - 1 - t; rows behind the last call zero) and, unless it is NULL, d_value ([n_calls][4] CANONICAL:
+ *                             the polynomial at the call's point).  ZKHIP_ERR_INVALID for lvl = 0 or > 26, k >= 2^lvl, poly >= n_polys
+ *                             or a coefficient word >= p (checked on the device like every generator's records:
+ *                             zkhip_tracegen_defer_checks; a refused call's rows are zeros), and at once for a NULL pointer, log_height
+ *                             > 27, log_final_poly_len > ZKHIP_MAX_LOG_FINAL_POLY or n_calls L > 2^log_height. */
+#define ZKHIP_FRI_FINAL_WIDTH 19
+int zkhip_fri_final_host(unsigned log_final_poly_len, unsigned lvl, uint64_t k, const uint32_t *coef, uint32_t x_out[1],
+                         uint32_t value_out[4]);
+int zkhip_fri_final_tracegen(zkhip_ctx *ctx, unsigned log_final_poly_len, const uint32_t *d_k, const uint32_t *d_lvl, const uint32_t *d_poly,
+                             const uint32_t *d_coef, size_t n_polys, size_t n_calls, unsigned log_height, uint32_t *d_trace,
+                             uint32_t *d_value);
+
 /* System chips: the PROGRAM chip and the execution frames that look instructions up in it.  OpenVM's ProgramAir keeps the program
  * (ZKHIP_PROGRAM_FIELDS = 9 fields per instruction: pc, opcode, operands a..g) as a CACHED main partition and one common column,
  * the execution frequency of each instruction; it receives every instruction that often on the program bus (the first AIR of the

@@ -1572,6 +1572,102 @@ inline void fri_query_air(AirBuilder& b, uint32_t point_bus, uint32_t hash_bus, 
     }
 }
 
+// air.fri_final_air(log_final_poly_len, point_bus, final_bus, coeff_bus): AirBuilder(19, 0) -- a query's last check: L = 2^log_final_poly_len
+// rows walking Horner over the final polynomial's coefficients from the highest down at x = x_inv^-2, the point of index k in the domain of
+// 2^lvl points; the is_last row receives (call, lvl, k, acc) on final_bus, what fri_query_air sends there (docs/fri_final.md)
+inline void fri_final_air(AirBuilder& b, unsigned log_final_poly_len, uint32_t point_bus, uint32_t final_bus, int coeff_bus = -1) {
+    const int64_t L = (int64_t)1 << log_final_poly_len;
+    Expr coef[4], acc[4], n_coef[4], n_acc[4];
+    for (int i = 0; i < 4; i++) coef[i] = b.var(i);
+    for (int i = 0; i < 4; i++) acc[i] = b.var(4 + i);
+    const Expr x = b.var(8), xinv = b.var(9), xi2 = b.var(10), k = b.var(11), lvl = b.var(12), j = b.var(13), poly = b.var(14), first = b.var(15), last = b.var(16),
+               real = b.var(17), call = b.var(18);
+    for (int i = 0; i < 4; i++) n_coef[i] = b.next(i);
+    for (int i = 0; i < 4; i++) n_acc[i] = b.next(4 + i);
+    const Expr n_x = b.next(8), n_xinv = b.next(9), n_k = b.next(11), n_lvl = b.next(12), n_j = b.next(13), n_poly = b.next(14), n_first = b.next(15), n_real = b.next(17),
+               n_call = b.next(18);
+    for (const Expr& f : {first, last, real}) {
+        const Expr t = f - 1;
+        b.assert_zero(f * t);
+    }
+    const Expr pad = 1 - real;
+    b.assert_zero(first * pad);
+    b.assert_zero(last * pad);
+    {
+        const Expr df = first - real;
+        b.when_first_row(df);
+    }
+    const Expr s = real - last;
+    b.when_last_row(s);
+    auto step_to = [&](const Expr& e) {   // when_transition(s * e)
+        const Expr g = s * e;
+        b.when_transition(g);
+    };
+    {
+        const Expr t = n_real - 1;
+        step_to(t);
+    }
+    step_to(n_first);
+    {
+        const Expr t = n_real - n_first;
+        const Expr g = last * t;
+        b.when_transition(g);
+    }
+    {
+        const Expr g = pad * n_real;
+        b.when_transition(g);
+    }
+    const Expr same[6][2] = {{call, n_call}, {poly, n_poly}, {k, n_k}, {lvl, n_lvl}, {x, n_x}, {xinv, n_xinv}};
+    for (const auto& v : same) {
+        const Expr t = v[1] - v[0];
+        step_to(t);
+    }
+    {
+        const Expr t = n_j - j;
+        const Expr u = t + 1;
+        step_to(u);
+    }
+    {
+        const Expr t = j - (L - 1);
+        b.assert_zero(first * t);
+    }
+    b.assert_zero(last * j);
+    for (int i = 0; i < 4; i++) {
+        const Expr t = acc[i] - coef[i];
+        b.assert_zero(first * t);
+    }
+    for (int i = 0; i < 4; i++) {
+        const Expr m = acc[i] * x;
+        const Expr t = n_acc[i] - m;
+        const Expr u = t - n_coef[i];
+        step_to(u);
+    }
+    {
+        const Expr m = xinv * xinv;
+        b.assert_zero(xi2 - m);
+    }
+    {
+        const Expr m = x * xi2;
+        b.assert_zero(m - real);
+    }
+    b.push_interaction(point_bus, {k, xinv}, first, Kind::Send);
+    {
+        std::vector<Expr> msg;
+        msg.push_back(call);
+        msg.push_back(lvl);
+        msg.push_back(k);
+        for (int i = 0; i < 4; i++) msg.push_back(acc[i]);
+        b.push_interaction(final_bus, msg, last, Kind::Receive);
+    }
+    if (coeff_bus >= 0) {
+        std::vector<Expr> msg;
+        msg.push_back(poly);
+        msg.push_back(j);
+        for (int i = 0; i < 4; i++) msg.push_back(coef[i]);
+        b.push_interaction((uint32_t)coeff_bus, msg, real, Kind::Send);
+    }
+}
+
 // air.mmcs_claims_air(claims_bus): AirBuilder(19, 0)
 inline void mmcs_claims_air(AirBuilder& b, uint32_t claims_bus) {
     std::vector<Expr> msg;

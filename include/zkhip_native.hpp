@@ -15,7 +15,9 @@
 // mmcs_rows_air + mmcs_path_air + the two Poseidon2 chips: opened words -> row digests -> path -> root; zkhip_mmcs_rows_tracegen,
 // docs/mmcs_rows.md).  The fold loop of a FRI query behind the reduced openings is built the same way (air.py fri_query_air with
 // fri_fold_air's line, domain_point_air, mmcs_path_air and the Poseidon2 chips; zkhip_fri_query_tracegen, docs/fri_query.md): a core on
-// cells, wired into no circuit yet.  The native address space and its instruction set are not.  The
+// cells, wired into no circuit yet; the query's last check, the comparison with the final polynomial at the query's point, is the chip
+// behind its final bus (air.py fri_final_air, zkhip_fri_final_tracegen, docs/fri_final.md).  The division by (zeta - x) in front of the
+// reduced openings and the origin of the betas and roots stay unstated.  The native address space and its instruction set are not built.  The
 // three arithmetic chips sit behind CUSTOM ecalls (9 / 10 / 11) on the RV32 memory, not behind OpenVM's native opcodes: a guest that uses
 // openvm `verify_stark` (a native-address-space recursion program) cannot run on this executor.  `[app_vm_config.native]` is therefore
 // COVERED IN PART: its field arithmetic, not its instruction set (docs/gaps.md).

@@ -50,6 +50,7 @@ pub const ZKHIP_REDUCED_OPENING_WIDTH: usize = 18;
 pub const ZKHIP_REDUCED_OPENING_BLOCK_ROWS: usize = 256;
 pub const ZKHIP_MMCS_ROWS_WIDTH: usize = 56;
 pub const ZKHIP_FRI_QUERY_WIDTH: usize = 61;
+pub const ZKHIP_FRI_FINAL_WIDTH: usize = 19;
 pub const ZKHIP_CASTF_WIDTH: usize = 6;
 pub const ZKHIP_FIELD_ARITH_WIDTH: usize = 8;
 pub const ZKHIP_FIELD_EXT_WIDTH: usize = 20;
@@ -317,6 +318,9 @@ extern "C" {
                                     d_beta: *const u32, d_root: *const u32, d_sibling: *const u32, d_has_ro: *const u32, d_ro: *const u32,
                                     n_calls: usize, n_rows: usize, log_height: c_uint, d_trace: *mut u32, d_hash_inputs: *mut u32,
                                     d_leaf_digest: *mut u32, d_final: *mut u32) -> c_int;
+    pub fn zkhip_fri_final_tracegen(ctx: *mut zkhip_ctx, log_final_poly_len: c_uint, d_k: *const u32, d_lvl: *const u32, d_poly: *const u32,
+                                    d_coef: *const u32, n_polys: usize, n_calls: usize, log_height: c_uint, d_trace: *mut u32,
+                                    d_value: *mut u32) -> c_int;
     pub fn zkhip_castf_tracegen(ctx: *mut zkhip_ctx, d_x: *const u32, n: usize, log_height: c_uint, d_trace: *mut u32, d_var_range_counts: *mut u32,
                                 max_bits: c_uint) -> c_int;
     pub fn zkhip_field_arith_tracegen(ctx: *mut zkhip_ctx, d_opcode: *const u32, d_b: *const u32, d_c: *const u32, n: usize, log_height: c_uint,
@@ -410,6 +414,7 @@ extern "C" {
     pub fn zkhip_hash_slice_host(input: *const u32, len: usize, out: *mut u32) -> c_int;
     pub fn zkhip_fri_query_host(index: u64, log_max: c_uint, n_layers: c_uint, beta: *const u32, sibling: *const u32, has_ro: *const u32, ro: *const u32,
                                 ro_top: *const u32, e0: *mut u32, e1: *mut u32, eval: *mut u32) -> c_int;
+    pub fn zkhip_fri_final_host(log_final_poly_len: c_uint, lvl: c_uint, k: u64, coef: *const u32, x_out: *mut u32, value_out: *mut u32) -> c_int;
     pub fn zkhip_fri_fold_row(index: u64, log_height: c_uint, beta: *const u32, e0: *const u32, e1: *const u32, out: *mut u32) -> c_int;
     pub fn zkhip_reduced_opening_host(alpha: *const u32, a: *const u32, b: *const u32, len: usize, out: *mut u32) -> c_int;
     pub fn zkhip_logup_exposed_check(exposed: *const u32, n: usize) -> c_int;

@@ -149,6 +149,7 @@ def load_library():
         "zkhip_reduced_opening_tracegen": (C.c_int, [vp, vp, vp, vp, vp, sz, sz, C.c_uint, vp]),
         "zkhip_mmcs_rows_tracegen": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, sz, C.c_uint, vp, vp, vp]),
         "zkhip_fri_query_tracegen": (C.c_int, [vp] * 10 + [sz, sz, C.c_uint, vp, vp, vp, vp]),
+        "zkhip_fri_final_tracegen": (C.c_int, [vp, C.c_uint, vp, vp, vp, vp, sz, sz, C.c_uint, vp, vp]),
         "zkhip_castf_tracegen": (C.c_int, [vp, vp, sz, C.c_uint, vp, vp, C.c_uint]),
         "zkhip_field_arith_tracegen": (C.c_int, [vp, vp, vp, vp, sz, C.c_uint, vp]),
         "zkhip_field_ext_tracegen": (C.c_int, [vp, vp, vp, vp, sz, C.c_uint, vp]),
@@ -199,6 +200,7 @@ def load_library():
         "zkhip_reduced_opening_host": (C.c_int, [u32p, u32p, u32p, sz, u32p]),
         "zkhip_hash_slice_host": (C.c_int, [u32p, sz, u32p]),
         "zkhip_fri_query_host": (C.c_int, [C.c_uint64, C.c_uint, C.c_uint] + [u32p] * 8),
+        "zkhip_fri_final_host": (C.c_int, [C.c_uint, C.c_uint, C.c_uint64, u32p, u32p, u32p]),
         "zkhip_logup_exposed_check": (C.c_int, [u32p, sz]),
         "zkhip_proof_decode_v1": (C.c_int, [C.POINTER(C.c_uint8), sz, C.c_int, C.POINTER(_V1Summary)]),
         "zkhip_proof_reencode_v1": (C.c_int, [C.POINTER(C.c_uint8), sz, C.c_int, C.POINTER(C.c_uint8), sz, C.POINTER(sz)]),
@@ -702,6 +704,19 @@ class Context:
                                                       C.c_void_p(hin.data_ptr()), C.c_void_p(dg.data_ptr()) if leaf_digests else None,
                                                       C.c_void_p(fin.data_ptr()) if final else None))
         return tr, hin, dg, fin
+
+    def fri_final_tracegen(self, t_k, t_lvl, t_poly, t_coef, log_final_poly_len, log_height, value=True):
+        """(19-column trace of the FRI final-polynomial chip, the calls' values [n_calls][4] CANONICAL or None) from records (int32 tensors,
+        canonical: per call the point's index k, the log2 lvl of the last domain's size and the polynomial it evaluates; coef
+        [n_polys][2^log_final_poly_len][4], ascending).  A call takes 2^log_final_poly_len rows.  value=False passes NULL."""
+        import torch
+
+        n_calls, n_polys = t_k.numel(), t_coef.numel() >> (2 + log_final_poly_len)
+        tr = torch.empty(FRI_FINAL_WIDTH << log_height, dtype=torch.int32, device=self.device)
+        val = torch.empty(4 * n_calls, dtype=torch.int32, device=self.device) if value else None
+        self._check(self.lib.zkhip_fri_final_tracegen(self.h, log_final_poly_len, *[C.c_void_p(t.data_ptr()) for t in (t_k, t_lvl, t_poly, t_coef)], n_polys, n_calls,
+                                                      log_height, C.c_void_p(tr.data_ptr()), C.c_void_p(val.data_ptr()) if value else None))
+        return tr, val
 
     def castf_tracegen(self, t_x, log_height, t_var_range_counts, max_bits):
         """6-column trace of the native CASTF chip from records (int32 tensor of values < 2^30); the limb checks are added to
@@ -2272,6 +2287,22 @@ def fri_query_host(index, log_max, beta, sibling, has_ro, ro, ro_top):
     if rc != 0:
         raise ZkhipError("zkhip_fri_query_host returned %d" % rc)
     return e0, e1, ev
+
+
+FRI_FINAL_WIDTH = 19                # ZKHIP_FRI_FINAL_WIDTH
+
+
+def fri_final_host(log_final_poly_len, lvl, k, coef):
+    """A query's last check on canonical words (coef [2^log_final_poly_len][4], ascending): returns (x, value) -- the point
+    g_lvl^bitrev(k, lvl) of the domain of 2^lvl points and the final polynomial at it, [4] canonical."""
+    cf = np.ascontiguousarray(coef, dtype=np.uint32).reshape(-1)
+    if not 0 <= int(log_final_poly_len) <= 8 or cf.size != 4 << int(log_final_poly_len):
+        raise ZkhipError("fri_final_host: coef has four words for each of the 2^log_final_poly_len <= 256 coefficients")
+    x, val = np.zeros(1, dtype=np.uint32), np.zeros(4, dtype=np.uint32)
+    rc = load_library().zkhip_fri_final_host(int(log_final_poly_len), int(lvl), int(k), _u32p(cf), _u32p(x), _u32p(val))
+    if rc != 0:
+        raise ZkhipError("zkhip_fri_final_host returned %d" % rc)
+    return int(x[0]), val
 
 
 # ---- the reference's stored-proof container (OpenVM-v1 Proof<SC>, bincode): include/zkhip_codec.hpp ----

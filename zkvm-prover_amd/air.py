@@ -1907,6 +1907,59 @@ def fri_query_air(point_bus, hash_bus, claims_bus, ro_bus, layer_bus=None, final
     return b
 
 
+FRI_FINAL_WIDTH = 19
+
+
+def fri_final_air(log_final_poly_len, point_bus, final_bus, coeff_bus=None):
+    """A query's last check of a FRI proof, in-circuit (the lines behind the `for l < n_layers` loop of the host verifier,
+    csrc/verifier.hip; zkhip_fri_final_host is the definition): the value the fold loop ends in must be the proof's final polynomial at
+    the query's point of the last domain.  Columns coef[4] | acc[4] | x | x_inv | xi2 | k | lvl | j | poly | is_first | is_last | is_real |
+    call.  With L = 2^log_final_poly_len a call is one query: L consecutive rows walking Horner from the highest coefficient down, row t
+    holding coefficient j = L - 1 - t; acc = coef on the first row and acc' = acc x + coef' on every later one (x is a base cell), and
+    the acc of the is_last row is the final polynomial at x.  j is L - 1 on an is_first row, falls by one a row and is 0 on the is_last
+    row, so a call has exactly L rows.  x is bound by xi2 = x_inv^2 and x xi2 = is_real: the first row sends (k, x_inv) on `point_bus`
+    (domain_point_air receives it), which makes x_inv the inverse of g_(lvl+1)^bitrev(k, lvl) -- and the square of that point is
+    g_lvl^bitrev(k, lvl), the point of index k in the domain of 2^lvl points.  The is_last row RECEIVES (call, lvl, k, acc) on
+    `final_bus`: field by field what fri_query_air sends there.  With `coeff_bus` every row sends (poly, j, coef).  The flags follow
+    reduced_opening_air's skeleton (s = is_real - is_last).  docs/fri_final.md has the argument why a satisfying trace with balanced
+    buses fixes the comparison, and what the chip does not state (which proof `poly` names; lvl = log_blowup + log_final_poly_len)."""
+    assert 0 <= log_final_poly_len <= 8
+    L = 1 << log_final_poly_len
+    b = AirBuilder(FRI_FINAL_WIDTH, 0)
+    coef, acc = [b.var(i) for i in range(4)], [b.var(4 + i) for i in range(4)]
+    x, xinv, xi2, k, lvl, j, poly, first, last, real, call = (b.var(8 + i) for i in range(11))
+    n_coef, n_acc = [b.next(i) for i in range(4)], [b.next(4 + i) for i in range(4)]
+    n_x, n_xinv, n_k, n_lvl, n_j, n_poly, n_first, n_real, n_call = (b.next(c) for c in (8, 9, 11, 12, 13, 14, 15, 17, 18))
+    for f in (first, last, real):
+        b.assert_zero(f * (f - 1))
+    pad = 1 - real
+    b.assert_zero(first * pad)
+    b.assert_zero(last * pad)
+    b.when_first_row(first - real)
+    s = real - last
+    b.when_last_row(s)
+    b.when_transition(s * (n_real - 1))
+    b.when_transition(s * n_first)
+    b.when_transition(last * (n_real - n_first))
+    b.when_transition(pad * n_real)
+    for v, n_v in ((call, n_call), (poly, n_poly), (k, n_k), (lvl, n_lvl), (x, n_x), (xinv, n_xinv)):
+        b.when_transition(s * (n_v - v))
+    b.when_transition(s * (n_j - j + 1))
+    b.assert_zero(first * (j - (L - 1)))
+    b.assert_zero(last * j)
+    for i in range(4):
+        b.assert_zero(first * (acc[i] - coef[i]))
+    for i in range(4):
+        b.when_transition(s * (n_acc[i] - acc[i] * x - n_coef[i]))
+    b.assert_zero(xi2 - xinv * xinv)
+    b.assert_zero(x * xi2 - real)
+    b.push_interaction(point_bus, [k, xinv], first, "send")
+    b.push_interaction(final_bus, [call, lvl, k] + acc, last, "receive")
+    if coeff_bus is not None:
+        b.push_interaction(coeff_bus, [poly, j] + coef, real, "send")
+    return b
+
+
 def hasher_user_air(bus):
     """A chip that needs 2-to-1 compressions (a Merkle-path checker, say): columns left[8] | right[8] | out[8] | is_real;
     it sends (left, right, out) on `bus` when is_real = 1 and relies on the Poseidon2 chip to receive it, i.e. to
